@@ -3,6 +3,8 @@
 
   python bench.py                                   # headline: BASELINE configs[1], N = 1
   python bench.py --config 3|4|5                    # the bf16 configs (streaming 100 frames / 4 clips per GPU / 4K)
+  python bench.py --full                            # the headline plus every extra object listed below
+  python bench.py --dump-outputs DIR                # also write what the last timed step computed, as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus 8 --steps 20 --warmup 3 [--config 4]
 
@@ -16,7 +18,18 @@ config 4 four clips per rank, config 3 one 100-frame streamed sequence per rank.
 so ranks share nothing on the data path (weak scaling); the only collective is one RCCL all-reduce of the PSNR sums
 after the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run sets up, warms up, times --steps steps, writes the outputs if --dump-outputs is given and prints the line: the
+contract fields (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...), `config`, `collectives` and
+`psnr_reduce`.  `ms_per_step` is the wall time of one timed step (MAX over ranks).
+
+--dump-outputs DIR: after the timed region, the SR output tensors of the last timed step (what a caller of the path receives) as
+float32 DIR/<name>.npy: `sr` (clip mode, one call per step) or `sr_call<c>` (one per call), `sr_frame<iii>` (stream mode, one per
+frame call).  An output that does not fit its share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample instead: the flat
+elements at sorted indices drawn by numpy's default_rng(crc32(name)), the same for every run with the same arguments.  Inputs and
+weights are seeded (crfp_amd.synth), so two builds can be compared output for output.  With N > 1 ranks each rank writes
+DIR/rank<r>/.
+
+Extra objects on that line, with --full only (the --no-* switches below thin them out):
   roofline      dominant kernel family by GPU time: algorithmic flops (or bytes) / hipEvent-measured duration, from a
                 second, instrumented single-stream pass of the same steps (every launch bracketed by hipEvents on its
                 own stream inside libcrfp_hip.so: crfp_prof_*).  `traffic` = HBM bytes per launch from the committed
@@ -28,17 +41,17 @@ Extra objects on that line:
   cpu_baseline  the oracle (CPU port of the reference path; its bf16 twin for the bf16 configs) timed on this host:
                 1 warm-up + 1 timed pass over the config-2 clip (or a bounded sample of the bigger configs).
   parity        max|HIP - oracle| (bf16 configs: statistics against the twin) and PSNR-Y delta on that sample.
-  other_configs (default run only) BASELINE configs[2..4] -- `--config 3|4|5` -- each as a short leg (3 steps) in a child process
+  other_configs (default config only) BASELINE configs[2..4] -- `--config 3|4|5` -- each as a short leg (3 steps) in a child process
                 after the headline's timed region: frames/s, ms per step, parity against the bf16 twin on 3 frames, conv roofline.
-  runtime_rig   (default run only) the reference's test_runtime.py measurement: ms per 1080p frame of the regional wiring (one C-ABI call
+  runtime_rig   (default config only) the reference's test_runtime.py measurement: ms per 1080p frame of the regional wiring (one C-ABI call
                 per 5-frame clip) and of the whole-frame CRFP_DSV engine on the same rig.
   warp_dcn_8d   SURVEY 8(d)'s figure un-re-scoped: API-tensor bytes of flow_warp x3 + DCNv2 x4 per steady-state frame divided by
                 the time of ALL warp / DCN kernels of such a frame, the fused offset-head + DCN kernel included.
   lockstep_batch_frames_per_sec  (clip configs) n = 2 / 4 clips per crfp_dsv_forward_batch call (lock-step launches over the clips), bit-exactness against
                 one-clip calls; warp_dcn_8d_spec_weights: the 8(d) figure, frames/s and parity with SURVEY 8(d)'s own N(0, 0.02) DCN heads.
-  dcn_g8_alone  (default run only) the DCNv2 kernel of dcn_0/1/2 by itself: CRFP_DCN_FUSED=0 in a child process, SURVEY 8(d) API bytes / its time;
+  dcn_g8_alone  (default config only) the DCNv2 kernel of dcn_0/1/2 by itself: CRFP_DCN_FUSED=0 in a child process, SURVEY 8(d) API bytes / its time;
                 north_star_per_kernel lists every warp / DCN kernel's fraction of 8 TB/s against the 0.60 target.
-  mask_gate     (default run only) what the mask-gated launches skip on this workload and the headline with dense launches instead (child process,
+  mask_gate     (default config only) what the mask-gated launches skip on this workload and the headline with dense launches instead (child process,
                 CRFP_MASK_GATE=0): same output bits, the dense rate is what rounds 1-3 measured.
   cra_engine    (config 2) CRFP_DSV_CRA, the reference's cross-resolution-fusion wiring, on its own one-call schedule: frames/s and the
                 difference to the per-operator composition of the same model.
@@ -49,6 +62,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -59,6 +73,23 @@ sys.path.insert(0, ROOT)
 import benchlegs  # noqa: E402
 from benchlegs import (CONFIGS, HBM_PEAK_GBS, ROCPROF_NAMES, kernel_family, pmc_traffic, time_op,  # noqa: E402,F401
                                 warp_dcn_8d)
+
+DUMP_BUDGET_BYTES = 32 << 20   # all --dump-outputs files of one rank together
+
+
+def dump_outputs(outdir, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """Write {name: tensor} as float32 outdir/<name>.npy.  A tensor larger than its equal share of the budget is replaced by a fixed
+    sample: its flat elements at the sorted, de-duplicated indices default_rng(crc32(name)).integers(0, numel, share) (1-D)."""
+    os.makedirs(outdir, exist_ok=True)
+    share = max(1, budget_bytes // 4 // max(1, len(arrays)))
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() <= share:
+            a = t.detach().float().cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, flat.numel(), share))
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -78,11 +109,15 @@ def main():
                     "default 1, config 4: 2 -- independent clips fill each other's kernel tails, bit-identical results)")
     ap.add_argument("--batch-clips", type=int, default=None, help="clips per library call (clip mode): n > 1 = crfp_dsv_forward_batch, the n clips "
                     "in lock-step, one launch per layer (config 4: all 4 clips of a rank; bit-identical per clip to one-clip calls)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every extra object of the line (roofline, per-kernel table, "
+                    "cpu_baseline, parity, strict_f32, other configs, ...); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as float32 DIR/<name>.npy "
+                    "(a fixed seeded sample of outputs larger than their share of 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--no-resident", action="store_true", help="stream mode: do not set CRFP_DSV_INPUTS_RESIDENT")
     ap.add_argument("--no-extras", action="store_true", help="skip strict_f32 / multi-stream / per-op / other-config legs")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run: skip the short legs of BASELINE configs 3 / 4 / 5")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full at the default config: skip the short legs of BASELINE configs 3 / 4 / 5")
     ap.add_argument("--cpu-sample-frames", type=int, default=None)
     ap.add_argument("--cpu-timeout", type=float, default=420.0)
     args = ap.parse_args()
@@ -144,15 +179,21 @@ def main():
         # lets the library run the state-independent part of frame i beside frame i - 1 (same bits; --no-resident: the plain call pattern)
         model.inputs_resident = eng.inputs_resident = not args.no_resident
 
+    # stream mode hands the caller one output per frame call; the step keeps them all only when they are to be written out
+    keep_frames = mode == "stream" and args.dump_outputs is not None
+
     def step(e=None):
-        """one step of this rank; returns the last output tensor(s)"""
+        """one step of this rank; returns the last output tensor(s) (stream mode with --dump-outputs: every frame's output)"""
         if mode == "stream":
             lrs, fvs, _ = data[0]
             eng.clear_states()
             o = None
+            frames = []
             for i in range(t):
                 o = eng.stream_frame(lrs[0, i], fvs[0, i], mk8[0, i])
-            return [o]
+                if keep_frames:
+                    frames.append(o)
+            return frames if keep_frames else [o]
         if n_flight == 1:
             return [(e or eng).forward(*d) for d in data]
         outs = [None] * ncalls
@@ -184,6 +225,11 @@ def main():
     frames_per_step = t * clips
     assert not any(e.overflowed(stream=(mode == "stream")) for e in engs), "numerics guard fired on the benchmark clip"
 
+    if args.dump_outputs is not None:
+        named = ({f"sr_frame{i:03d}": o for i, o in enumerate(outs)} if mode == "stream" else
+                 {"sr": outs[0]} if len(outs) == 1 else {f"sr_call{c}": o for c, o in enumerate(outs)})
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), named)
+
     # PSNR reduction (the only collective of the path): raw squared-error sums of the last SR frame(s) against the synthetic
     # HR scene inside the fovea window (not a quality figure without trained weights: it exercises the reduction)
     last = outs[-1] if mode == "stream" else outs[-1][0, -1]
@@ -206,18 +252,19 @@ def main():
         **({"inputs_resident": bool(eng.inputs_resident)} if mode == "stream" else {})}, dist)
     result["frames_per_step_per_gpu"] = frames_per_step
 
-    # everything below adds objects to the line; the code of each leg lives in benchlegs.py
+    # everything below adds objects to the line (--full only); the code of each leg lives in benchlegs.py
     import types
     c = types.SimpleNamespace(args=args, cfg=cfg, custom=custom, dev=dev, rank=rank, world=world, mode=mode, storage=storage, t=t, h=h, w=w, fv=fv,
                               clips=clips, bclips=bclips, n_flight=n_flight, data=data, data1=data1, data_np=data_np, mk8=mk8 if mode == "stream" else None,
                               model=model, eng=eng, sdt=sdt, agg=agg, frames_per_step=frames_per_step, step=step, result=result, fam=None, extras=False)
-    if rank == 0 and not args.no_kernel_profile:
+    full = args.full
+    if full and rank == 0 and not args.no_kernel_profile:
         benchlegs.profile_objects(c)
 
-    extras = c.extras = rank == 0 and world == 1 and not args.no_extras
+    extras = c.extras = full and rank == 0 and world == 1 and not args.no_extras
     if extras and mode == "clip":
         benchlegs.leg_side_stream(c)
-    if rank == 0 and world == 1 and mode == "stream" and c.eng.inputs_resident:
+    if full and rank == 0 and world == 1 and mode == "stream" and c.eng.inputs_resident:
         benchlegs.leg_stream_without_resident(c)
     if extras and mode == "clip" and storage == "f32":
         benchlegs.leg_strict_f32(c)
@@ -252,7 +299,7 @@ def main():
     if extras and mode == "clip" and args.config == 2 and not custom and not args.no_other_configs and "warp_dcn" in result:
         benchlegs.leg_dcn_g8_alone(c)
 
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         benchlegs.leg_cpu_baseline(c)
 
     if rank == 0:

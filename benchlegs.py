@@ -522,7 +522,7 @@ def leg_other_configs(c):
     import subprocess
     others = {}
     for c in (3, 4, 5):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(c), "--steps", "3", "--warmup", "1", "--no-extras",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(c), "--steps", "3", "--warmup", "1", "--full", "--no-extras",
                "--cpu-sample-frames", "3", "--cpu-timeout", "240"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CRFP_FORCE_DIST")}
         try:
@@ -574,8 +574,8 @@ def leg_dcn_g8_alone(c):
     # kernel itself is measured here on the two-kernel path (CRFP_DCN_FUSED=0, read once per process -> child process): SURVEY 8(d)'s API
     # bytes (258.1 MB fp32 per launch @A) over the time of dcn_g8_pipe_kernel alone.
     import subprocess
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "3", "--warmup", "2", "--no-extras", "--no-cpu-baseline",
-           "--no-other-configs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--steps", "3", "--warmup", "2", "--full", "--no-extras",
+           "--no-cpu-baseline", "--no-other-configs"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CRFP_FORCE_DIST")}
     env["CRFP_DCN_FUSED"] = "0"
     alone = {"switch": "CRFP_DCN_FUSED=0 (two-kernel path: conv_mfma:dcn.offset_mask + dcn_g8_pipe_kernel), child process"}

@@ -36,6 +36,9 @@ sys.path.insert(0, ROOT)
 from crfp_amd import synth  # noqa: E402
 from oracle import crfp_oracle as orc  # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import golden_io  # noqa: E402  (goldens larger than a committed file may be are written in parts)
+
 
 def inject_stubs():
     class DCNv2(nn.Module):
@@ -204,11 +207,11 @@ def main():
         lrs, fvs, mks = synth.make_clip(seed=11, n=1, t=t, h=h, w=w, fv_size=fv, sigma_t=10.0)
         y = model(lrs=T(lrs), fvs=T(fvs), mks=T(mks))
         flows = model.compute_flow(T(lrs))[0]
-        np.savez_compressed(os.path.join(HERE, name + ".npz"), weights_seed=np.int64(SEED),
+        golden_io.save(name, dict(weights_seed=np.int64(SEED),
                             weights_sha256=np.array(synth.state_dict_digest(sdm)), y_only=np.bool_(y_only),
                             clip_seed=np.int64(11), fv_size=np.int64(fv), h=np.int64(h), w=np.int64(w),
                             t=np.int64(t), out=y.numpy(), flows=flows.numpy(),
-                            lrs_sha=np.array(synth.state_dict_digest({"lrs": lrs, "fvs": fvs, "mks": mks.astype(np.float32)})))
+                            lrs_sha=np.array(synth.state_dict_digest({"lrs": lrs, "fvs": fvs, "mks": mks.astype(np.float32)}))))
         print(name, "out", tuple(y.shape), "mean %.6f" % float(y.mean()), "flow absmax %.3f" % float(flows.abs().max()))
 
 
@@ -233,9 +236,9 @@ def main():
         if i == 5:
             sm.clear_states()
         outs.append(sm(T(lrs[:, i:i + 1]), T(fvs[:, i:i + 1]), T(mks[:, i:i + 1]), T(fgs[:, i:i + 1])).numpy())
-    np.savez_compressed(os.path.join(HERE, "stream_16x24_t7.npz"), weights_seed=np.int64(SEED), clip_seed=np.int64(13),
+    golden_io.save("stream_16x24_t7", dict(weights_seed=np.int64(SEED), clip_seed=np.int64(13),
                         h=np.int64(h), w=np.int64(w), t=np.int64(t), fv_size=np.int64(48), clear_at=np.int64(5),
-                        fgs=fgs, out=np.concatenate(outs, axis=1))
+                        fgs=fgs, out=np.concatenate(outs, axis=1)))
     print("stream_16x24_t7 out", np.concatenate(outs, axis=1).shape)
 
 

@@ -73,10 +73,10 @@ def main():
     rs = np.random.RandomState(6)
     fvs = torch.from_numpy(rs.uniform(0, 1, (1, t, 3, fv, fv)).astype(np.float32))
     out = net(lrs, fvs, warp_size=warp)
-    np.savez_compressed(os.path.join(HERE, "runtime_small.npz"), weights_seed=np.int64(SEED),
+    make_golden.golden_io.save("runtime_small", dict(weights_seed=np.int64(SEED),
                         weights_sha256=np.array(synth.state_dict_digest(sd)), keys=np.array(list(shapes)),
                         shapes=np.array([str(s) for s in shapes.values()]), lrs=lrs.numpy(), fvs=fvs.numpy(),
-                        warp=np.array(warp), out=out.numpy())
+                        warp=np.array(warp), out=out.numpy()))
     print(out.shape, float(out.mean()), float(out.abs().max()))
     # round 4: the calls the one-call engine does not take and the module mirror routes through its per-operator composition --
     # a model built with offset_prop=False (no conv_fuse / dcn_3.upsample parameters) and the default, oversized warp_size on a small
@@ -96,7 +96,7 @@ def main():
     extra["noprop.out"] = net2(lrs2, fvs2, warp_size=(96, 128)).numpy()
     extra["oversize.lrs"], extra["oversize.fvs"] = lrs2.numpy(), fvs2.numpy()
     extra["oversize.out"] = net(lrs2, fvs2).numpy()          # warp_size = the signature's default (1080, 1920) on a 128 x 192 frame
-    np.savez_compressed(os.path.join(HERE, "runtime_flags.npz"), **extra)
+    make_golden.golden_io.save("runtime_flags", extra)
     print({k: (v.shape if hasattr(v, "shape") else v) for k, v in extra.items()})
 
 

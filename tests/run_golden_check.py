@@ -9,9 +9,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from crfp_amd import synth  # noqa: E402
+import golden_io  # noqa: E402  (this file's directory is on sys.path)
 from crfp_amd.model import CRFP  # noqa: E402
 
-g = dict(np.load(os.path.join(ROOT, "tests", "golden", "dsv_20x36_t4.npz")))
+g = golden_io.load("dsv_20x36_t4")
 sd = synth.make_state_dict(int(g["weights_seed"]))
 geom = os.environ.get("CRFP_CHECK_GEOM")   # "h,w,t": a synthetic clip of another geometry (DIGEST only; MAXDIFF is then not against a golden)
 if geom:

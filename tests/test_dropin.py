@@ -1,9 +1,10 @@
 """CPU: the drop-in boundary as INTEGRATION.md documents it -- the `shim/` directory on PYTHONPATH makes the reference's
 entry scripts bind `model`, `dcn_v2` and `pytorch_memlab` to this build even when started from the reference's own
 checkout; `crfp_amd.option` / `crfp_amd.main` mirror option.py / main.py; the independent DCNv2 restatement agrees with
-the oracle.  Tests that need /root/reference skip when it is absent (it does not exist on the GPU box)."""
+the oracle.  What the tests need from the reference checkout (option.py's defaults, eval.sh's argument list, the checkout's module
+layout) is recorded in tests/golden/reference_cli.json (tests/golden/make_dropin_golden.py)."""
+import json
 import os
-import shlex
 import subprocess
 import sys
 import textwrap
@@ -12,11 +13,27 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout only exists in the build container")
 SHIM = os.path.join(ROOT, "shim")
+
+
+def _ref_cli():
+    with open(os.path.join(GOLDEN, "reference_cli.json")) as f:
+        return json.load(f)
+
+
+def _stand_in_checkout(root):
+    """A directory laid out like the reference's checkout (the recorded top-level modules and model/ files).  Its model files raise
+    when imported, so only the shim's finder can make `import model` succeed; the other modules are importable markers."""
+    g = _ref_cli()
+    os.makedirs(root / "model")
+    for f in g["model_files"]:
+        (root / "model" / f).write_text("raise ImportError('model/ of the checkout was imported: the shim did not win')\n")
+    for name in g["checkout_modules"]:
+        if not (root / name).exists():
+            (root / f"{name}.py").write_text("STAND_IN = True\n")
+    return str(root)
 
 
 def _run_in(cwd, code, extra_env=None):
@@ -27,13 +44,13 @@ def _run_in(cwd, code, extra_env=None):
     return r.stdout
 
 
-@needs_ref
 def test_shim_wins_from_the_reference_checkout(tmp_path):
     """`cd <reference> && PYTHONPATH=<repo>/shim python3 main.py` situation: sys.path[0] is the reference, which holds its
     own `model/`; the shim's finder must still win for model / dcn_v2 / pytorch_memlab and leave utils / dataset alone.
     Then the exact constructor call of main.py:34 (on the CPU device: modules only hold parameters) and the
     nn.DataParallel wrap of main.py:37-38."""
     fnet = tmp_path / "fnet.pth"
+    REF = _stand_in_checkout(tmp_path / "checkout")
     out = _run_in(REF, f"""
         import os, sys, importlib.util
         assert os.getcwd() == {REF!r} and sys.path[0] == ''
@@ -88,19 +105,14 @@ def test_cpu_forward_is_refused_not_emulated():
         m(lrs=torch.zeros(1, 2, 3, 8, 8), fvs=torch.zeros(1, 2, 3, 64, 64), mks=torch.zeros(1, 2, 1, 64, 64, dtype=torch.bool))
 
 
-@needs_ref
 def test_option_flags_match_the_reference():
     """Every flag of option.py:10-119 exists here with the same default, and eval.sh's argument list parses."""
-    code = "import sys, json; sys.argv=['x']; import option; print(json.dumps(vars(option.args)))"
-    r = subprocess.run([sys.executable, "-c", code], cwd=REF, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    import json
-    ref = json.loads(r.stdout)
+    g = _ref_cli()
+    ref = g["option_defaults"]
     from crfp_amd import option
     mine = vars(option.parse([]))
     assert mine == ref
-    eval_sh = open(os.path.join(REF, "eval.sh")).read()
-    argv = shlex.split(eval_sh.split("main.py", 1)[1].replace("\\\n", " "))
+    argv = g["eval_sh_argv"]
     a = option.parse(argv)
     assert a.eval and a.reset and a.FV_size == 96 and a.scale == 8 and a.N_frames == 15 and a.dataset == "Reds"
     assert set(option.USED) | set(option.IGNORED) == set(ref)

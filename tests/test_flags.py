@@ -8,14 +8,14 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+import golden_io
 
 T = torch.from_numpy
 
 
 @pytest.fixture(scope="module")
 def flags():
-    return dict(np.load(os.path.join(GOLDEN, "dsv_flags.npz")))
+    return golden_io.load("dsv_flags")
 
 
 def _kwargs(g, name):
@@ -101,7 +101,7 @@ def test_flag_combinations_behave_like_the_reference(flags):
 # ---- the regional runtime wiring (model/CRFP_runtime.py): calls the one-call engine does not take
 @pytest.fixture(scope="module")
 def rt_flags():
-    return dict(np.load(os.path.join(GOLDEN, "runtime_flags.npz")))
+    return golden_io.load("runtime_flags")
 
 
 def _rt_model(g, device, offset_prop, seed):

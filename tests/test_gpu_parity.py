@@ -11,7 +11,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from conftest import GOLDEN  # noqa: E402
+import golden_io  # noqa: E402
 
 T = torch.from_numpy
 
@@ -171,7 +171,7 @@ def _model(sd_np, y_only=False):
 @pytest.mark.parametrize("name", ["dsv_16x24_t3", "dsv_20x36_t4", "dsv_16x24_t2_yonly"])
 def test_full_forward_golden(name):
     from crfp_amd import synth
-    g = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    g = golden_io.load(name)
     y_only = bool(g["y_only"])
     sd = synth.make_state_dict(int(g["weights_seed"]), y_only=y_only)
     lrs, fvs, mks = synth.make_clip(int(g["clip_seed"]), 1, int(g["t"]), int(g["h"]), int(g["w"]),
@@ -249,7 +249,7 @@ def test_streaming_variant_golden():
     """reference model/CRFP_test.py MRCF_simple_v18 (one frame per call, fgs regional mask, clear_states)."""
     from crfp_amd import synth
     from crfp_amd.model import CRFP
-    g = dict(np.load(os.path.join(GOLDEN, "stream_16x24_t7.npz")))
+    g = golden_io.load("stream_16x24_t7")
     sd = synth.make_state_dict(int(g["weights_seed"]))
     t, h, w = int(g["t"]), int(g["h"]), int(g["w"])
     lrs, fvs, mks = synth.make_clip(int(g["clip_seed"]), 1, t, h, w, fv_size=int(g["fv_size"]), sigma_t=10.0)

@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import golden_io  # noqa: E402
 from conftest import GOLDEN  # noqa: E402
 
 T = torch.from_numpy
@@ -50,7 +51,7 @@ def test_streaming_through_one_reused_input_buffer():
     """A caller that refills ONE device buffer per input in place: the previous LR frame the engine hands to
     FNet must be its own copy (model/CRFP_test.py:2234-2238 clones it)."""
     from crfp_amd import synth
-    g = dict(np.load(os.path.join(GOLDEN, "stream_16x24_t7.npz")))
+    g = golden_io.load("stream_16x24_t7")
     sd = synth.make_state_dict(int(g["weights_seed"]))
     t, h, w = int(g["t"]), int(g["h"]), int(g["w"])
     lrs, fvs, mks = synth.make_clip(int(g["clip_seed"]), 1, t, h, w, fv_size=int(g["fv_size"]), sigma_t=10.0)
@@ -285,7 +286,7 @@ def test_runtime_variant_vs_reference_golden(orc, capsys):
     from crfp_amd import synth
     from crfp_amd.model import MRCF_runtime
     from oracle import runtime_oracle as ro
-    g = dict(np.load(os.path.join(GOLDEN, "runtime_small.npz")))
+    g = golden_io.load("runtime_small")
     m = MRCF_runtime.MRCF_simple_v18(mid_channels=32, y_only=False, hr_dcn=True, offset_prop=True, split_ratio=3,
                                      spynet_pretrained='pretrained_models/fnet.pth', device=dev())
     sd = synth.make_state_dict_like({k: tuple(v.shape) for k, v in m.state_dict().items()}, int(g["weights_seed"]))

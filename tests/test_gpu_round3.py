@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import golden_io
+
 pytestmark = pytest.mark.gpu
 
 T = torch.from_numpy
@@ -293,7 +295,7 @@ def test_runtime_engine_one_call_vs_reference_golden_and_oracle(orc):
     (tests/golden/runtime_small.npz), against the per-operator composition, and against the oracle at geometries the golden does
     not cover: window = whole frame, a window that is not a multiple of 64, ragged frame sizes, t = 1, y_only."""
     from oracle import runtime_oracle as ro
-    g = dict(np.load(os.path.join(ROOT, "tests", "golden", "runtime_small.npz")))
+    g = golden_io.load("runtime_small")
     m, sd = _runtime_model(int(g["weights_seed"]))
     lrs, fvs, warp = T(g["lrs"]).to(dev()), T(g["fvs"]).to(dev()), tuple(int(v) for v in g["warp"])
     out = m(lrs, fvs, warp_size=warp)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
 from conftest import ROOT
 
 from crfp_amd import synth
@@ -267,11 +268,10 @@ def test_regional_engine_tables_and_argument_errors(lib):
     from crfp_amd import _lib
     from crfp_amd.engine import RuntimeEngine
     from crfp_amd.model import MRCF_runtime
-    from conftest import GOLDEN
     m = MRCF_runtime.MRCF_simple_v18(mid_channels=32, y_only=False, hr_dcn=True, offset_prop=True, split_ratio=3, device=torch.device("cpu"))
     names = RuntimeEngine.param_names()
     assert len(names) == _lib.RT_NUM_PARAMS == 158 and names == list(m.state_dict().keys())
-    assert names == [str(k) for k in np.load(os.path.join(GOLDEN, "runtime_small.npz"))["keys"]]
+    assert names == [str(k) for k in golden_io.load("runtime_small")["keys"]]
     for i, (k, v) in enumerate(m.state_dict().items()):
         assert lib.crfp_rt_param_numel(i, 0) == v.numel(), k
     assert lib.crfp_rt_param_numel(names.index("conv_last.weight"), 1) == 1 * 4 * 9
@@ -318,6 +318,24 @@ def test_plain_c_host_runs_on_the_gpu(tmp_path):
     """examples/c_host_smoke.c: hipMalloc'ed buffers, crfp_flow_warp_f32 / crfp_upsample_bilinear_f32 / an argument error, from C."""
     r = subprocess.run([_build_c_host(tmp_path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "c_host_smoke: OK" in r.stdout, r.stdout + r.stderr
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: float32 <name>.npy; an output within its share of the budget is written whole (its shape kept), a larger
+    one as the elements at default_rng(crc32(name))'s sorted indices -- the same file on every run."""
+    import zlib
+    import bench
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    big = torch.linspace(0, 1, 10000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big}, budget_bytes=8000)
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and np.array_equal(s, small.numpy())
+    idx = np.unique(np.random.default_rng(zlib.crc32(b"big")).integers(0, 10000, 1000))
+    assert b.dtype == np.float32 and b.ndim == 1 and 900 < b.size <= 1000 and np.array_equal(b, big.numpy()[idx])
+    for n in ("small", "big"):
+        assert (tmp_path / "a" / f"{n}.npy").read_bytes() == (tmp_path / "b" / f"{n}.npy").read_bytes()
+    assert s.nbytes + b.nbytes <= 8000
 
 
 def test_bench_pmc_traffic_is_tagged_with_the_kernel_source_digest(tmp_path, monkeypatch):

@@ -10,6 +10,7 @@ import torch
 from crfp_amd import synth
 from oracle import crfp_oracle as orc
 
+import golden_io
 from conftest import GOLDEN
 
 T = torch.from_numpy
@@ -112,7 +113,7 @@ def test_metrics(ops_golden):
 
 @pytest.mark.parametrize("name", ["dsv_16x24_t3", "dsv_20x36_t4", "dsv_16x24_t2_yonly"])
 def test_full_forward(name):
-    g = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    g = golden_io.load(name)
     y_only = bool(g["y_only"])
     sd = synth.make_state_dict(int(g["weights_seed"]), y_only=y_only)
     assert synth.state_dict_digest(sd) == str(g["weights_sha256"])
@@ -127,7 +128,7 @@ def test_full_forward(name):
 
 def test_streaming_variant_with_regional_mask():
     """model/CRFP_test.py MRCF_simple_v18: one frame per call, fgs mask, clear_states mid-way."""
-    g = dict(np.load(os.path.join(GOLDEN, "stream_16x24_t7.npz")))
+    g = golden_io.load("stream_16x24_t7")
     sd = synth.make_state_dict(int(g["weights_seed"]))
     t, h, w = int(g["t"]), int(g["h"]), int(g["w"])
     lrs, fvs, mks = synth.make_clip(int(g["clip_seed"]), 1, t, h, w, fv_size=int(g["fv_size"]), sigma_t=10.0)
@@ -187,7 +188,7 @@ def test_runtime_variant_oracle_matches_reference_golden():
     from crfp_amd import synth
     from crfp_amd.model import MRCF_runtime
     from oracle import crfp_oracle as orc, runtime_oracle as ro
-    g = dict(np.load(os.path.join(GOLDEN, "runtime_small.npz")))
+    g = golden_io.load("runtime_small")
     m = MRCF_runtime.MRCF_simple_v18(mid_channels=32, y_only=False, hr_dcn=True, offset_prop=True, split_ratio=3,
                                      spynet_pretrained='pretrained_models/fnet.pth', device=torch.device("cpu"))
     shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}

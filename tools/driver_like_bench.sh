@@ -15,10 +15,13 @@ d = json.loads(lines[-1])
 print({k: d[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup",
                          "ms_per_step", "dtype", "scaling", "vs_baseline")})
 print(d["config"])
-r = d["roofline"]
-print("roofline", {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac")}, "traffic", r["traffic"])
-c = d["cpu_baseline"]
-print("cpu_baseline", c["value"], c["unit"], "cores", c["cores"], c["kind"])
+# roofline / cpu_baseline are on the line of `bench.py --full` only
+if "roofline" in d:
+    r = d["roofline"]
+    print("roofline", {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac")}, "traffic", r["traffic"])
+if "cpu_baseline" in d:
+    c = d["cpu_baseline"]
+    print("cpu_baseline", c["value"], c["unit"], "cores", c["cores"], c["kind"])
 for k in ("parity", "dcn_fused"):
     if k in d:
         print(k, d[k] if not isinstance(d[k], dict) else {a: b for a, b in d[k].items() if not isinstance(b, (dict, list))})
