@@ -92,7 +92,7 @@ for _n in ("packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batc
     SIGNATURES["crfp_cra_" + _n + "_bf16"] = SIGNATURES["crfp_dsv_" + _n]
 # the CRFP_simple / CRFP wirings (round 6): CRFP_DSV's parameter names, their own shapes / packed weights / workspace, the same forward call
 for _w in ("simple", "dense"):
-    for _n in ("param_numel", "packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batch_status_offset", "forward_batch"):
+    for _n in ("param_numel", "packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batch_status_offset", "forward_batch", "stream_batch"):
         SIGNATURES[f"crfp_{_w}_{_n}"] = SIGNATURES["crfp_dsv_" + _n]
         if _n != "param_numel":
             SIGNATURES[f"crfp_{_w}_{_n}_bf16"] = SIGNATURES["crfp_dsv_" + _n]

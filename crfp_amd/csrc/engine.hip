@@ -1504,24 +1504,31 @@ int CRFP_API(crfp_dsv_forward_clip)(const void* packed, int flags, const float* 
     return CRFP_API(crfp_dsv_forward_batch)(packed, flags, lrs, fvs, mks, out, 1, t, h, w, workspace, workspace_bytes, stream);
 }
 
+}  // extern "C"
+
 // One frame of n independent sequences in lock-step (the reference's streaming forward carries the batch axis too, model/CRFP_test.py:2250-2451):
 // lr / lr_prev [n,3,h,w], fv [n,3,8h,8w], mk [n,1,8h,8w], out [n,3|1,8h,8w]; the workspace holds the n recurrent states.
-int CRFP_API(crfp_dsv_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
-                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
-                          size_t workspace_bytes, void* stream) {
+// wiring: W_DSV (MRCF_simple_v18) or W_SIMPLE / W_DENSE (MRCF_simple_v13 / v15, model/CRFP_test.py:1184-1486 / 1805-2113: CRFP_simple / CRFP
+// with the state kept between calls).  Same clip kernels, same buffer sets, same two schedules for every wiring.
+static int stream_batch_impl(int wiring, const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                             const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                             size_t workspace_bytes, void* stream) {
     const int y_only = flags & CRFP_DSV_Y_ONLY;
     if (n < 1) { set_error("dsv_stream_batch: n = %d", n); return CRFP_E_BADARG; }
+    // v13 / v15 compute the regional mask's x0.25 resample fg_lv0 (model/CRFP_test.py:1357-1359, 1978-1980) but never read it; only v18
+    // scales by it (:2347,2361,2375).  `fg` is accepted and ignored there, for any n: no fg_prep launch, no fg branch in Runner::frame.
+    if (wiring != W_DSV) fg = nullptr;
     if (fg && n > 1) { set_error("dsv_stream_batch: the regional mask `fg` is supported for one sequence per call (n = 1)"); return CRFP_E_UNSUPPORTED; }
     if (n > kFlatFrames) { set_error("dsv_stream_batch: at most %d sequences per call (got %d)", kFlatFrames, n); return CRFP_E_UNSUPPORTED; }
     const int B = n;
     const long long lr_f = 3LL * h * w, fq = (long long)h * w * 4;
     if (kActBf16 && (flags & CRFP_DSV_STRICT_F32)) { set_error("dsv (bf16 storage): CRFP_DSV_STRICT_F32 belongs to the fp32 entry points"); return CRFP_E_UNSUPPORTED; }
-    Layout L(B, 1, h, w);
+    Layout L(B, 1, h, w, wiring);
     int rc = check_common(packed, B, 1, h, w, workspace, workspace_bytes, L);
     if (rc) return rc;
     const bool resident = (flags & CRFP_DSV_INPUTS_RESIDENT) != 0;
     if (!lr || !fv || !mk || !out || (!first && !resident && !lr_prev)) { set_error("dsv_stream_batch: null tensor"); return CRFP_E_BADARG; }
-    Runner R{model_for(y_only, flags & CRFP_DSV_STRICT_F32), (const float*)packed, (char*)workspace, L, (hipStream_t)stream};
+    Runner R{model_for(y_only, flags & CRFP_DSV_STRICT_F32, wiring), (const float*)packed, (char*)workspace, L, (hipStream_t)stream};
     R.strict = (flags & CRFP_DSV_STRICT_F32) ? 1 : 0;
     // one frame of every sequence: the call's arguments ARE the frames (batch stride = one frame); flows and encoder_lr features sit in the
     // first B slots / the parity's B slots of their stores
@@ -1653,6 +1660,28 @@ int CRFP_API(crfp_dsv_stream_batch)(const void* packed, int flags, const float* 
     if (hipStreamWaitEvent(main_s, ev_side, 0) != hipSuccess) return fail("join");
     R.frame(0, false, io, fg);
     return R.rc;
+}
+
+extern "C" {
+
+int CRFP_API(crfp_dsv_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return stream_batch_impl(W_DSV, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
+}
+
+// The same call for the reference's streaming MRCF_simple_v13 / v15 (the CRFP_simple / CRFP wirings): packed = the wiring's packed weights,
+// workspace sized by crfp_{simple,dense}_batch_workspace_bytes(n, 1, h, w); flags, n <= 32 and status words as crfp_dsv_stream_batch; `fg` is
+// accepted and ignored for any n.
+int CRFP_API(crfp_simple_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return stream_batch_impl(W_SIMPLE, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
+}
+int CRFP_API(crfp_dense_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return stream_batch_impl(W_DENSE, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
 }
 
 int CRFP_API(crfp_dsv_stream_frame)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,

@@ -461,7 +461,7 @@ class RuntimeEngine:
 class CRAEngine(DSVEngine):
     """Handle on the one-call schedule of the reference's CRFP_DSV_CRA wiring (crfp_cra_* entry points, include/crfp_hip.h): the same
     clip / lock-step batch forward, flags, status words and overflow policies as DSVEngine, over this wiring's own packed weights and
-    workspace.  Clip forward only: the reference's one-frame-per-call model (model/CRFP_test.py) is the plain CRFP_DSV."""
+    workspace.  Clip forward only: the reference's streaming form of this wiring (MRCF_simple_v18_cra) is commented out in test_video.py:187."""
 
     WIRING = "cra"
     MODEL_NAME = "CRFP_DSV_CRA"
@@ -477,7 +477,8 @@ class CRAEngine(DSVEngine):
         return getattr(_lib.lib(), fam + name[len("crfp_dsv_"):] + self._sfx)
 
     def stream_frame(self, *a, **k):
-        raise NotImplementedError("crfp_amd: the one-frame-per-call schedule exists for the plain CRFP_DSV wiring only")
+        raise NotImplementedError(f"crfp_amd: {type(self).__name__} is a clip handle; the one-frame-per-call schedules are DSVEngine's and, for "
+                                  "CRFP_simple / CRFP, SimpleStreamEngine's / DenseStreamEngine's (none for CRFP_DSV_CRA)")
 
     def compute_flow(self, cur, prev):
         raise NotImplementedError(f"crfp_amd: use the model's flow network modules ({self.MODEL_NAME}.compute_flow)")
@@ -501,3 +502,22 @@ class DenseEngine(SimpleEngine):
 
     WIRING = "dense"
     MODEL_NAME = "CRFP"
+
+
+class _StreamMixin:
+    """The one-frame-per-call schedule of the reference's streaming MRCF_simple_v13 / v15 (model/CRFP_test.py:1184-1486, 1805-2113): CRFP_simple /
+    CRFP with the state kept between calls.  ``stream_frame`` / ``clear_states`` are DSVEngine's -- the copy of the previous frame, the
+    ``inputs_resident`` checks and the overflow policies ("fallback" refused) -- on the wiring's own ``crfp_{simple,dense}_stream_batch``.  The
+    regional mask ``fg`` is accepted for any n and has no effect: these two models never read it."""
+
+    _CALLS = CRAEngine._CALLS + ("stream_batch",)
+    stream_frame = DSVEngine.stream_frame
+    clear_states = DSVEngine.clear_states
+
+
+class SimpleStreamEngine(_StreamMixin, SimpleEngine):
+    """SimpleEngine plus the streaming entry point crfp_simple_stream_batch (MRCF_simple_v13)."""
+
+
+class DenseStreamEngine(_StreamMixin, DenseEngine):
+    """DenseEngine plus the streaming entry point crfp_dense_stream_batch (MRCF_simple_v15)."""

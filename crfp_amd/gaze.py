@@ -146,10 +146,16 @@ def main(argv=None):
     ap.add_argument("--fv-size", type=int, default=96)
     ap.add_argument("--regional-dcn", type=int, default=0, help="side of the regional-DCN box in HR pixels (0 = whole frame)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--model-code", type=int, default=18, choices=(13, 15, 18),
+                    help="the streaming model test_video.py builds for this code: 13 MRCF_simple_v13, 15 MRCF_simple_v15, 18 MRCF_simple_v18")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
-    sd = synth.make_state_dict(7)
-    m = CRFP.MRCF_simple_v18(device=dev, mid_channels=32)
+    if a.model_code == 18:
+        sd = synth.make_state_dict(7)
+        m = CRFP.MRCF_simple_v18(device=dev, mid_channels=32)
+    else:   # the ablation wirings have other shapes under the same keys: weights seeded from the model's own table
+        m = getattr(CRFP, f"MRCF_simple_v{a.model_code}")(device=dev, mid_channels=32, y_only=False, hr_dcn=True, offset_prop=True)
+        sd = synth.make_state_dict_like({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()}, strict=True)
     m = m.to(dev).eval()
     chunk = 10   # synthetic frames are generated in chunks of correlated frames and the state carried across
@@ -175,7 +181,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     dt_model = time.perf_counter() - t0
     res.pop("per_frame"); res.pop("trajectory")
-    print(json.dumps({"workload": f"BASELINE config 3 shape: {a.frames} streamed frames {a.lr_h}x{a.lr_w} -> x8, sigma_T={a.sigma}, fp32, synthetic",
+    model = "" if a.model_code == 18 else f", {type(m).__name__}"
+    print(json.dumps({"workload": f"BASELINE config 3 shape: {a.frames} streamed frames {a.lr_h}x{a.lr_w} -> x8, sigma_T={a.sigma}, fp32, synthetic{model}",
                       "frames_per_sec_with_region_metrics": a.frames / dt, "frames_per_sec_model_only": a.frames / dt_model, **res}))
 
 

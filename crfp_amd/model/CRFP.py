@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from crfp_amd import ops
 from crfp_amd.dcn_v2 import DCNv2
-from crfp_amd.engine import CRAEngine, DenseEngine, DSVEngine, SimpleEngine
+from crfp_amd.engine import CRAEngine, DenseEngine, DenseStreamEngine, DSVEngine, SimpleEngine, SimpleStreamEngine
 from . import LTE
 
 
@@ -599,6 +599,11 @@ class CRFP_simple(nn.Module):
     @torch.no_grad()
     def forward_composed(self, lrs, fvs, mks):
         """The recurrence of model/CRFP.py:938-1079 (dense: :1223-1365) as a composition of per-operator HIP calls: every flag combination."""
+        return self._composed(lrs, fvs, mks)[0]
+
+    def _composed(self, lrs, fvs, mks, state=None, prev_lr=None):
+        """forward_composed's loop from a given recurrent state [n, last, 8h, 8w] and the LR frame [n, 3, h, w] in front of lrs[:, 0] (both None:
+        a clip starts from nothing) -> (out [n, t, 3|1, 8h, 8w], state after the last frame).  The streaming models carry the two between calls."""
         if lrs.dim() != 5 or not lrs.is_cuda:
             raise RuntimeError("crfp_amd: needs CUDA/HIP tensors lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], mks[n,t,1,8h,8w]")
         n, t, _, h, w = lrs.shape
@@ -606,7 +611,10 @@ class CRFP_simple(nn.Module):
         lrelu = lambda x: torch.nn.functional.leaky_relu(x, 0.1)   # noqa: E731
         lrs = lrs.float().contiguous()
         mkf = mks.to(torch.float32)
-        flows = self.compute_flow(lrs)[0] if t > 1 else None
+        # flows[:, i] belongs to frame i + 1 of the clip; with a previous frame it is prepended and frame i uses flows[:, i]
+        ext = lrs if prev_lr is None else torch.cat((prev_lr.float()[:, None], lrs), 1)
+        shift = 1 if prev_lr is None else 0
+        flows = self.compute_flow(ext)[0] if ext.shape[1] > 1 else None
         flat = lrs.reshape(n * t, 3, h, w)
         up8_all = ops.upsample_bilinear(flat, scale_factor=8)
         x_lr = self.encoder_lr(flat, islr=True)[2].view(n, t, m, h, w)
@@ -615,11 +623,10 @@ class CRFP_simple(nn.Module):
         blocks = (self.forward_resblocks_0, self.forward_resblocks_1, self.forward_resblocks_2)
         dcns = (self.dcn_0, self.dcn_1, self.dcn_2)
         rep = 2 if self.dense else 1                 # the dense variant hands the (warped) previous state to every block once more
-        state = None                                 # [n, last, 8h, 8w] after the first frame
-        outs = []
+        outs = []                                    # state: [n, last, 8h, 8w] after the first frame
         for i in range(t):
             cur = self.upsample(x_lr[:, i].contiguous())
-            if i == 0:
+            if state is None:
                 z2, z8 = lrs.new_zeros(n, m, 2 * h, 2 * w), lrs.new_zeros(n, l, 8 * h, 8 * w)
                 for block in blocks:
                     cur = block(torch.cat([cur] + [z2] * rep, 1))
@@ -629,7 +636,7 @@ class CRFP_simple(nn.Module):
                 else:
                     state = self.forward_resblocks_3(torch.cat([cur] + [z2] * rep, 1))
             else:
-                flow = flows[:, i - 1].contiguous()
+                flow = flows[:, i - shift].contiguous()
                 f2c = ops.upsample_bilinear(flow, scale_factor=2, mul=2.0)
                 f2 = f2c.permute(0, 2, 3, 1).contiguous()
                 if self.hr_dcn:      # warp at 8x, then both versions of the state to 2x (:1021-1026)
@@ -660,7 +667,7 @@ class CRFP_simple(nn.Module):
             lr = lrs[:, i]
             base = (0.299 * lr[:, 0] + 0.587 * lr[:, 1] + 0.114 * lr[:, 2]).unsqueeze(1) if self.y_only else lr
             outs.append(_run(self.conv_last, state) + ops.upsample_bilinear(base.contiguous(), scale_factor=8))
-        return torch.stack(outs, dim=1)
+        return torch.stack(outs, dim=1), state
 
 
 class CRFP(CRFP_simple):
@@ -683,3 +690,52 @@ class MRCF_simple_v18(CRFP_DSV):
 
     def forward(self, lrs, fvs, mks, fgs=None):
         return self.forward_stream(lrs, fvs, mks, fgs)
+
+
+class _AblationStream:
+    """One frame (or several) per call for the CRFP_simple / CRFP wirings: the reference's MRCF_simple_v13 / v15 (model/CRFP_test.py:1184-1486,
+    1805-2113) are those two models with the recurrent state and the previous LR frame kept on the model between calls, the previous frame
+    prepended to the flow pairs, and a ``fgs`` argument they compute a resample of but never use (:1357-1359, 1978-1980).  mid_channels 32
+    (16: embedded) with both flags on streams through the wiring's one-frame-per-call engine call (n > 1 sequences in lock-step, one call per
+    frame; ``storage`` and ``inputs_resident`` as on MRCF_simple_v18); every other constructor combination streams through the per-operator
+    composition with the state carried between calls."""
+
+    def __init__(self, device, mid_channels=16, y_only=False, hr_dcn=True, offset_prop=True, spynet_pretrained=None):
+        super().__init__(device, mid_channels, y_only, hr_dcn, offset_prop, spynet_pretrained)
+        self._stream_state = self._stream_prev = None   # composed path: state [n, last, 8h, 8w] and the last LR frame [n, 3, h, w]
+
+    def clear_states(self):
+        self._stream_state = self._stream_prev = None
+        if self._engine is not None:
+            self._engine.clear_states()
+
+    @torch.no_grad()
+    def forward(self, lrs, fvs, mks, fgs=None):
+        """lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], mks / fgs[n,t,1,8h,8w] -> [n,t,3|1,8h,8w], continuing the sequence of the previous call."""
+        if not self.has_engine():
+            out, self._stream_state = self._composed(lrs, fvs, mks, self._stream_state, self._stream_prev)
+            self._stream_prev = lrs[:, -1].float().clone()   # a copy, as the reference's pre_lrs (:1299-1304)
+            return out
+        eng = self.engine()
+        frames = [lrs, fvs, mks]
+        if eng.inputs_resident and not all(x[:, 0].is_contiguous() for x in frames):
+            # frame i of n > 1 sequences is a strided view: the copies are kernels on this stream that the library's side stream would not
+            # wait for (CRFP_DSV_INPUTS_RESIDENT) -- make them all first and let them finish
+            frames = [x.transpose(0, 1).contiguous().transpose(0, 1) for x in frames]
+            torch.cuda.current_stream().synchronize()
+        lrs, fvs, mks = frames
+        fg = (lambda i: None) if fgs is None else (lambda i: fgs[:, i].contiguous())   # noqa: E731   (accepted; the library never reads it)
+        outs = [eng.stream_frame(lrs[:, i].contiguous(), fvs[:, i].contiguous(), mks[:, i].contiguous(), fg(i)) for i in range(lrs.shape[1])]
+        return torch.stack(outs, dim=1)
+
+
+class MRCF_simple_v13(_AblationStream, CRFP_simple):
+    """The reference's streaming CRFP_simple (model/CRFP_test.py:1184-1486; test_video.py's model code 13): see _AblationStream."""
+
+    _engine_class = SimpleStreamEngine
+
+
+class MRCF_simple_v15(_AblationStream, CRFP):
+    """The reference's streaming CRFP (model/CRFP_test.py:1805-2113; test_video.py's model code 15): see _AblationStream."""
+
+    _engine_class = DenseStreamEngine

@@ -30,6 +30,8 @@
  *   crfp_fnet_*               model/CRFP.py:743-814  FNet.forward, :1483-1508 compute_flow
  *   crfp_dsv_*                model/CRFP.py:1387-1706 CRFP_DSV (ctor weights, forward) and the
  *                             one-frame-per-call variant model/CRFP_test.py:2114-2478
+ *   crfp_simple_* / crfp_dense_*  model/CRFP.py:816-1099 CRFP_simple / :1101-1385 CRFP (clip forward) and their
+ *                             one-frame-per-call variants model/CRFP_test.py:1184-1486 MRCF_simple_v13 / :1805-2113 v15
  *   crfp_psnr_partial_f32     utils.py:166-185,242-254,328-330 (psnr_cuda / bgr2ycbcr(y_only))
  *   crfp_spynet_forward       model/CRFP.py:554-741 SPyNet.forward (+ SPyNetBasicModule, `conv` :145-152)
  *   crfp_convkxk_f32          model/CRFP.py:145-152 `conv`: ReLU -> nn.Conv2d(k, stride 1, pad k/2)
@@ -280,6 +282,18 @@ size_t crfp_dense_batch_workspace_bytes(int n, int t, int h, int w);
 size_t crfp_dense_batch_status_offset(int n, int t, int h, int w);
 int crfp_dense_forward_batch(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
                              float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+/* Streaming forms of the two wirings: the reference's one-frame-per-call MRCF_simple_v13 / MRCF_simple_v15 (model/CRFP_test.py:1184-1486,
+ * 1805-2113), i.e. CRFP_simple / CRFP with the state kept between calls.  Arguments, flags (CRFP_DSV_INPUTS_RESIDENT included), the n <= 32
+ * limit and the status words of crfp_dsv_stream_batch; packed weights are the wiring's own, the workspace is sized by
+ * crfp_{simple,dense}_batch_workspace_bytes(n, 1, h, w) and its status words sit at crfp_{simple,dense}_batch_status_offset(n, 1, h, w).
+ * `fg` is accepted and ignored for any n: v13 / v15 compute its resample but never use it (:1357-1359, 1978-1980).  Streaming a clip one
+ * frame per call gives the clip call's bits. */
+int crfp_simple_stream_batch(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                             const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int crfp_dense_stream_batch(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                            const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ---- bf16 storage (BASELINE configs 3-5): the same engine with every activation tensor and the recurrent state held
  * as bf16 in HBM (half the traffic of the HBM-bound kernels, one bf16 MFMA per product instead of three fp16 ones).
@@ -322,6 +336,12 @@ size_t crfp_dense_batch_workspace_bytes_bf16(int n, int t, int h, int w);
 size_t crfp_dense_batch_status_offset_bf16(int n, int t, int h, int w);
 int crfp_dense_forward_batch_bf16(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
                                   float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+int crfp_simple_stream_batch_bf16(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                                  const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int crfp_dense_stream_batch_bf16(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                                 const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 int crfp_fnet_forward_bf16(const void* packed, const float* cur, const float* prev, float* flow, int n, int h, int w,
                            void* workspace, size_t workspace_bytes, void* stream);
 int crfp_dsv_debug_fetch_bf16(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,

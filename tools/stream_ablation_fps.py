@@ -1,0 +1,50 @@
+"""frames/s of the one-frame-per-call schedules of the reference's three streaming models -- MRCF_simple_v13 (CRFP_simple), MRCF_simple_v15
+(CRFP) and MRCF_simple_v18 (CRFP_DSV), mid_channels 32 -- at BASELINE config 3's frame size (180 x 320 -> 1440 x 2560), fp32 and bf16 storage,
+with and without inputs_resident, in one process on one box.  The frames sit on the device before the timed loop (a decoded video held in
+HBM); each pass streams `calls` frames, cycling over 10 distinct ones, after clear_states().
+usage: python tools/stream_ablation_fps.py [calls] [passes]"""
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, ".")
+from crfp_amd import synth  # noqa: E402
+from crfp_amd.model import CRFP  # noqa: E402
+
+
+def main():
+    calls = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    passes = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    dev = torch.device("cuda:0")
+    lrs, fvs, mks = (torch.from_numpy(a).to(dev) for a in synth.make_clip(3, 1, 10, 180, 320, fv_size=96))
+    mks = mks.bool()
+    torch.cuda.synchronize()
+    frames = [(lrs[:, i:i + 1], fvs[:, i:i + 1], mks[:, i:i + 1]) for i in range(10)]
+    for cls in ("MRCF_simple_v13", "MRCF_simple_v15", "MRCF_simple_v18"):
+        m = getattr(CRFP, cls)(dev, mid_channels=32)
+        sd = synth.make_state_dict(7) if cls.endswith("18") else synth.make_state_dict_like({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7)
+        m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()}, strict=True)
+        m = m.to(dev).eval()
+        for storage in ("f32", "bf16"):
+            for resident in (False, True):
+                m.storage, m.inputs_resident = storage, resident
+                rates = []
+                with torch.no_grad():
+                    for p in range(passes + 1):          # pass 0: warm-up (packing, workspace, side stream)
+                        m.clear_states()
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for i in range(calls):
+                            m(*frames[i % 10])
+                        torch.cuda.synchronize()
+                        if p:
+                            rates.append(calls / (time.perf_counter() - t0))
+                    assert not m.engine().overflowed(stream=True)
+                print(f"{cls} storage={storage} resident={int(resident)} calls={calls} frames_per_sec median={statistics.median(rates):.1f} "
+                      f"passes={[round(r, 1) for r in rates]}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
