@@ -1,0 +1,246 @@
+"""Large, steered motion for the gather kernels and the engines (pure numpy / torch on the CPU; test infrastructure only).
+
+Why steered.  ``synth.make_state_dict`` gives flows of |f| < 2 LR pixels.  Scaling ``spynet.flow.2`` up does not help: the flow of random
+FNet weights is smooth and nearly one-signed, so the whole frame leaves the image as the gain rises, and the gain multiplies the conv
+round-off in front of tanh * 256.  Here the flow network is turned into a known function of the frames' colours instead
+(``steer_fnet``), and the frames are painted so that this function takes the targets one asks for (``steered_frames``):
+
+    flow_x = 256 tanh(g blur(R - G)),    flow_y = 256 tanh(g blur(B - R_prev))
+
+with ``blur`` = FNet's three 2x2 average pools followed by its three bilinear x2 resizes (and the final resize to h x w).
+
+The float64 references of the operator tests (``warp_ref64``; DCN is tests/dcn_paper_ref.py, with ``dcn_ref64`` as its fast form) sample at
+``index + flow`` directly -- no [-1, 1] normalisation, no grid_sample -- so the fp32 round-off of the oracle's coordinate path is not part
+of the yardstick.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from crfp_amd import synth  # noqa: E402
+
+G_DEFAULT = 2.0
+# regime -> M of the engine-level tests.  CLIP_SEED was picked on the CPU oracle so that the regime conditions hold at every geometry the tests
+# use, for the fp32 flow and for the flow of the bf16 twin (seeds 3 and 4 miss one under bf16 storage; 8 keeps 0.045 of margin everywhere);
+# tests/test_motion_cases.py re-checks both.  Pick another seed rather than loosen a condition.
+REGIMES = {"moderate": 24.0, "large": 60.0, "saturating": 2000.0}
+CLIP_SEED = 8
+
+
+# ----------------------------------------------------------------------------- steered flow network and frames
+def steer_fnet(sd, g=G_DEFAULT):
+    """A copy of a ``synth.make_state_dict`` / ``make_state_dict_like`` dict with every ``spynet.*`` tensor replaced: biases and weights zero,
+    except a centre-tap identity on channels 0..3 in every FNet conv but ``flow.2`` (channels 0-2 carry the current frame's R, G, B, channel 3
+    the previous frame's R; all >= 0, so the ReLUs pass them) and ``flow.2`` = g * (ch0 - ch1), g * (ch2 - ch3).  Everything else is untouched."""
+    out = type(sd)()
+    for k, v in sd.items():
+        if not k.startswith("spynet."):
+            out[k] = v
+            continue
+        z = np.zeros_like(v)
+        if k.endswith(".weight"):
+            if k == "spynet.flow.2.weight":
+                z[0, 0, 1, 1], z[0, 1, 1, 1], z[1, 2, 1, 1], z[1, 3, 1, 1] = g, -g, g, -g
+            else:
+                for c in range(4):
+                    z[c, c, 1, 1] = 1.0
+        out[k] = z
+    return out
+
+
+def steered_frames(seed, t, h, w, M, g=G_DEFAULT, blk=8):
+    """lrs[1,t,3,h,w], fvs, mks as ``synth.make_clip`` gives them (fovea 64, or 48 on maps less than 20 rows high), with the LR frames
+    repainted in blk x blk blocks: every block of every frame draws flow targets fx, fy ~ U(-M, M), z = atanh(clip(f / 256, +-0.999)) / g,
+    R ~ U(0.3, 0.7), G = clip(R - zx, 0, 1), B = clip(R_prev + zy, 0, 1) (frame 0, which has no flow: B = R)."""
+    rs = np.random.RandomState(seed)
+    _, fvs, mks = synth.make_clip(seed, 1, t, h, w, fv_size=64 if min(h, w) >= 20 else 48, sigma_t=10.0)
+    nby, nbx = -(-h // blk), -(-w // blk)
+    grow = lambda a: np.kron(a, np.ones((blk, blk)))[:h, :w]   # noqa: E731
+    lrs = np.zeros((1, t, 3, h, w), np.float32)
+    r_prev = None
+    for i in range(t):
+        fx, fy = rs.uniform(-M, M, (nby, nbx)), rs.uniform(-M, M, (nby, nbx))
+        zx = np.arctanh(np.clip(fx / 256.0, -0.999, 0.999)) / g
+        zy = np.arctanh(np.clip(fy / 256.0, -0.999, 0.999)) / g
+        r = rs.uniform(0.3, 0.7, (nby, nbx))
+        gch = np.clip(r - zx, 0.0, 1.0)
+        bch = r if r_prev is None else np.clip(r_prev + zy, 0.0, 1.0)
+        lrs[0, i] = np.stack([grow(r), grow(gch), grow(bch)]).astype(np.float32)
+        r_prev = r
+    return lrs, fvs, mks
+
+
+def steered_case(regime, t, h, w, seed=CLIP_SEED, y_only=False, weights_seed=7):
+    """(state dict with the steered flow network, lrs, fvs, mks) of one regime."""
+    sd = steer_fnet(synth.make_state_dict(weights_seed, y_only=y_only))
+    return (sd,) + steered_frames(seed, t, h, w, REGIMES[regime])
+
+
+def flow_stats(flow, h, w):
+    """flow[..., 2, h, w] in pixels (x, y) -> in-frame share (-1 < x + fx < w and -1 < y + fy < h), share of max(|fx|, |fy|) > 8 (and > 16),
+    share of positive values per component, absolute maximum."""
+    f = flow.detach().cpu().double().numpy() if isinstance(flow, torch.Tensor) else np.asarray(flow, np.float64)
+    f = f.reshape(-1, 2, h, w)
+    px, py = np.arange(w).reshape(1, 1, w) + f[:, 0], np.arange(h).reshape(1, h, 1) + f[:, 1]
+    mag = np.maximum(np.abs(f[:, 0]), np.abs(f[:, 1]))
+    return {"in_frame": float(((px > -1) & (px < w) & (py > -1) & (py < h)).mean()),
+            "over8": float((mag > 8).mean()), "over16": float((mag > 16).mean()),
+            "pos": (float((f[:, 0] > 0).mean()), float((f[:, 1] > 0).mean())), "absmax": float(np.abs(f).max())}
+
+
+def fmt_stats(s):
+    return (f"in-frame {s['in_frame']:.2f}, >8 px {s['over8']:.2f}, >16 px {s['over16']:.2f}, x+ {s['pos'][0]:.2f}, y+ {s['pos'][1]:.2f}, "
+            f"max {s['absmax']:.1f} px")
+
+
+def assert_regime(s, regime):
+    """The regime conditions: conditions on the flow a test really uses, not measurements."""
+    if regime == "saturating":
+        assert s["in_frame"] <= 0.05 and s["absmax"] >= 200.0, s
+        return
+    assert 0.15 <= s["in_frame"] <= 0.85, s
+    assert s["over8"] >= 0.5, s
+    assert all(0.2 <= p <= 0.8 for p in s["pos"]), s
+
+
+# ----------------------------------------------------------------------------- float64 operator references
+def _bilinear64(x, px, py, border):
+    """x[c, h, w] float64 sampled at (px, py)[h, w]: four corners with bilinear weights; zeros mode drops each out-of-range corner, border mode
+    clamps the coordinate first."""
+    c, h, w = x.shape
+    if border:
+        px, py = np.clip(px, 0.0, w - 1.0), np.clip(py, 0.0, h - 1.0)
+    x0, y0 = np.floor(px), np.floor(py)
+    lx, ly = px - x0, py - y0
+    out = np.zeros((c,) + px.shape, np.float64)
+    for dy, dx, wt in ((0, 0, (1 - ly) * (1 - lx)), (0, 1, (1 - ly) * lx), (1, 0, ly * (1 - lx)), (1, 1, ly * lx)):
+        yy, xx = y0 + dy, x0 + dx
+        ok = (yy >= 0) & (yy <= h - 1) & (xx >= 0) & (xx <= w - 1)
+        yi, xi = np.clip(yy, 0, h - 1).astype(np.int64), np.clip(xx, 0, w - 1).astype(np.int64)
+        out += x[:, yi, xi] * (wt * ok)
+    return out
+
+
+def warp_ref64(x, flow, padding_mode="zeros"):
+    """flow_warp in float64: x[n,c,h,w], flow[n,h,w,2] (dx, dy); output pixel (y, x) samples the input at (x + dx, y + dy)."""
+    x, flow = np.asarray(x, np.float64), np.asarray(flow, np.float64)
+    n, c, h, w = x.shape
+    xs, ys = np.arange(w, dtype=np.float64).reshape(1, w), np.arange(h, dtype=np.float64).reshape(h, 1)
+    return np.stack([_bilinear64(x[b], xs + flow[b, ..., 0], ys + flow[b, ..., 1], padding_mode == "border") for b in range(n)])
+
+
+def dcn_ref64(x, offset, mask, weight, bias, dg):
+    """DCNv2 3x3 / pad 1 in float64 by corner sampling (``_bilinear64``): a fast stand-in for tests/dcn_paper_ref.py on maps where the paper
+    form's dense hat matrices are too slow; test_motion_cases.py holds the two together."""
+    x, offset, mask = np.asarray(x, np.float64), np.asarray(offset, np.float64), np.asarray(mask, np.float64)
+    weight, bias = np.asarray(weight, np.float64), np.asarray(bias, np.float64)
+    B, C, H, W = x.shape
+    O, cpg = weight.shape[0], C // dg
+    xs, ys = np.arange(W, dtype=np.float64).reshape(1, W), np.arange(H, dtype=np.float64).reshape(H, 1)
+    out = np.zeros((B, O, H, W)) + bias.reshape(1, O, 1, 1)
+    for b in range(B):
+        for g in range(dg):
+            for k in range(9):
+                py = ys + (k // 3 - 1) + offset[b, 2 * (g * 9 + k)]
+                px = xs + (k % 3 - 1) + offset[b, 2 * (g * 9 + k) + 1]
+                val = _bilinear64(x[b, g * cpg:(g + 1) * cpg], px, py, False) * mask[b, g * 9 + k]
+                out[b] += np.einsum("oc,cyx->oyx", weight[:, g * cpg:(g + 1) * cpg, k // 3, k % 3], val)
+    return out
+
+
+# ----------------------------------------------------------------------------- operator inputs
+def edge_targets(size):
+    """Sample coordinates on and next to the range checks of an axis of `size` pixels: -1, -1 +- 2^-10, -0.5, 0, 0.5, size-1, size-1 +- 2^-10, size."""
+    e = 2.0 ** -10
+    return [-1.0, -1.0 - e, -1.0 + e, -0.5, 0.0, 0.5, size - 1.0, size - 1.0 - e, size - 1.0 + e, float(size)]
+
+
+def _draw(rs, R, idx, size, keep):
+    """Displacements U(-R, R) per element of `idx` (the element's own coordinate on an axis of `size` pixels); where `keep` is set the draw is
+    U(-R, R) conditioned on the sample landing in (-1, size) -- uniform on the intersection of the two intervals, which is never empty."""
+    d = rs.uniform(-R, R, idx.shape)
+    lo, hi = np.maximum(-R, -1.0 - idx), np.minimum(R, size - idx)
+    return np.where(keep, lo + (hi - lo) * rs.uniform(0.02, 0.98, idx.shape), d)
+
+
+def planted_flow(seed, n, h, w, R, keep_share=0.45):
+    """flow[n,h,w,2] float32 (dx, dy) from U(-R, R); on a random `keep_share` of the pixels the draw is conditioned on landing in the frame (a field
+    of plain U(-64, 64) draws leaves a 9 x 11 map on 99 % of its pixels, and a kernel that returns zeros would pass).  Planted rows: at the four
+    corners and in the middle of the map, runs of pixels whose sample coordinate is exactly one of ``edge_targets`` -- first in x (y in
+    the frame), then in y, then in both."""
+    rs = np.random.RandomState(seed)
+    xs, ys = np.broadcast_to(np.arange(w, dtype=np.float64), (n, h, w)), np.broadcast_to(np.arange(h, dtype=np.float64).reshape(h, 1), (n, h, w))
+    keep = rs.uniform(0, 1, (n, h, w)) < keep_share
+    flow = np.stack([_draw(rs, R, xs, w, keep), _draw(rs, R, ys, h, keep)], -1).astype(np.float32).astype(np.float64)
+    tx, ty = edge_targets(w), edge_targets(h)
+    for (y0, x0) in ((0, 0), (0, w - 5), (h - 6, 0), (h - 6, w - 5), (h // 2 - 3, w // 2 - 2)):
+        for j in range(30):
+            y, x = y0 + j // 5, x0 + j % 5
+            kind, which = divmod(j, 10)
+            if kind in (0, 2):
+                flow[:, y, x, 0] = tx[which] - x
+            if kind in (1, 2):
+                flow[:, y, x, 1] = ty[which] - y
+    flow = flow.astype(np.float32)
+    # the planted coordinates are exact in fp32 as well (index + flow: small integers and multiples of 2^-10)
+    assert np.array_equal((flow[:, 0, 0:5, 0].astype(np.float64) + np.arange(5))[0], np.array(tx[:5]))
+    return flow
+
+
+def planted_offsets(seed, n, groups, h, w, R, keep_share=0.45):
+    """DCN offsets[n, 2 * groups, h, w] float32 with channels (dy, dx) interleaved per (deformable group, tap), as ``planted_flow``: `groups` =
+    dg * 9 for ``ops.dcnv2`` (the tap's own grid displacement is part of the sample coordinate), 1 for ``ops.dcnv2_shared`` (planted for the
+    centre tap).  The planted rows move with the channel, so that every edge target meets every tap."""
+    rs = np.random.RandomState(seed)
+    off = np.zeros((n, 2 * groups, h, w), np.float64)
+    xs, ys = np.broadcast_to(np.arange(w, dtype=np.float64), (n, h, w)), np.broadcast_to(np.arange(h, dtype=np.float64).reshape(h, 1), (n, h, w))
+    tx, ty = edge_targets(w), edge_targets(h)
+    for gk in range(groups):
+        k = gk % 9 if groups > 1 else 4
+        gy, gx = k // 3 - 1, k % 3 - 1
+        keep = rs.uniform(0, 1, (n, h, w)) < keep_share
+        dy, dx = _draw(rs, R, ys + gy, h, keep), _draw(rs, R, xs + gx, w, keep)
+        dy, dx = dy.astype(np.float32).astype(np.float64), dx.astype(np.float32).astype(np.float64)
+        for (y0, x0) in ((0, 0), (0, w - 5), (h - 6, 0), (h - 6, w - 5), (h // 2 - 3, w // 2 - 2)):
+            for j in range(30):
+                y, x = y0 + j // 5, x0 + j % 5
+                kind, which = divmod(j, 10)
+                which = (which + gk) % 10
+                if kind in (0, 2):
+                    dx[:, y, x] = tx[which] - (x + gx)
+                if kind in (1, 2):
+                    dy[:, y, x] = ty[which] - (y + gy)
+        off[:, 2 * gk], off[:, 2 * gk + 1] = dy, dx
+    return off.astype(np.float32)
+
+
+def ulp32(v):
+    """Spacing of float32 at |v|."""
+    return float(np.spacing(np.float32(abs(v))))
+
+
+def max_adjacent_diff(x, zero_pad=True):
+    """max |x[.., i] - x[.., i + 1]| over both axes of x[n,c,h,w]; with ``zero_pad`` the zero frame around the map counts as pixels (a sample
+    between -1 and 0 interpolates between the padding and pixel 0: its slope is |x[0]|)."""
+    x = np.asarray(x, np.float64)
+    if zero_pad:
+        x = np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)))
+    return float(max(np.abs(np.diff(x, axis=2)).max(), np.abs(np.diff(x, axis=3)).max()))
+
+
+def coord_rounding_term(x, px, py, zero_pad=True):
+    """The fp32 coordinate-rounding term of the operator bound.  The kernels form the sample coordinate ``index + displacement`` in fp32, the
+    float64 reference forms it exactly: the two differ by at most half an fp32 ulp of the coordinate.  A bilinear interpolant moves by at most
+    (largest difference of two adjacent pixels) per unit of coordinate, and only samples that land in the frame, -1 < p < size, see the image at
+    all, so   term = 1/2 ulp32(max |coord| over in-frame samples) * max |adjacent-pixel difference of x|.   px, py: float64 coordinates."""
+    h, w = x.shape[-2:]
+    inside = (px > -1) & (px < w) & (py > -1) & (py < h)
+    if not inside.any():
+        return 0.0, 0.0
+    cmax = float(max(np.abs(px[inside]).max(), np.abs(py[inside]).max()))
+    return 0.5 * ulp32(cmax) * max_adjacent_diff(x, zero_pad), float(inside.mean())

@@ -15,9 +15,17 @@ from crfp_amd.model import CRFP  # noqa: E402
 g = golden_io.load("dsv_20x36_t4")
 sd = synth.make_state_dict(int(g["weights_seed"]))
 geom = os.environ.get("CRFP_CHECK_GEOM")   # "h,w,t": a synthetic clip of another geometry (DIGEST only; MAXDIFF is then not against a golden)
+motion = os.environ.get("CRFP_CHECK_MOTION")   # "M" (with CRFP_CHECK_GEOM, DIGEST only): steered flow network and frames with flow targets U(-M, M) LR pixels
+if motion and not geom:
+    raise SystemExit("CRFP_CHECK_MOTION needs CRFP_CHECK_GEOM")
 if geom:
     gh, gw, gt = (int(v) for v in geom.split(","))
-    lrs, fvs, mks = synth.make_clip(4321, 1, gt, gh, gw, fv_size=48)
+    if motion:
+        from helpers import motion_cases  # noqa: E402
+        sd = motion_cases.steer_fnet(sd)
+        lrs, fvs, mks = motion_cases.steered_frames(motion_cases.CLIP_SEED, gt, gh, gw, float(motion))
+    else:
+        lrs, fvs, mks = synth.make_clip(4321, 1, gt, gh, gw, fv_size=48)
     g["out"] = np.zeros((1, gt, 3, 8 * gh, 8 * gw), np.float32)
 else:
     lrs, fvs, mks = synth.make_clip(int(g["clip_seed"]), 1, int(g["t"]), int(g["h"]), int(g["w"]), fv_size=int(g["fv_size"]))

@@ -1,0 +1,172 @@
+"""CPU: pins tests/helpers/motion_cases.py -- the steered flow network and frames give the motion regimes the GPU tests rely on, the float64
+operator references agree with the oracle and with the paper form of DCNv2, and the references would notice wrong out-of-range handling."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import dcn_paper_ref
+from helpers import motion_cases as mc
+
+T = torch.from_numpy
+GEOMS = [(24, 40), (33, 47)]
+SHAPES = [(9, 11), (23, 45), (64, 96)]
+
+
+@pytest.fixture(scope="module")
+def orc():
+    from oracle import crfp_oracle
+    return crfp_oracle
+
+
+@pytest.fixture(autouse=True)
+def _nograd():
+    with torch.no_grad():
+        yield
+
+
+@pytest.mark.parametrize("regime,h,w", [(r, h, w) for r in mc.REGIMES for (h, w) in GEOMS] + [("large", 17, 65)])
+def test_steered_regimes_through_the_oracle(orc, regime, h, w):
+    sd, lrs, fvs, mks = mc.steered_case(regime, 3, h, w)
+    P = orc.load_numpy_state(sd)
+    flow = orc.compute_flow(P, T(lrs))
+    s = mc.flow_stats(flow, h, w)
+    print(f"{regime} {h}x{w}: {mc.fmt_stats(s)}")
+    mc.assert_regime(s, regime)
+    with orc.bf16_storage():      # the flow of the bf16-storage engine: colours rounded to 8 bits in front of tanh * 256 move it by up to a pixel
+        s16 = mc.flow_stats(orc.compute_flow(orc.bf16_weights(P), T(lrs)), h, w)
+    print(f"{regime} {h}x{w}, bf16 twin: {mc.fmt_stats(s16)}")
+    mc.assert_regime(s16, regime)
+    assert fvs.shape == (1, 3, 3, 8 * h, 8 * w) and mks.shape == (1, 3, 1, 8 * h, 8 * w) and mks.any()
+    assert lrs.min() >= 0.0 and lrs.max() <= 1.0
+
+
+def test_steered_flow_is_the_stated_function_of_the_frames(orc):
+    """flow_x = 256 tanh(g blur(R - G)), flow_y = 256 tanh(g blur(B - R_prev)); only the spynet.* tensors change."""
+    from crfp_amd import synth
+    base = synth.make_state_dict(7)
+    sd = mc.steer_fnet(base, g=2.0)
+    assert list(sd) == list(base)
+    for k in base:
+        if k.startswith("spynet."):
+            assert np.count_nonzero(sd[k]) == (0 if k.endswith(".bias") else 4) and sd[k].shape == base[k].shape, k
+        else:
+            assert sd[k] is base[k], k
+    h, w = 33, 47
+    lrs = T(mc.steered_frames(mc.CLIP_SEED, 3, h, w, 60.0)[0])
+    flow = orc.compute_flow(orc.load_numpy_state(sd), lrs)[0]
+
+    def blur(v):
+        for _ in range(3):
+            v = F.avg_pool2d(v, 2, 2)
+        for _ in range(3):
+            v = F.interpolate(v, scale_factor=2, mode="bilinear", align_corners=False)
+        return v
+
+    cur, prev = lrs[0, 1:], lrs[0, :-1]
+    z = torch.stack([blur(cur[:, 0:1]) - blur(cur[:, 1:2]), blur(cur[:, 2:3]) - blur(prev[:, 0:1])], 1)[:, :, 0]
+    want = F.interpolate(256.0 * torch.tanh(2.0 * z), size=(h, w), mode="bilinear", align_corners=False)
+    assert float((flow - want).abs().max()) < 1e-3      # pixels; fp32 sums in another order in front of tanh * 256
+
+
+def test_large_motion_reaches_the_output(orc):
+    """Under the large regime the warped tensors are neither empty nor full, so an engine test compares more than zeros with zeros."""
+    h, w = 24, 40
+    sd, lrs, fvs, mks = mc.steered_case("large", 2, h, w)
+    P, cfg = orc.load_numpy_state(sd), orc.DSVConfig()
+    flow = orc.compute_flow(P, T(lrs))
+    st = orc.new_state(cfg, 1, h, w, T(lrs))
+    _, st = orc.dsv_frame(P, cfg, st, T(lrs)[:, 0], T(fvs)[:, 0], T(mks)[:, 0], None)
+    taps = {}
+    with orc.tapping(taps):
+        orc.dsv_frame(P, cfg, st, T(lrs)[:, 1], T(fvs)[:, 1], T(mks)[:, 1], flow[:, 0])
+    for name in ("prev2w", "prevhrw", "carryw"):
+        share = float((taps[name] != 0).float().mean())
+        print(f"{name}: {share:.2f} non-zero")
+        assert 0.1 <= share <= 0.9, (name, share)
+
+
+def test_wrong_padding_mode_would_fail_the_injected_flow_test(orc):
+    """The guard of the engine test: the same two frames with the warps' out-of-range corners clamped to the border instead of dropped move
+    the output by far more than the 1e-4 the engine is held to."""
+    h, w = 24, 40
+    sd, lrs, fvs, mks = mc.steered_case("large", 2, h, w)
+    P, cfg = orc.load_numpy_state(sd), orc.DSVConfig()
+    flow = orc.compute_flow(P, T(lrs))
+    _, st = orc.dsv_frame(P, cfg, orc.new_state(cfg, 1, h, w, T(lrs)), T(lrs)[:, 0], T(fvs)[:, 0], T(mks)[:, 0], None)
+    keep = {k: (list(v) if isinstance(v, list) else v) for k, v in st.items()}
+    good, _ = orc.dsv_frame(P, cfg, st, T(lrs)[:, 1], T(fvs)[:, 1], T(mks)[:, 1], flow[:, 0])
+    real = orc.flow_warp
+    orc.flow_warp = lambda x, f, padding_mode="zeros": real(x, f, "border")
+    try:
+        bad, _ = orc.dsv_frame(P, cfg, keep, T(lrs)[:, 1], T(fvs)[:, 1], T(mks)[:, 1], flow[:, 0])
+    finally:
+        orc.flow_warp = real
+    d = float((good - bad).abs().max())
+    print(f"zeros vs border warps, frame 1 of the large clip: max|delta| = {d:.3e}")
+    assert d > 100 * 1e-4
+
+
+@pytest.mark.parametrize("h,w", SHAPES)
+@pytest.mark.parametrize("R", [9.0, 64.0, 2058.0])
+def test_planted_inputs(h, w, R):
+    """U(-R, R) in range and in float32, every edge target present in x and in y, at least 20 % of the samples in the frame for R <= 64."""
+    flow = mc.planted_flow(5, 2, h, w, R)
+    assert flow.dtype == np.float32 and np.abs(flow).max() <= max(R, w + 1.0)
+    px, py = np.arange(w) + flow[..., 0].astype(np.float64), np.arange(h).reshape(h, 1) + flow[..., 1].astype(np.float64)
+    for t in mc.edge_targets(w):
+        assert (px == t).any(), t
+    for t in mc.edge_targets(h):
+        assert (py == t).any(), t
+    inside = ((px > -1) & (px < w) & (py > -1) & (py < h)).mean()
+    assert inside >= (0.2 if R <= 64 else 0.0)
+    if R > 64 and min(h, w) < 60:
+        assert inside <= 0.5
+    off = mc.planted_offsets(6, 1, 18, h, w, R)
+    assert off.shape == (1, 36, h, w) and off.dtype == np.float32
+    sy = np.arange(h).reshape(h, 1) + 1 + off[0, 2 * 8].astype(np.float64)      # tap 8 = (+1, +1)
+    sx = np.arange(w) + 1 + off[0, 2 * 8 + 1].astype(np.float64)
+    assert (sy == -1.0).any() or (sy == float(h)).any() or (sy == h - 1.0).any()
+    assert (sx == -1.0).any() or (sx == float(w)).any() or (sx == w - 1.0).any()
+
+
+@pytest.mark.parametrize("mode", ["zeros", "border"])
+def test_warp_ref64_against_the_oracle_and_its_guard(orc, mode):
+    """The float64 restatement agrees with the oracle's grid_sample route where that route is accurate (small motion), and the two padding
+    modes are far apart under large motion: a kernel that clamped in zeros mode (or the reverse) cannot pass the operator test."""
+    rs = np.random.RandomState(2)
+    x = rs.standard_normal((2, 4, 23, 45)).astype(np.float32)
+    small = rs.uniform(-3, 3, (2, 23, 45, 2)).astype(np.float32)
+    assert np.abs(mc.warp_ref64(x, small, mode) - orc.flow_warp(T(x), T(small), mode).double().numpy()).max() < 2e-5
+    big = mc.planted_flow(3, 2, 23, 45, 64.0)
+    other = "border" if mode == "zeros" else "zeros"
+    assert np.abs(mc.warp_ref64(x, big, mode) - orc.flow_warp(T(x), T(big), other).double().numpy()).max() > 1.0
+    # exact coordinates: a sample at -1 or at W is zero in zeros mode and pixel 0 / W - 1 in border mode
+    f = np.zeros((1, 23, 45, 2), np.float32)
+    f[0, :, 0, 0], f[0, :, 44, 0] = -1.0, 1.0
+    r = mc.warp_ref64(x[:1], f, mode)
+    want = np.zeros_like(x[0, :, :, 0]) if mode == "zeros" else x[0, :, :, 0]
+    assert np.array_equal(r[0, :, :, 0], want.astype(np.float64)) and np.array_equal(r[0, :, :, 1:44], x[0, :, :, 1:44].astype(np.float64))
+
+
+@pytest.mark.parametrize("C,O,dg,h,w,R", [(8, 12, 2, 9, 11, 64.0), (32, 32, 8, 23, 45, 9.0), (8, 12, 2, 23, 45, 2058.0)])
+def test_dcn_ref64_is_the_paper_form(C, O, dg, h, w, R):
+    """``dcn_ref64`` (corner sampling, used on the 64 x 96 maps where the paper form's dense hat matrices take 13 s) against
+    tests/dcn_paper_ref.py on planted offsets: the same function to float64 round-off."""
+    rs = np.random.RandomState(C + h)
+    x = rs.standard_normal((1, C, h, w))
+    off = mc.planted_offsets(7, 1, dg * 9, h, w, R)
+    m = rs.uniform(0, 1, (1, dg * 9, h, w))
+    wt, b = rs.standard_normal((O, C, 3, 3)) * 0.2, rs.standard_normal(O)
+    assert np.abs(mc.dcn_ref64(x, off, m, wt, b, dg) - dcn_paper_ref.dcnv2_paper(x, off, m, wt, b, dg)).max() < 1e-12
+
+
+def test_coord_rounding_term():
+    assert mc.ulp32(1.5) == 2.0 ** -23 and mc.ulp32(96.0) == 2.0 ** -17 and mc.ulp32(2058.0) == 2.0 ** -12
+    x = np.zeros((1, 1, 4, 4)); x[0, 0, 0, 0] = 3.0; x[0, 0, 2, 2] = -1.0; x[0, 0, 2, 3] = 1.5
+    assert mc.max_adjacent_diff(x, zero_pad=False) == 3.0 and mc.max_adjacent_diff(x) == 3.0
+    x[0, 0, 0, 0] = 0.0
+    assert mc.max_adjacent_diff(x, zero_pad=False) == 2.5
+    px, py = np.array([[-5.0, 2.5, 3.75]]), np.array([[0.0, 0.0, 100.0]])
+    term, share = mc.coord_rounding_term(x, px, py)
+    assert term == 0.5 * 2.0 ** -22 * 2.5 and abs(share - 1 / 3) < 1e-12     # only (2.5, 0) is in the frame
