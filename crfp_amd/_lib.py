@@ -54,6 +54,8 @@ SIGNATURES = {
     "crfp_fovea_head_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "crfp_fovea_head_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_psnr_ssim_partial_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 2 + [C.c_void_p]),
+    "crfp_window_scores_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "crfp_window_scores_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_dsv_param_name": (C.c_char_p, [C.c_int]),
     "crfp_dsv_param_numel": (C.c_int, [C.c_int, C.c_int]),
     "crfp_dsv_packed_weight_bytes": (C.c_size_t, [C.c_int]),

@@ -393,6 +393,18 @@ int crfp_psnr_ssim_partial_f32(const float* a, const float* b, const unsigned ch
     return launch_psnr_ssim_partial(a, b, mask, acc, n, c, h, w, mul, add, (hipStream_t)stream);
 }
 
+size_t crfp_window_scores_workspace_bytes(int n) { return window_scores_workspace_bytes(n); }
+
+int crfp_window_scores_f32(const float* hr, const float* sr, float* psnr, float* ssim, int n, int c, int h, int w, int k, int stride,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!hr || !sr || !psnr || !ssim) { set_error("window_scores: null pointer"); return CRFP_E_BADARG; }
+    if (n < 1 || c < 1 || k < 1 || stride < 1 || k > h || k > w) { set_error("window_scores: bad argument (need n, c, k, stride >= 1 and k <= h, w)"); return CRFP_E_BADARG; }
+    if (k > 16) { set_error("window_scores: kernel_size > 16 is not implemented"); return CRFP_E_UNSUPPORTED; }
+    if (n > 65535) { set_error("window_scores: more than 65535 images per call"); return CRFP_E_UNSUPPORTED; }
+    if (!workspace || workspace_bytes < crfp_window_scores_workspace_bytes(n)) { set_error("window_scores: workspace too small"); return CRFP_E_BADARG; }
+    return launch_window_scores(hr, sr, psnr, ssim, n, c, h, w, k, stride, (float*)workspace, (hipStream_t)stream);
+}
+
 int crfp_psnr_partial_f32(const float* a, const float* b, double* acc, int n, int c, int h, int w, void* stream) {
     if (!a || !b || !acc || n < 1 || c < 1 || h < 1 || w < 1) { set_error("psnr_partial: bad argument"); return CRFP_E_BADARG; }
     return launch_psnr_partial(a, b, acc, n, c, h, w, (hipStream_t)stream);

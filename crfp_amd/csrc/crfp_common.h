@@ -467,5 +467,8 @@ int launch_cra_blend(const float* y, long long y_b, const float* fused, long lon
 int launch_psnr_ssim_partial(const float* a, const float* b, const uint8_t* mask, double* acc, int N, int C, int H, int W,
                              float mul, float add, hipStream_t s);
 int launch_psnr_partial(const float* a, const float* b, double* acc, int N, int C, int H, int W, hipStream_t s);
+size_t window_scores_workspace_bytes(int N);
+int launch_window_scores(const float* hr, const float* sr, float* psnr, float* ssim, int N, int C, int H, int W, int k, int stride,
+                         float* part, hipStream_t s);
 
 }  // namespace CRFP_NS

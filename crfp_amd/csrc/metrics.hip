@@ -1,4 +1,6 @@
-// Masked PSNR + SSIM partial sums in one pass over an image pair.
+// Image-quality metrics of the eval path, two kernel families.
+//
+// 1. psnr_ssim_partial_kernel: masked PSNR + SSIM partial sums in one pass over an image pair.
 // Replaces utils.calc_psnr_and_ssim_cuda -> psnr_cuda / ssim_cuda / _ssim (reference utils.py:166-185,187-240,242-254):
 //   x' = x*mul + add                              (the data-dependent range conversion of utils.py:244-250, chosen by the host)
 //   mse  = sum_c,p m(p) (a'-b')^2 / (sum_p m(p) * C)
@@ -6,6 +8,13 @@
 //          C1 = 0.01^2, C2 = 0.03^2 (image range [0,1]).
 // The reference filters with the 121-tap outer-product window; here the window is applied separably (rows, then columns) in
 // fp32 -- same weights g[i]*g[j] up to fp32 rounding order.  acc[0] += sum m (a'-b')^2, acc[1] += sum m S, acc[2] += sum m.
+//
+// 2. window_probe_kernel + window_scores_kernel: the foveated score maps of the video rig (reference test_video.py:23-63
+// foveated_metric -> the batch_avg=True branches of utils.py:166-172,197-221,242-254): PSNR and mean SSIM of every k x k window at
+// stride s, each window treated as an image of its own (zero padding at the WINDOW's border).  The reference unfolds both images
+// (300 floats per window) and runs five grouped convolutions over the patches; here a workgroup keeps one channel of a tile of the
+// image pair in LDS, nothing per window is ever written to memory, and the data-dependent range conversion is decided on the
+// device (no host synchronisation).
 #include "crfp_common.h"
 
 namespace crfp {
@@ -78,18 +87,212 @@ __global__ __launch_bounds__(256) void psnr_ssim_partial_kernel(const float* __r
     }
 }
 
+static void ssim_window(SsimWin& win) {
+    // utils.gaussian(11, 1.5): float32 tensor of exp(...) normalised by its float32 sum
+    float g[11], sum = 0.0f;
+    for (int x = 0; x < 11; ++x) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); }
+    for (int x = 0; x < 11; ++x) sum += g[x];
+    for (int x = 0; x < 11; ++x) win.g[x] = g[x] / sum;
+}
+
 int launch_psnr_ssim_partial(const float* a, const float* b, const uint8_t* mask, double* acc, int N, int C, int H, int W,
                              float mul, float add, hipStream_t s) {
     SsimWin win;
-    {   // utils.gaussian(11, 1.5): float32 tensor of exp(...) normalised by its float32 sum
-        float g[11], sum = 0.0f;
-        for (int x = 0; x < 11; ++x) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); }
-        for (int x = 0; x < 11; ++x) sum += g[x];
-        for (int x = 0; x < 11; ++x) win.g[x] = g[x] / sum;
-    }
+    ssim_window(win);
     ProfScope prof("psnr_ssim_partial", s, (double)N * C * H * W * 8.0, (double)N * C * H * W * 2.0 * 5 * 22);
     dim3 grid((W + SW - 1) / SW, (H + SH - 1) / SH, N * C);
     psnr_ssim_partial_kernel<<<grid, 256, 0, s>>>(a, b, mask, acc, C, H, W, mul, add, win);
+    CRFP_CHECK_LAUNCH();
+    return 0;
+}
+
+
+// ---------------------------------------------------------------------------------------------------- window score maps
+constexpr int WS_THREADS = 256;
+constexpr int WS_PROBE_BLOCKS = 256;   // partial (min, max) pairs per image; = WS_THREADS so that one load per thread folds them
+constexpr int WS_KMAX = 16;            // largest window side (the accumulators of one window column live in registers)
+constexpr int WS_PIX = 4096;           // LDS floats per image for the pixel tile of one channel (16 KiB each)
+constexpr int WS_ITEMS = 1280;         // (window, column) pairs per workgroup: 128 windows of 10 columns = 5 full passes of 256 lanes
+
+// torch.min / torch.max semantics: a NaN wins and stays
+__device__ __forceinline__ float ws_min(float a, float b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ float ws_max(float a, float b) { return (b > a || b != b) ? b : a; }
+
+// (min, max) of the pixels of `b` that some window covers (rows < hc, columns < wc), all channels of image blockIdx.y:
+// stage one of two, one pair per workgroup into part[n][WS_PROBE_BLOCKS][2]; window_scores_kernel folds the pairs.
+__global__ __launch_bounds__(WS_THREADS) void window_probe_kernel(const float* __restrict__ b, float* __restrict__ part,
+                                                                  int C, int H, int W, int hc, int wc) {
+    __shared__ float red[2][WS_THREADS / 64];
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const float* pb = b + (long long)n * C * H * W;
+    float mn = pb[0], mx = mn;   // pixel (0, 0) is covered by window (0, 0)
+    for (int row = blockIdx.x; row < C * hc; row += WS_PROBE_BLOCKS) {
+        const int c = row / hc, r = row - c * hc;
+        const float* pr = pb + ((long long)c * H + r) * W;
+        for (int x = tid; x < wc; x += WS_THREADS) { const float v = pr[x]; mn = ws_min(mn, v); mx = ws_max(mx, v); }
+    }
+    for (int o = 32; o > 0; o >>= 1) { mn = ws_min(mn, __shfl_down(mn, o)); mx = ws_max(mx, __shfl_down(mx, o)); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = mn; red[1][tid >> 6] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < WS_THREADS / 64; ++i) { mn = ws_min(mn, red[0][i]); mx = ws_max(mx, red[1][i]); }
+        float* o = part + ((long long)n * WS_PROBE_BLOCKS + blockIdx.x) * 2;
+        o[0] = mn; o[1] = mx;
+    }
+}
+
+struct WinScoreArgs {
+    int C, H, W, k, s, Hr, Wr;     // image, window side, stride, score-map size
+    int twx, twy, cols, rows;      // windows per workgroup tile; its pixel tile = (twy-1)*s+k rows of (twx-1)*s+k columns
+    float floor_db;                // PSNR of a window with mse == 0 (utils.py:171)
+    SsimWin win;
+};
+
+// One workgroup = twy x twx windows of image blockIdx.z.  Per channel: the pixel tile of both images goes to LDS (rows
+// coalesced, range-converted on load); then one lane per (window, column x) walks the window's k rows: the row-filtered
+// a, b, a^2, b^2, ab at (r, x) from <= 11 LDS taps (truncated at the window's border = the reference's zero padding of the
+// patch), pushed at once into the <= 11 column accumulators they belong to (registers; rows and columns fully unrolled so
+// that every gaussian weight is an immediate).  After the last row the lane owns the SSIM map of its column; it adds the
+// column's sum of S and of (a-b)^2 to its own LDS slot.  After the last channel one lane per window adds the k slots in
+// order and writes the two scores: one store each, no atomics.
+__global__ __launch_bounds__(WS_THREADS) void window_scores_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                   const float* __restrict__ part, float* __restrict__ psnr,
+                                                                   float* __restrict__ ssim, WinScoreArgs A) {
+    __shared__ float ta[WS_PIX], tb[WS_PIX];
+    __shared__ double pse[WS_ITEMS], pss[WS_ITEMS];
+    __shared__ float red[2][WS_THREADS / 64];
+    const int tid = threadIdx.x, n = blockIdx.z;
+    const int k = A.k, s = A.s, cols = A.cols;
+    // ---- range conversion of utils.py:244-250 from the probe's partial pairs (every workgroup folds the same 256 pairs in the same order)
+    float mn = part[((long long)n * WS_PROBE_BLOCKS + tid) * 2], mx = part[((long long)n * WS_PROBE_BLOCKS + tid) * 2 + 1];
+    for (int o = 32; o > 0; o >>= 1) { mn = ws_min(mn, __shfl_down(mn, o)); mx = ws_max(mx, __shfl_down(mx, o)); }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = mn; red[1][tid >> 6] = mx; }
+    __syncthreads();
+    mn = red[0][0]; mx = red[1][0];
+    for (int i = 1; i < WS_THREADS / 64; ++i) { mn = ws_min(mn, red[0][i]); mx = ws_max(mx, red[1][i]); }
+    const float span = mx - mn;
+    const int mode = span > 2.0f ? 2 : (span > 1.0f ? 1 : 0);   // NaN span: no conversion, as the reference's comparisons
+
+    const int wx0 = blockIdx.x * A.twx, wy0 = blockIdx.y * A.twy;
+    const int px0 = wx0 * s, py0 = wy0 * s;
+    const int nwx = min(A.twx, A.Wr - wx0), nwy = min(A.twy, A.Hr - wy0);      // windows of this tile that exist
+    const int ucols = (nwx - 1) * s + k, urows = (nwy - 1) * s + k;              // pixels they cover: inside the image by construction
+    const int items = nwx * nwy * k;
+    const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+    for (int c = 0; c < A.C; ++c) {
+        const float* pa = a + ((long long)n * A.C + c) * A.H * A.W;
+        const float* pb = b + ((long long)n * A.C + c) * A.H * A.W;
+        if (c) __syncthreads();   // the previous channel's lanes are done with the tile
+        for (int i = tid; i < urows * ucols; i += WS_THREADS) {
+            const int r = i / ucols, x = i - r * ucols;
+            const long long g = (long long)(py0 + r) * A.W + px0 + x;
+            float va = pa[g], vb = pb[g];
+            if (mode == 2) { va = va / 255.0f; vb = vb / 255.0f; }
+            else if (mode == 1) { va = (va + 1.0f) * 0.5f; vb = (vb + 1.0f) * 0.5f; }
+            ta[r * cols + x] = va; tb[r * cols + x] = vb;
+        }
+        __syncthreads();
+        for (int it = tid; it < items; it += WS_THREADS) {
+            const int wl = it / k, x = it - wl * k;
+            const int wyl = wl / nwx, wxl = wl - wyl * nwx;
+            const int base = wyl * s * cols + wxl * s;
+            float wr[11]; int qo[11];        // row taps of column x: weight (0 outside the window) and tile offset
+#pragma unroll
+            for (int j = 0; j < 11; ++j) {
+                const int q = x - 5 + j;
+                const bool in = q >= 0 && q < k;
+                wr[j] = in ? A.win.g[j] : 0.0f;
+                qo[j] = base + (in ? q : x);
+            }
+            float acc[WS_KMAX][5];
+#pragma unroll
+            for (int y = 0; y < WS_KMAX; ++y)
+#pragma unroll
+                for (int q = 0; q < 5; ++q) acc[y][q] = 0.0f;
+            double se = 0.0;
+#pragma unroll
+            for (int r = 0; r < WS_KMAX; ++r) {
+                if (r < k) {
+                    const int ro = r * cols;
+                    float h0 = 0, h1 = 0, h2 = 0, h3 = 0, h4 = 0;
+#pragma unroll
+                    for (int j = 0; j < 11; ++j) {
+                        const float va = ta[ro + qo[j]], vb = tb[ro + qo[j]], g = wr[j];
+                        h0 = fmaf(g, va, h0); h1 = fmaf(g, vb, h1);
+                        h2 = fmaf(g, va * va, h2); h3 = fmaf(g, vb * vb, h3); h4 = fmaf(g, va * vb, h4);
+                    }
+                    const float d = ta[ro + base + x] - tb[ro + base + x];
+                    se += (double)(d * d);
+#pragma unroll
+                    for (int y = 0; y < WS_KMAX; ++y) {
+                        if (y - r <= 5 && r - y <= 5) {     // compile-time: the column taps of row r
+                            const float g = A.win.g[r - y + 5];
+                            acc[y][0] = fmaf(g, h0, acc[y][0]); acc[y][1] = fmaf(g, h1, acc[y][1]);
+                            acc[y][2] = fmaf(g, h2, acc[y][2]); acc[y][3] = fmaf(g, h3, acc[y][3]);
+                            acc[y][4] = fmaf(g, h4, acc[y][4]);
+                        }
+                    }
+                }
+            }
+            double ss = 0.0;
+#pragma unroll
+            for (int y = 0; y < WS_KMAX; ++y) {
+                if (y < k) {
+                    const float mu1 = acc[y][0], mu2 = acc[y][1];
+                    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+                    const float s1 = acc[y][2] - mu1_sq, s2 = acc[y][3] - mu2_sq, s12 = acc[y][4] - mu12;
+                    ss += (double)(((2.0f * mu12 + C1) * (2.0f * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2)));
+                }
+            }
+            // the same lane owns slot `it` for every channel
+            pse[it] = c ? pse[it] + se : se;
+            pss[it] = c ? pss[it] + ss : ss;
+        }
+    }
+    __syncthreads();
+    const double cnt = (double)A.C * k * k;
+    for (int wl = tid; wl < nwx * nwy; wl += WS_THREADS) {
+        double se = 0.0, ss = 0.0;
+        for (int x = 0; x < k; ++x) { se += pse[wl * k + x]; ss += pss[wl * k + x]; }
+        const int wyl = wl / nwx, wxl = wl - wyl * nwx;
+        const long long o = ((long long)n * A.Hr + wy0 + wyl) * A.Wr + wx0 + wxl;
+        // every square is an fp32 number and their sum is exact enough in double that se == 0 <=> the fp32 sum is 0 <=> all are 0
+        psnr[o] = se == 0.0 ? A.floor_db : (float)(-10.0 * log10(se / cnt));
+        ssim[o] = (float)(ss / cnt);
+    }
+}
+
+size_t window_scores_workspace_bytes(int N) { return N < 1 ? 0 : (size_t)N * WS_PROBE_BLOCKS * 2 * sizeof(float); }
+
+// hr, sr: [N,C,H,W]; psnr, ssim: [N,Hr,Wr].  The caller has checked 1 <= k <= WS_KMAX, k <= H, k <= W, s >= 1.
+int launch_window_scores(const float* hr, const float* sr, float* psnr, float* ssim, int N, int C, int H, int W, int k, int stride,
+                         float* part, hipStream_t s) {
+    WinScoreArgs A;
+    A.C = C; A.H = H; A.W = W; A.k = k; A.s = stride;
+    A.Hr = (H - k) / stride + 1; A.Wr = (W - k) / stride + 1;
+    ssim_window(A.win);
+    A.floor_db = (float)(-20.0 * log10(sqrt((1.0 / 255.0) * (1.0 / 255.0) / ((double)C * k * k))));
+    // the tile: as many windows as the LDS budget holds (1 x 1 always fits: k*k <= 256), then the fewest pixels, then the widest rows
+    long long best = -1;
+    A.twx = A.twy = 1;
+    for (int ty = 1; ty <= std::min(A.Hr, 64); ++ty)
+        for (int tx = 1; tx <= std::min(A.Wr, 64); ++tx) {
+            const long long pc = (long long)(tx - 1) * stride + k, pr = (long long)(ty - 1) * stride + k;
+            if (pc * pr > WS_PIX || tx * ty * k > WS_ITEMS) break;   // wider tiles of this row only grow
+            const long long score = ((long long)tx * ty << 32) + ((long long)(WS_PIX - pc * pr) << 8) + tx;
+            if (score > best) { best = score; A.twx = tx; A.twy = ty; }
+        }
+    A.cols = (A.twx - 1) * stride + k; A.rows = (A.twy - 1) * stride + k;
+    const int hc = (A.Hr - 1) * stride + k, wc = (A.Wr - 1) * stride + k;
+    const double px = (double)N * C * H * W, wins = (double)N * A.Hr * A.Wr;
+    {
+        ProfScope prof("window_probe", s, px * 4.0, px * 2.0);
+        window_probe_kernel<<<dim3(WS_PROBE_BLOCKS, N), WS_THREADS, 0, s>>>(sr, part, C, H, W, hc, wc);
+        CRFP_CHECK_LAUNCH();
+    }
+    ProfScope prof("window_scores", s, px * 8.0 + wins * 8.0, wins * C * k * k * 2.0 * (8.0 * 11 + 5.0 * 11));
+    dim3 grid((A.Wr + A.twx - 1) / A.twx, (A.Hr + A.twy - 1) / A.twy, N);
+    window_scores_kernel<<<grid, WS_THREADS, 0, s>>>(hr, sr, part, psnr, ssim, A);
     CRFP_CHECK_LAUNCH();
     return 0;
 }

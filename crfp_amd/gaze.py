@@ -11,6 +11,8 @@ Per frame n (one model call, state kept on the device between calls):
     mk_past = union of the last three mk_out, as it was BEFORE this frame's ring is pushed (:371-375);
     fg = the regional-DCN box of rg x rg pixels around the window centre, or all ones (:351-358).
   * metrics = utils.calc_psnr_and_ssim_cuda(sr, gt, mask) for whole / fovea / outskirt / past (:360-370), arithmetic mean.
+  * score maps (optional) = utils.foveated_metric(.., kernel_size=10, stride_size=5) of the model output and of a baseline frame
+    against the ground truth (:381-384), and the running extrema the rig keeps from the baseline's call (:385-392).
 """
 from __future__ import annotations
 
@@ -85,10 +87,16 @@ class RegionMasks:
 
 
 def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_size: int = 96, seed: int = 1234,
-                   fv_start: int = 0, regional_dcn: bool = False, rg: int = 0, metric_fn=None) -> Dict[str, object]:
+                   fv_start: int = 0, regional_dcn: bool = False, rg: int = 0, metric_fn=None, score_maps: bool = False,
+                   baseline: Optional[torch.Tensor] = None) -> Dict[str, object]:
     """Stream `lr [N,3,h,w]` / `gt [N,3,8h,8w]` (device tensors, range [0,1]) through `model` (MRCF_simple_v18 interface:
     ``model(lrs=, fvs=, mks=, fgs=)`` one frame per call, ``clear_states()``) along a gaussian gaze trajectory and collect
-    the rig's region metrics.  Returns per-region mean PSNR / SSIM, the trajectory and the outputs' checksum."""
+    the rig's region metrics.  Returns per-region mean PSNR / SSIM, the trajectory and the outputs' checksum.
+    score_maps: also score every frame's output per 10 x 10 window at stride 5 (utils.foveated_metric, eval mode: nothing is
+    drawn) -> "psnr_score" / "ssim_score" [N,Hr,Wr] on the device; with `baseline` [N,3,H,W] (the rig's bicubic frames) those
+    too ("psnr_score_baseline" / "ssim_score_baseline") and "score_extrema" = the rig's running (psnr_min, psnr_max, ssim_min,
+    ssim_max) from the baseline's calls, started at (1000, 0, 1000, 0) as the rig starts them (from the output's calls when
+    there is no baseline).  All of it stays on the device: no host synchronisation is added to the loop."""
     regions_fn = None
     if metric_fn is None:
         from . import utils as U
@@ -100,6 +108,11 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
     acc = {r: [] for r in regions}
     traj = []
     ones = torch.ones((1, 1, H, W), device=gt.device, dtype=torch.bool)
+    maps = {k: [] for k in ("psnr_score", "ssim_score", "psnr_score_baseline", "ssim_score_baseline")}
+    extrema = None
+    if score_maps:
+        from . import utils as U
+        extrema = torch.tensor([1000.0, 0.0, 1000.0, 0.0], device=gt.device)   # psnr_min, psnr_max, ssim_min, ssim_max
     model.clear_states()
     with torch.no_grad():
         for n in range(N):
@@ -119,7 +132,20 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
                 for r, mask in todo:
                     p, s = metric_fn(sr, g, mask)
                     acc[r].append((float(p), float(s)))
+            if score_maps:
+                hw, fv2 = (H, W), (fv_size, fv_size)
+                ps, ss, pe, se = U.foveated_metric(None, sr[0], g[0], (cur_y, cur_x), hw, fv2, 10, 5, eval_mode=True)
+                maps["psnr_score"].append(ps); maps["ssim_score"].append(ss)
+                if baseline is not None:
+                    ps, ss, pe, se = U.foveated_metric(None, baseline[n], g[0], (cur_y, cur_x), hw, fv2, 10, 5, eval_mode=True)
+                    maps["psnr_score_baseline"].append(ps); maps["ssim_score_baseline"].append(ss)
+                lo, hi = torch.stack([pe[0], se[0]]), torch.stack([pe[1], se[1]])
+                extrema[0::2] = torch.minimum(extrema[0::2], lo)
+                extrema[1::2] = torch.maximum(extrema[1::2], hi)
     out: Dict[str, object] = {"trajectory": traj, "frames": N}
+    if score_maps:
+        out.update({k: torch.stack(v) for k, v in maps.items() if v})
+        out["score_extrema"] = extrema
     for r in regions:
         if acc[r]:
             out[f"psnr_{r}"] = float(np.mean([v[0] for v in acc[r]]))
@@ -148,6 +174,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--model-code", type=int, default=18, choices=(13, 15, 18),
                     help="the streaming model test_video.py builds for this code: 13 MRCF_simple_v13, 15 MRCF_simple_v15, 18 MRCF_simple_v18")
+    ap.add_argument("--score-maps", action="store_true",
+                    help="also time the stream with the per-window score maps of the output and of the bilinear x8 baseline")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     if a.model_code == 18:
@@ -181,9 +209,20 @@ def main(argv=None):
     torch.cuda.synchronize()
     dt_model = time.perf_counter() - t0
     res.pop("per_frame"); res.pop("trajectory")
+    extra = {}
+    if a.score_maps:   # the same stream once more with both score maps per frame; the baseline is the bilinear x8 frame, unclamped
+        base = F.interpolate(lr, scale_factor=8, mode="bilinear", align_corners=False)
+        run_gaze_video(m, lr[:3], gt[:3], a.sigma, a.fv_size, a.seed, score_maps=True, baseline=base[:3])   # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sm = run_gaze_video(m, lr, gt, a.sigma, a.fv_size, a.seed, regional_dcn=a.regional_dcn > 0, rg=a.regional_dcn,
+                            score_maps=True, baseline=base)
+        torch.cuda.synchronize()
+        extra["frames_per_sec_with_score_maps"] = a.frames / (time.perf_counter() - t0)
+        extra["score_extrema"] = [float(v) for v in sm["score_extrema"].cpu()]
     model = "" if a.model_code == 18 else f", {type(m).__name__}"
     print(json.dumps({"workload": f"BASELINE config 3 shape: {a.frames} streamed frames {a.lr_h}x{a.lr_w} -> x8, sigma_T={a.sigma}, fp32, synthetic{model}",
-                      "frames_per_sec_with_region_metrics": a.frames / dt, "frames_per_sec_model_only": a.frames / dt_model, **res}))
+                      "frames_per_sec_with_region_metrics": a.frames / dt, "frames_per_sec_model_only": a.frames / dt_model, **extra, **res}))
 
 
 if __name__ == "__main__":

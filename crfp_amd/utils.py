@@ -1,6 +1,7 @@
 """Host-side mirror of the metric functions of the reference's ``utils`` module that sit on the eval path
 (utils.py:166-185 psnr_cuda, :187-240 ssim, :242-254 calc_psnr_and_ssim_cuda, :328-330 bgr2ycbcr(y_only)),
-computed by libcrfp_hip.so (crfp_psnr_ssim_partial_f32: one pass over the image pair gives both figures).
+computed by libcrfp_hip.so (crfp_psnr_ssim_partial_f32: one pass over the image pair gives both figures), and of the video rig's
+foveated_metric (test_video.py:23-98; crfp_window_scores_f32: both score maps from one fused kernel, no unfold).
 Same names, argument meaning and quirks; CUDA/HIP tensors only (no CPU path in the product)."""
 from __future__ import annotations
 
@@ -84,6 +85,48 @@ def calc_psnr_and_ssim_regions(sr, hr, masks):
     for se, ss, ms in sums.tolist():
         out.append((torch.tensor(_psnr_from(se, ms, tuple(sr.shape))), torch.tensor(ss / (ms * sr.shape[1]))))
     return out
+
+
+def window_scores(sr, hr, kernel_size=10, stride=5):
+    """Raw per-window (psnr [dB], ssim) maps, [Hr,Wr] for [C,H,W] input and [n,Hr,Wr] for [n,C,H,W], of every kernel_size x
+    kernel_size window at `stride`, each window scored as an image of its own (zero padding at the window's border).  The range
+    conversion is picked on the device from sr's span over the covered pixels, per image; the call does not synchronise."""
+    sr, hr = _dev(sr, "sr"), _dev(hr, "hr")
+    if sr.dim() not in (3, 4) or sr.shape != hr.shape:
+        raise ValueError(f"sr / hr must be [C,H,W] or [n,C,H,W] of one shape, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    n, (c, h, w) = (1 if sr.dim() == 3 else sr.shape[0]), sr.shape[-3:]
+    k, s = int(kernel_size), int(stride)
+    if k < 1 or s < 1 or k > h or k > w:
+        raise ValueError(f"window {k} at stride {s} does not fit a {h} x {w} image")
+    hr_, wr_ = (h - k) // s + 1, (w - k) // s + 1
+    psnr = torch.empty((n, hr_, wr_), dtype=torch.float32, device=sr.device)
+    ssim = torch.empty_like(psnr)
+    L = _lib.lib()
+    ws_bytes = L.crfp_window_scores_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=sr.device)
+    with torch.cuda.device(sr.device):
+        _lib.check(L.crfp_window_scores_f32(hr.data_ptr(), sr.data_ptr(), psnr.data_ptr(), ssim.data_ptr(), n, c, h, w, k, s,
+                                            ws.data_ptr(), ws_bytes, _stream()), "crfp_window_scores_f32")
+    return (psnr[0], ssim[0]) if sr.dim() == 3 else (psnr, ssim)
+
+
+def foveated_metric(LR, LR_fv, HR, mn, hw, crop, kernel_size, stride_size, eval_mode=False):
+    """test_video.foveated_metric: (psnr/100, (ssim.clip(0,1) - 0.7)/0.3, (psnr.min, psnr.max), (ssim.min, ssim.max)) of the per-window
+    maps of LR_fv (the model output) against HR, both [3,H,W]; unless eval_mode, the crop rectangle at mn is then drawn into HR and
+    LR_fv in place with the colour [0, 0, 255], as the reference does.  LR is unused there too.  Everything stays on the device."""
+    if LR_fv.dim() != 3 or LR_fv.shape[0] != 3:
+        raise ValueError(f"foveated_metric needs [3,H,W] images (the reference's .view(.., 3, k, k)), got {tuple(LR_fv.shape)}")
+    psnr_score, ssim_score = window_scores(LR_fv, HR, kernel_size, stride_size)
+    if not eval_mode:
+        (m, n), (crop_h, crop_w) = mn, crop
+        colour = torch.tensor([0., 0., 255.], device=HR.device).unsqueeze(1)
+        for img in (HR, LR_fv):
+            img[:, m:m + crop_h, n] = colour
+            img[:, m:m + crop_h, n + crop_w - 1] = colour
+            img[:, m, n:n + crop_w] = colour
+            img[:, m + crop_h - 1, n:n + crop_w] = colour
+    extrema = (psnr_score.min(), psnr_score.max()), (ssim_score.min(), ssim_score.max())
+    return (psnr_score / 100, (ssim_score.clip(0, 1) - 0.7) / 0.3) + extrema
 
 
 def bgr2ycbcr(img, y_only=False):

@@ -33,6 +33,7 @@
  *   crfp_simple_* / crfp_dense_*  model/CRFP.py:816-1099 CRFP_simple / :1101-1385 CRFP (clip forward) and their
  *                             one-frame-per-call variants model/CRFP_test.py:1184-1486 MRCF_simple_v13 / :1805-2113 v15
  *   crfp_psnr_partial_f32     utils.py:166-185,242-254,328-330 (psnr_cuda / bgr2ycbcr(y_only))
+ *   crfp_window_scores_f32    test_video.py:23-63 foveated_metric (per-window PSNR / SSIM maps)
  *   crfp_spynet_forward       model/CRFP.py:554-741 SPyNet.forward (+ SPyNetBasicModule, `conv` :145-152)
  *   crfp_convkxk_f32          model/CRFP.py:145-152 `conv`: ReLU -> nn.Conv2d(k, stride 1, pad k/2)
  *   crfp_upsample_bilinear_ac_f32  F.interpolate(..., bilinear, align_corners=True) (model/CRFP.py:647-651)
@@ -167,6 +168,18 @@ int crfp_fovea_head_f32(const float* state, const float* x_hr, const unsigned ch
  * acc[0] += sum m (a'-b')^2 (all channels), acc[1] += sum m SSIM_map (all channels), acc[2] += sum m (per pixel). */
 int crfp_psnr_ssim_partial_f32(const float* a, const float* b, const unsigned char* mask, double* acc, int n, int c, int h, int w,
                                float mul, float add, void* stream);
+
+/* Foveated score maps: PSNR and mean SSIM of every k x k window at stride `stride`, each window scored as an image of its own
+ * (reference test_video.py:23-63 foveated_metric -> the batch_avg=True branches of utils.py:166-172,197-221,242-254; callers
+ * test_video.py:381-384, trainer.py:456,628), fused: no unfold, nothing per window in memory.  hr, sr: [n,c,h,w] fp32; psnr, ssim:
+ * [n,Hr,Wr] with Hr = (h-k)/stride + 1, Wr = (w-k)/stride + 1, raw values (dB; the unclipped mean of the SSIM map).  The range
+ * conversion of utils.py:244-250 is decided on the device, per image, from the span of `sr` over the pixels some window covers
+ * (> 2: x/255; > 1: (x+1)/2), so a batch equals n calls bit for bit and the call never synchronises.  A window with mse == 0 gets
+ * -20 log10(sqrt((1/255)^2 / (c k k))) and SSIM 1.  1 <= k <= 16 (CRFP_E_UNSUPPORTED above), k <= h, k <= w, stride >= 1;
+ * a null pointer, a bad size or a short workspace is CRFP_E_BADARG.  Each output element is written once (no atomics). */
+size_t crfp_window_scores_workspace_bytes(int n);
+int crfp_window_scores_f32(const float* hr, const float* sr, float* psnr, float* ssim, int n, int c, int h, int w, int k, int stride,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- CRFP_DSV engine (mid_channels=32, hr_dcn=True, offset_prop=True; y_only selectable).
  * Parameters arrive as CRFP_DSV_NUM_PARAMS device pointers in the order of the reference's

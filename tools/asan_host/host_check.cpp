@@ -93,6 +93,37 @@ int main() {
     EXPECT(crfp_dense_forward_batch_bf16(p16, 0, p16, nullptr, m16, p16, 1, 7, 180, 320, p16, (size_t)1 << 40, nullptr) != 0);
     EXPECT(crfp_dsv_forward_clip_bf16(p16, CRFP_DSV_STRICT_F32, p16, p16, m16, p16, 7, 180, 320, p16, (size_t)1 << 40, nullptr) != 0);
     EXPECT(std::strlen(crfp_last_error_string()) > 0);
+    // the window score maps: every refusal comes before the first launch
+    {
+        const size_t wsb = crfp_window_scores_workspace_bytes(2);
+        const long l0 = crfp_stub_launches();
+        EXPECT(wsb > 0 && crfp_window_scores_workspace_bytes(0) == 0 && crfp_window_scores_workspace_bytes(3) > wsb);
+        EXPECT(crfp_window_scores_f32(nullptr, p16, p16, p16, 2, 3, 24, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(crfp_window_scores_f32(p16, nullptr, p16, p16, 2, 3, 24, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, nullptr, p16, 2, 3, 24, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, nullptr, 2, 3, 24, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 24, 31, 10, 5, nullptr, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 24, 31, 10, 5, p16, wsb - 1, nullptr) == CRFP_E_BADARG);   // one byte short
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 0, 3, 24, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 0, 24, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 24, 31, 0, 5, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 24, 31, 10, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 9, 31, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);        // k > h
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 24, 9, 10, 5, p16, wsb, nullptr) == CRFP_E_BADARG);        // k > w
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 24, 31, 17, 5, p16, wsb, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, 3, 8, 31, 17, 5, p16, wsb, nullptr) == CRFP_E_BADARG);        // k > h comes first
+        EXPECT(crfp_stub_launches() == l0);
+        // and accepted calls over the tile chooser's corners (stub runtime: nothing runs)
+        for (int k : {1, 7, 10, 16})
+            for (int st : {1, 5, 12, 1000})
+                for (int c : {1, 3}) {
+                    EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 2, c, 75, 130, k, st, p16, wsb, nullptr) == 0);
+                    EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 1, c, 1072, 1920, k, st, p16, wsb, nullptr) == 0);
+                    EXPECT(crfp_window_scores_f32(p16, p16, p16, p16, 1, c, k, k, k, st, p16, wsb, nullptr) == 0);
+                }
+        EXPECT(crfp_stub_launches() == l0 + 2 * 3 * 4 * 4 * 2);
+    }
     // ---- whole engine calls on the stub runtime (tools/asan_host/hip_stub.cpp: every HIP call succeeds, no kernel runs): the host side of a
     // call -- argument checks, Layout arenas, the launch-argument tables of ~50 launches per frame, the fork / join of the side stream, the
     // per-thread stream table and crfp_shutdown() -- under the sanitizers.  Device pointers are fabricated and never dereferenced on the host.
