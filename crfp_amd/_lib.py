@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -73,10 +74,6 @@ SIGNATURES = {
     "crfp_dsv_stream_batch": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 4 +
                               [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_fnet_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
-    "crfp_rt_param_name": (C.c_char_p, [C.c_int]),
-    "crfp_rt_param_numel": (C.c_int, [C.c_int, C.c_int]),
-    "crfp_rt_packed_weight_bytes": (C.c_size_t, [C.c_int]),
-    "crfp_rt_pack_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_rt_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
     "crfp_rt_forward_clip": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_prof_enable": (C.c_int, [C.c_int]),
@@ -86,23 +83,56 @@ SIGNATURES = {
     "crfp_dsv_debug_fetch": (C.c_int, [C.c_char_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p] +
                              [C.POINTER(C.c_int)] * 3 + [C.c_void_p]),
 }
-# the CRFP_DSV_CRA wiring: its own parameter table / packed weights / workspace, the forward call of crfp_dsv_forward_batch
 CRA_NUM_PARAMS = 144
-for _n in ("param_name", "param_numel", "packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batch_status_offset", "forward_batch"):
-    SIGNATURES["crfp_cra_" + _n] = SIGNATURES["crfp_dsv_" + _n]
-for _n in ("packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batch_status_offset", "forward_batch"):
-    SIGNATURES["crfp_cra_" + _n + "_bf16"] = SIGNATURES["crfp_dsv_" + _n]
-# the CRFP_simple / CRFP wirings (round 6): CRFP_DSV's parameter names, their own shapes / packed weights / workspace, the same forward call
-for _w in ("simple", "dense"):
-    for _n in ("param_numel", "packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batch_status_offset", "forward_batch", "stream_batch"):
-        SIGNATURES[f"crfp_{_w}_{_n}"] = SIGNATURES["crfp_dsv_" + _n]
-        if _n != "param_numel":
-            SIGNATURES[f"crfp_{_w}_{_n}_bf16"] = SIGNATURES["crfp_dsv_" + _n]
-# bf16-storage twins of the engine entry points (same argument lists)
-for _n in ("crfp_dsv_packed_weight_bytes", "crfp_dsv_pack_weights", "crfp_dsv_workspace_bytes", "crfp_dsv_status_offset",
-           "crfp_dsv_forward_clip", "crfp_dsv_stream_frame", "crfp_fnet_forward", "crfp_dsv_debug_fetch",
-           "crfp_dsv_batch_workspace_bytes", "crfp_dsv_batch_status_offset", "crfp_dsv_forward_batch", "crfp_dsv_stream_batch"):
-    SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
+
+
+@dataclasses.dataclass(frozen=True)
+class Family:
+    """One engine family of the C-ABI: what crfp_amd.engine's handles and the bindings below know about a wiring."""
+    prefix: str          # C-ABI prefix of its entry points
+    names: str           # the family whose param_name table (and parameter count) names its parameters
+    num_params: int
+    model: str           # the model class, for error messages
+    ops: frozenset       # the operations it exports, as `prefix + op`
+    bf16: frozenset      # those with a bf16-storage twin `prefix + op + "_bf16"` (same argument list)
+
+
+_PACK = frozenset(("param_numel", "packed_weight_bytes", "pack_weights"))
+_CLIP = _PACK | {"batch_workspace_bytes", "batch_status_offset", "forward_batch"}   # clip / lock-step batch forward
+_STREAM = _CLIP | {"stream_batch"}                                                  # + one frame per call
+_DSV = _STREAM | {"fnet_forward", "debug_fetch"}
+_NUMEL = frozenset(("param_numel",))   # shapes do not depend on the storage type
+# dsv: CRFP_DSV.  cra: CRFP_DSV_CRA, its own parameter table, clip forward only.  simple / dense: the CRFP_simple / CRFP wirings -- CRFP_DSV's
+# parameter names with their own shapes -- clip forward and the one-frame-per-call form (MRCF_simple_v13 / v15).  rt: the regional benchmark
+# wiring, fp32 storage only, with a forward call and a workspace query of its own.
+FAMILIES = {
+    "dsv": Family("crfp_dsv_", "dsv", NUM_PARAMS, "CRFP_DSV", _DSV, _DSV - _NUMEL),
+    "cra": Family("crfp_cra_", "cra", CRA_NUM_PARAMS, "CRFP_DSV_CRA", _CLIP, _CLIP - _NUMEL),
+    "simple": Family("crfp_simple_", "dsv", NUM_PARAMS, "CRFP_simple", _STREAM, _STREAM - _NUMEL),
+    "dense": Family("crfp_dense_", "dsv", NUM_PARAMS, "CRFP", _STREAM, _STREAM - _NUMEL),
+    "rt": Family("crfp_rt_", "rt", RT_NUM_PARAMS, "MRCF_simple_v18", _PACK | {"workspace_bytes", "forward_clip"}, frozenset()),
+}
+
+
+def symbol(family: str, op: str, storage: str = "f32") -> str:
+    """The C name of operation `op` for a family and a storage type.  NotImplementedError when the family does not export it."""
+    row = FAMILIES[family]
+    if op not in row.ops:
+        raise NotImplementedError(f"crfp_amd: {row.model} has no {op} entry point")
+    base = "crfp_fnet_forward" if op == "fnet_forward" else row.prefix + op   # the flow network alone carries no family prefix
+    return base + ("_bf16" if storage == "bf16" and op in row.bf16 else "")
+
+
+# per-family entries: a name that is not spelled out above has the argument list of CRFP_DSV's entry point for the same operation
+for _k, _row in FAMILIES.items():
+    SIGNATURES.setdefault(FAMILIES[_row.names].prefix + "param_name", SIGNATURES["crfp_dsv_param_name"])
+    for _op in _row.ops:
+        for _st in ("f32", "bf16"):
+            if symbol(_k, _op, _st) not in SIGNATURES:
+                SIGNATURES[symbol(_k, _op, _st)] = SIGNATURES[symbol("dsv", _op)]
+# bf16-storage twins of the C-ABI's n = 1 conveniences (crfp_dsv_forward_clip = crfp_dsv_forward_batch with n = 1, and so on)
+for _n in ("workspace_bytes", "status_offset", "forward_clip", "stream_frame"):
+    SIGNATURES[f"crfp_dsv_{_n}_bf16"] = SIGNATURES[f"crfp_dsv_{_n}"]
 
 _lib = None
 

@@ -8,14 +8,12 @@ The modules only *hold parameters*; all arithmetic runs in the HIP library: ``CR
 one C-ABI call per clip (crfp_amd.engine.DSVEngine), the smaller modules call per-operator entry
 points.  Inference only (no autograd), CUDA/HIP tensors only.
 """
-import os
-
 import torch
 import torch.nn as nn
 
 from crfp_amd import ops
 from crfp_amd.dcn_v2 import DCNv2
-from crfp_amd.engine import CRAEngine, DenseEngine, DenseStreamEngine, DSVEngine, SimpleEngine, SimpleStreamEngine
+from crfp_amd.engine import CRAEngine, DenseEngine, DenseStreamEngine, DSVEngine, PackedModel, SimpleEngine, SimpleStreamEngine
 from . import LTE
 
 
@@ -270,7 +268,37 @@ class SPyNet(nn.Module):
         return flow
 
 
-class CRFP_DSV(nn.Module):
+class _ClipEngine(PackedModel):
+    """Engine management of the clip models: which handle class drives the wiring, for which constructor arguments it exists, and the
+    numerics policy (``precision``, ``on_overflow``, ``storage``, ``inputs_resident``: not part of the reference's interface) it is given."""
+
+    _engine_class = DSVEngine
+    _engine_mids = (16, 32)   # mid_channels = 16 runs embedded in the 32-channel schedule (crfp_amd.engine.embed_mid32)
+
+    def has_engine(self) -> bool:
+        """The one-call C++ schedule (csrc/engine.hip) exists for the configuration the reference ships and evaluates (main.py:34 with
+        eval.sh's flags: mid_channels=32, hr_dcn, offset_prop) and -- round 6 -- for mid_channels = 16 (the constructor default,
+        model/CRFP.py:1388), which runs as the same function embedded in the 32-channel schedule; every other flag combination
+        (hr_dcn / offset_prop off, mid_channels > 32) runs ``forward_composed``."""
+        return self.mid_channels in self._engine_mids and bool(self.hr_dcn) and bool(self.offset_prop)
+
+    def _new_engine(self, dev):
+        return self._engine_class(self.state_dict(), dev, self.y_only, storage=self.storage, mid_channels=self.mid_channels)
+
+    def _engine_stale(self) -> bool:
+        return self._engine.storage != self.storage
+
+    def engine(self) -> DSVEngine:
+        if not self.has_engine():
+            raise RuntimeError(f"crfp_amd: no one-call engine for mid_channels={self.mid_channels}, hr_dcn={self.hr_dcn}, "
+                               f"offset_prop={self.offset_prop}: this model runs through forward_composed (per-operator HIP calls)")
+        eng = super().engine()
+        eng.precision, eng.on_overflow = self.precision, self.on_overflow
+        eng.inputs_resident = bool(self.inputs_resident)
+        return eng
+
+
+class CRFP_DSV(nn.Module, _ClipEngine):
     """Drop-in for the reference's CRFP_DSV (model/CRFP.py:1387-1706).  ``spynet_pretrained`` may be
     None (the reference would crash: it torch.load()s it unconditionally, :1407) -- weights then come
     from ``load_state_dict`` / ``init_weights``."""
@@ -311,62 +339,11 @@ class CRFP_DSV(nn.Module):
         self.upsample_post = PixelShufflePack((m * self.split_ratio) // 4, l, 4, upsample_kernel=3)
         self.conv_last = nn.Conv2d(l, 1 if y_only else 3, 3, 1, 1)
         self.lrelu = nn.LeakyReLU(negative_slope=0.1, inplace=True)
-        self._engine = None
-        self._engine_sig = None
-        self._engine_sum = None
         # numerics policy of the HIP engine (crfp_amd.engine.DSVEngine): not part of the reference's interface
         self.precision = "split"      # "split": split-fp16 MFMA scheme (fp32-grade) | "f32": strict fp32 MFMA
         self.on_overflow = "poison"   # "poison" | "fallback" | "raise" when an activation leaves the fp16 operand range
         self.storage = "f32"          # "f32" | "bf16": activation / state storage in HBM (BASELINE configs 3-5 are bf16)
         self.inputs_resident = False  # streaming only: the frame tensors are complete before each call (CRFP_DSV_INPUTS_RESIDENT, engine.py)
-
-    # ---- engine management: repack whenever a parameter was modified or moved
-    def _signature(self):
-        """(address, in-place version) of every parameter: changes under load_state_dict, optimizer steps, ``.to()`` and any
-        in-place op on the parameter itself.  It does NOT see writes through ``param.data`` (a ``.data`` alias has its own
-        version counter) -- after such writes call ``invalidate_packed()``.  ``CRFP_CHECK_PACKED=1`` in the environment makes
-        every ``engine()`` call verify an on-device checksum of the parameters against the one taken at pack time (one host
-        sync per call: a debugging aid) and raise if they differ."""
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def _checksum(self):
-        ps = [p.detach().reshape(-1) for p in self.parameters()]
-        flat = torch.cat(ps).double()
-        return torch.stack([flat.sum(), flat.abs().sum(), (flat * torch.arange(1, flat.numel() + 1, device=flat.device, dtype=torch.float64)).sum()])
-
-    def invalidate_packed(self):
-        """Drop the packed-weight image: the next forward repacks from the current parameter values.  Needed only after
-        writing parameters through ``.data`` (see ``_signature``)."""
-        self._engine_sig = None
-
-    _engine_class = DSVEngine
-    _engine_mids = (16, 32)   # mid_channels = 16 runs embedded in the 32-channel schedule (crfp_amd.engine.embed_mid32)
-
-    def has_engine(self) -> bool:
-        """The one-call C++ schedule (csrc/engine.hip) exists for the configuration the reference ships and evaluates (main.py:34 with
-        eval.sh's flags: mid_channels=32, hr_dcn, offset_prop) and -- round 6 -- for mid_channels = 16 (the constructor default,
-        model/CRFP.py:1388), which runs as the same function embedded in the 32-channel schedule; every other flag combination
-        (hr_dcn / offset_prop off, mid_channels > 32) runs ``forward_composed``."""
-        return self.mid_channels in self._engine_mids and bool(self.hr_dcn) and bool(self.offset_prop)
-
-    def engine(self) -> DSVEngine:
-        if not self.has_engine():
-            raise RuntimeError(f"crfp_amd: no one-call engine for mid_channels={self.mid_channels}, hr_dcn={self.hr_dcn}, "
-                               f"offset_prop={self.offset_prop}: this model runs through forward_composed (per-operator HIP calls)")
-        dev = next(self.parameters()).device
-        sig = self._signature()
-        check = os.environ.get("CRFP_CHECK_PACKED") == "1"
-        if (self._engine is None or self._engine_sig != sig or self._engine.device != dev
-                or self._engine.storage != self.storage):
-            self._engine = self._engine_class(self.state_dict(), dev, self.y_only, storage=self.storage, mid_channels=self.mid_channels)
-            self._engine_sig = sig
-            self._engine_sum = self._checksum() if check else None
-        elif check and self._engine_sum is not None and not torch.equal(self._engine_sum, self._checksum()):
-            raise RuntimeError("crfp_amd: parameters changed without their version counters moving (a write through `.data`?): "
-                               "the packed weights are stale -- call model.invalidate_packed() after such writes")
-        self._engine.precision, self._engine.on_overflow = self.precision, self.on_overflow
-        self._engine.inputs_resident = bool(self.inputs_resident)
-        return self._engine
 
     def compute_flow(self, lrs):
         n, t, c, h, w = lrs.shape
@@ -533,7 +510,7 @@ class CRFP_DSV_CRA(CRFP_DSV):
         return mk2 * fused + (1.0 - mk2) * y
 
 
-class CRFP_simple(nn.Module):
+class CRFP_simple(nn.Module, _ClipEngine):
     """The reference's CRFP_simple ("v13", model/CRFP.py:816-1099) and, with ``dense = True``, its sibling CRFP ("v15", :1101-1385): the
     ablation wirings in front of CRFP_DSV -- no carried features (every level passes all mid_channels on), ``upsample`` keeps
     mid_channels, the previous state is warped at 8x FIRST and then brought to 2x (:1023-1026), and both constructor flags are live:
@@ -576,7 +553,6 @@ class CRFP_simple(nn.Module):
         self.upsample_post = PixelShufflePack(m, l, 4, upsample_kernel=3)
         self.conv_last = nn.Conv2d(l, 1 if y_only else 3, 3, 1, 1)
         self.lrelu = nn.LeakyReLU(negative_slope=0.1, inplace=True)
-        self._engine = self._engine_sig = self._engine_sum = None
         # numerics policy of the HIP engine, as on CRFP_DSV (not part of the reference's interface)
         self.precision, self.on_overflow, self.storage, self.inputs_resident = "split", "poison", "f32", False
 
@@ -586,9 +562,6 @@ class CRFP_simple(nn.Module):
         return self.spynet(cur.contiguous(), prev.contiguous()).view(n, t - 1, 2, h, w), None
 
     init_weights = CRFP_DSV.init_weights
-    # engine management: CRFP_DSV's (repack whenever a parameter was modified or moved)
-    _signature, _checksum, invalidate_packed = CRFP_DSV._signature, CRFP_DSV._checksum, CRFP_DSV.invalidate_packed
-    has_engine, engine, _engine_mids = CRFP_DSV.has_engine, CRFP_DSV.engine, CRFP_DSV._engine_mids
 
     @torch.no_grad()
     def forward(self, lrs, fvs, mks):

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from crfp_amd import ops
+from crfp_amd.engine import PackedModel, RuntimeEngine
 from . import LTE
 from .CRFP import DCN_module, FNet, PixelShufflePack, PixelUnShufflePack_v2, _run, conv3x3, flow_warp
 
@@ -73,7 +74,7 @@ class ResidualBlocksWithInputConv(ResidualBlocksWithInputConv_v2):
     _DIV = 3
 
 
-class MRCF_simple_v18(nn.Module):
+class MRCF_simple_v18(nn.Module, PackedModel):
     def __init__(self, device, mid_channels=16, y_only=False, hr_dcn=True, offset_prop=True, split_ratio=3,
                  spynet_pretrained=None):
         super().__init__()
@@ -108,36 +109,9 @@ class MRCF_simple_v18(nn.Module):
         self.lrelu = nn.LeakyReLU(negative_slope=0.1, inplace=True)
         self.print_timings = False       # True: per-operator composition + the reference's six per-stage lines on every call (:8654-8662)
         self.last_timings = {}
-        self._engine = None
-        self._engine_sig = None
-        self._engine_sum = None
 
-    # ---- packed-weight management: same contract as CRFP_DSV's (model/CRFP.py of this package)
-    def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def _checksum(self):
-        flat = torch.cat([p.detach().reshape(-1) for p in self.parameters()]).double()
-        return torch.stack([flat.sum(), flat.abs().sum(), (flat * torch.arange(1, flat.numel() + 1, device=flat.device, dtype=torch.float64)).sum()])
-
-    def invalidate_packed(self):
-        """drop the packed weights; needed only after writes through ``.data`` (CRFP_CHECK_PACKED=1 detects a missed one)"""
-        self._engine_sig = None
-
-    def engine(self):
-        import os
-        from crfp_amd.engine import RuntimeEngine
-        dev = next(self.parameters()).device
-        sig = self._signature()
-        check = os.environ.get("CRFP_CHECK_PACKED") == "1"
-        if self._engine is None or self._engine_sig != sig or self._engine.device != dev:
-            self._engine = RuntimeEngine(self.state_dict(), dev, y_only=self.y_only)
-            self._engine_sig = sig
-            self._engine_sum = self._checksum() if check else None
-        elif check and self._engine_sum is not None and not torch.equal(self._engine_sum, self._checksum()):
-            raise RuntimeError("crfp_amd: parameters changed without their version counters moving (a write through `.data`?): "
-                               "the packed weights are stale -- call model.invalidate_packed() after such writes")
-        return self._engine
+    def _new_engine(self, dev):   # packed-weight management: crfp_amd.engine.PackedModel
+        return RuntimeEngine(self.state_dict(), dev, y_only=self.y_only)
 
     def _upsample_post_lrelu(self, x):
         """lrelu(pixel_shuffle(conv(x), 4)) (:8602, :8636): the activation is elementwise, so it and the shuffle ride in the conv's store"""

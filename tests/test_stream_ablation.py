@@ -83,7 +83,7 @@ def test_stream_engines_keep_the_clip_engines_refusals():
     assert engine.SimpleEngine.stream_frame is engine.CRAEngine.stream_frame is engine.DenseEngine.stream_frame
     assert issubclass(engine.SimpleStreamEngine, engine.SimpleEngine) and issubclass(engine.DenseStreamEngine, engine.DenseEngine)
     e = object.__new__(engine.DenseStreamEngine)
-    e._sfx = "_bf16"
+    e.storage = "bf16"
     with pytest.raises(NotImplementedError):
-        e._fn("crfp_dsv_debug_fetch")
+        e._call("debug_fetch")
 
