@@ -405,6 +405,24 @@ int crfp_window_scores_f32(const float* hr, const float* sr, float* psnr, float*
     return launch_window_scores(hr, sr, psnr, ssim, n, c, h, w, k, stride, (float*)workspace, (hipStream_t)stream);
 }
 
+size_t crfp_frame_metrics_workspace_bytes(int n, int m, int h, int w) { return frame_metrics_workspace_bytes(n, m, h, w); }
+
+int crfp_frame_metrics_f32(const float* sr, const float* hr, const uint8_t* masks, double* out, int n, int c, int m, int h, int w, int flags,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (!sr || !hr || !out) { set_error("frame_metrics: null pointer"); return CRFP_E_BADARG; }
+    if (n < 1 || h < 1 || w < 1) { set_error("frame_metrics: bad argument (need n, h, w >= 1)"); return CRFP_E_BADARG; }
+    if (c < 1 || c > 4) { set_error("frame_metrics: c must be 1..4, got %d", c); return CRFP_E_BADARG; }
+    if (m < 0 || m > 7) { set_error("frame_metrics: m must be 0..7 masks, got %d", m); return CRFP_E_BADARG; }
+    if (m > 0 && !masks) { set_error("frame_metrics: null masks with m = %d", m); return CRFP_E_BADARG; }
+    if (flags & ~CRFP_METRICS_LUMA) { set_error("frame_metrics: unknown flags 0x%x", flags); return CRFP_E_BADARG; }
+    if ((flags & CRFP_METRICS_LUMA) && c != 3) { set_error("frame_metrics: the LUMA flag needs c = 3, got %d", c); return CRFP_E_BADARG; }
+    if (n > 65535 || h > 16 * 65535 || frame_metrics_tiles(h, w) > 0x7fffffffLL) {
+        set_error("frame_metrics: more than 65535 frames per call or a frame beyond the launch grid"); return CRFP_E_UNSUPPORTED;
+    }
+    if (!workspace || workspace_bytes < crfp_frame_metrics_workspace_bytes(n, m, h, w)) { set_error("frame_metrics: workspace too small"); return CRFP_E_WORKSPACE; }
+    return launch_frame_metrics(sr, hr, masks, out, n, c, m, h, w, flags & CRFP_METRICS_LUMA, workspace, (hipStream_t)stream);
+}
+
 int crfp_psnr_partial_f32(const float* a, const float* b, double* acc, int n, int c, int h, int w, void* stream) {
     if (!a || !b || !acc || n < 1 || c < 1 || h < 1 || w < 1) { set_error("psnr_partial: bad argument"); return CRFP_E_BADARG; }
     return launch_psnr_partial(a, b, acc, n, c, h, w, (hipStream_t)stream);

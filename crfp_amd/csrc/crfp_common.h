@@ -470,5 +470,9 @@ int launch_psnr_partial(const float* a, const float* b, double* acc, int N, int 
 size_t window_scores_workspace_bytes(int N);
 int launch_window_scores(const float* hr, const float* sr, float* psnr, float* ssim, int N, int C, int H, int W, int k, int stride,
                          float* part, hipStream_t s);
+long long frame_metrics_tiles(int H, int W);
+size_t frame_metrics_workspace_bytes(int N, int M, int H, int W);
+int launch_frame_metrics(const float* sr, const float* hr, const uint8_t* masks, double* out, int N, int C, int M, int H, int W, int luma,
+                         void* workspace, hipStream_t s);
 
 }  // namespace CRFP_NS

@@ -112,9 +112,10 @@ def counted_frames(i_batch: int, n_frames: int) -> Iterable[int]:
     return (i for i in range(n_frames) if not (i == 0 and i_batch % 50 == 0))
 
 
-def eval_clip(model, batch: dict, i_batch: int, with_ssim: bool = True, sr: Optional[torch.Tensor] = None):
+def eval_clip(model, batch: dict, i_batch: int, with_ssim: bool = True, sr: Optional[torch.Tensor] = None, fused: bool = False):
     """One eval batch through the model (trainer.py:307-369): batch has LR, HR, Ref, Ref_sp on device.  sr: the model's output for
-    this batch when the caller already ran it (eval_reds with clips_per_call > 1)."""
+    this batch when the caller already ran it (eval_reds with clips_per_call > 1).  fused: all counted frames are scored by ONE
+    utils.frame_metrics_table call (range probes on the device) and fetched with one copy, instead of four host round trips per frame."""
     if sr is None:
         with torch.no_grad():
             sr = model(lrs=batch["LR"], fvs=batch["Ref"], mks=batch["Ref_sp"])
@@ -124,6 +125,16 @@ def eval_clip(model, batch: dict, i_batch: int, with_ssim: bool = True, sr: Opti
     if C == 1:   # y_only model (trainer.py:331-335): chroma of the bicubic LR_sr under the predicted luma, back to RGB
         yuv = rgb2yuv(batch["LR_sr"].view(B * N, 3, H, W).to(sr.dtype))
         sr = yuv2rgb(torch.cat((sr[:, 0:1], yuv[:, 1:3]), dim=1)).contiguous()
+    if fused:
+        from . import utils as U
+        idx = list(counted_frames(i_batch, N))
+        if not idx:
+            return []
+        if idx != list(range(sr.shape[0])):
+            sel = torch.tensor(idx, device=sr.device)
+            sr, hr = sr.index_select(0, sel), hr.index_select(0, sel)
+        rows = U.frame_metrics_table(sr, hr, None, luma=True)[:, 0].cpu().tolist()
+        return [tuple(r) if with_ssim else (r[0], r[2]) for r in rows]
     fn = frame_metrics if with_ssim else frame_psnrs
     return [fn(sr[i:i + 1], hr[i:i + 1]) for i in counted_frames(i_batch, N)]
 
@@ -140,12 +151,13 @@ def load_checkpoint(model, model_path: str):
 
 
 def eval_reds(model, args, rank: int = 0, world: int = 1, dist=None, device=None, with_ssim: bool = True, log=None,
-              clips_per_call: int = 1):
+              clips_per_call: int = 1, fused_metrics: bool = False):
     """Trainer.eval_basicvsr over dataset.reds.EvalSet (trainer.py:295-413): batch size 1, items sharded round-robin over
     ranks (each item is an independent clip window), per-frame metrics, one final all-reduce.
     clips_per_call > 1 (not in the reference, whose eval DataLoader is batch_size=1, dataset/dataloader.py:14): that many of a rank's
     windows go through ONE model call (crfp_dsv_forward_batch: lock-step launches over the windows, per window bit-identical to its
-    own call), every window keeping its own `i_batch` for the frame-0 rule -- the same metrics, more frames per second."""
+    own call), every window keeping its own `i_batch` for the frame-0 rule -- the same metrics, more frames per second.
+    fused_metrics: eval_clip(fused=True), one metric call and one copy per clip."""
     from .dataset import reds
     ds = reds.EvalSet(args)
     dev = device if device is not None else next(model.parameters()).device
@@ -166,7 +178,7 @@ def eval_reds(model, args, rank: int = 0, world: int = 1, dist=None, device=None
                     sr_all = model(lrs=batch["LR"], fvs=batch["Ref"], mks=batch["Ref_sp"])
                 for b, i in enumerate(group):
                     one = {k: (v[b:b + 1] if torch.is_tensor(v) else v) for k, v in batch.items()}
-                    cache[i] = eval_clip(model, one, i, with_ssim, sr=sr_all[b:b + 1])
+                    cache[i] = eval_clip(model, one, i, with_ssim, sr=sr_all[b:b + 1], fused=fused_metrics)
             m = cache[i_batch]
             if log is not None:
                 log(i_batch, m)
@@ -177,7 +189,7 @@ def eval_reds(model, args, rank: int = 0, world: int = 1, dist=None, device=None
     def clip_fn(i_batch):
         item = ds[i_batch]
         batch = {k: (v.unsqueeze(0).to(dev) if torch.is_tensor(v) else v) for k, v in item.items()}   # DataLoader(batch_size=1)
-        m = eval_clip(model, batch, i_batch, with_ssim)
+        m = eval_clip(model, batch, i_batch, with_ssim, fused=fused_metrics)
         if log is not None:
             log(i_batch, m)
         return m
@@ -202,6 +214,7 @@ def main(argv=None):
     ap.add_argument("--FV_size", type=int, default=96)
     ap.add_argument("--y_only", type=int, default=0)
     ap.add_argument("--clips_per_call", type=int, default=1, help="windows per model call (lock-step batch; same metrics)")
+    ap.add_argument("--fused_metrics", action="store_true", help="score each clip's frames in one fused call (utils.frame_metrics_table)")
     a = ap.parse_args(argv)
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     dist = None
@@ -214,7 +227,7 @@ def main(argv=None):
     model = CRFP.CRFP_DSV(device=dev, mid_channels=32, y_only=bool(a.y_only), hr_dcn=True, offset_prop=True).to(dev).eval()
     if a.model_path:
         load_checkpoint(model, a.model_path)
-    res = eval_reds(model, a, rank, world, dist, dev, clips_per_call=a.clips_per_call)
+    res = eval_reds(model, a, rank, world, dist, dev, clips_per_call=a.clips_per_call, fused_metrics=a.fused_metrics)
     if rank == 0:
         print(json.dumps(res))
 

@@ -88,7 +88,7 @@ class RegionMasks:
 
 def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_size: int = 96, seed: int = 1234,
                    fv_start: int = 0, regional_dcn: bool = False, rg: int = 0, metric_fn=None, score_maps: bool = False,
-                   baseline: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                   baseline: Optional[torch.Tensor] = None, fused_metrics: bool = False) -> Dict[str, object]:
     """Stream `lr [N,3,h,w]` / `gt [N,3,8h,8w]` (device tensors, range [0,1]) through `model` (MRCF_simple_v18 interface:
     ``model(lrs=, fvs=, mks=, fgs=)`` one frame per call, ``clear_states()``) along a gaussian gaze trajectory and collect
     the rig's region metrics.  Returns per-region mean PSNR / SSIM, the trajectory and the outputs' checksum.
@@ -96,9 +96,16 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
     drawn) -> "psnr_score" / "ssim_score" [N,Hr,Wr] on the device; with `baseline` [N,3,H,W] (the rig's bicubic frames) those
     too ("psnr_score_baseline" / "ssim_score_baseline") and "score_extrema" = the rig's running (psnr_min, psnr_max, ssim_min,
     ssim_max) from the baseline's calls, started at (1000, 0, 1000, 0) as the rig starts them (from the output's calls when
-    there is no baseline).  All of it stays on the device: no host synchronisation is added to the loop."""
+    there is no baseline).  All of it stays on the device: no host synchronisation is added to the loop.
+    fused_metrics: the four regions of a frame come from ONE utils.frame_metrics_table call (masks fovea / outskirt / past; frame 0
+    passes an all-zero past whose row is dropped), the rows stay on the device and are fetched once after the loop: the loop
+    itself no longer synchronises.  Same dict."""
     regions_fn = None
-    if metric_fn is None:
+    if fused_metrics:
+        if metric_fn is not None:
+            raise ValueError("fused_metrics scores with the library's own table: it cannot be combined with metric_fn")
+        from . import utils as U
+    elif metric_fn is None:
         from . import utils as U
         metric_fn, regions_fn = U.calc_psnr_and_ssim_cuda, U.calc_psnr_and_ssim_regions
     N, _, H, W = gt.shape
@@ -110,6 +117,8 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
     ones = torch.ones((1, 1, H, W), device=gt.device, dtype=torch.bool)
     maps = {k: [] for k in ("psnr_score", "ssim_score", "psnr_score_baseline", "ssim_score_baseline")}
     extrema = None
+    rows = []          # fused_metrics: one [4, 4] device row block per frame
+    no_past = torch.zeros((1, 1, H, W), device=gt.device, dtype=torch.bool)
     if score_maps:
         from . import utils as U
         extrema = torch.tensor([1000.0, 0.0, 1000.0, 0.0], device=gt.device)   # psnr_min, psnr_max, ssim_min, ssim_max
@@ -125,7 +134,10 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
             sr = sr.reshape(1, -1, H, W)
             todo = [(r, mask) for r, mask in (("whole", ones), ("fovea", m["fovea"]), ("outskirt", m["outskirt"]),
                                               ("past", m["past"])) if mask is not None]   # frame 0 has no past ring
-            if regions_fn is not None:   # one range probe and one host sync per frame
+            if fused_metrics:   # one call for the four regions, nothing fetched inside the loop
+                past = m["past"] if m["past"] is not None else no_past
+                rows.append(U.frame_metrics_table(sr, g, torch.cat((m["fovea"], m["outskirt"], past), 1))[0])
+            elif regions_fn is not None:   # one range probe and one host sync per frame
                 for (r, _), (p, s) in zip(todo, regions_fn(sr, g, [mask for _, mask in todo])):
                     acc[r].append((float(p), float(s)))
             else:
@@ -142,6 +154,12 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
                 lo, hi = torch.stack([pe[0], se[0]]), torch.stack([pe[1], se[1]])
                 extrema[0::2] = torch.minimum(extrema[0::2], lo)
                 extrema[1::2] = torch.maximum(extrema[1::2], hi)
+    if rows:
+        table = torch.stack(rows).cpu()   # [N, 4, 4]: the one fetch
+        for n in range(N):
+            for k, r in enumerate(regions):
+                if r != "past" or n > 0:   # frame 0 has no past ring
+                    acc[r].append((float(table[n, k, 0]), float(table[n, k, 1])))
     out: Dict[str, object] = {"trajectory": traj, "frames": N}
     if score_maps:
         out.update({k: torch.stack(v) for k, v in maps.items() if v})
@@ -176,6 +194,8 @@ def main(argv=None):
                     help="the streaming model test_video.py builds for this code: 13 MRCF_simple_v13, 15 MRCF_simple_v15, 18 MRCF_simple_v18")
     ap.add_argument("--score-maps", action="store_true",
                     help="also time the stream with the per-window score maps of the output and of the bilinear x8 baseline")
+    ap.add_argument("--fused-metrics", action="store_true",
+                    help="also time the stream with the four regions of a frame scored by one fused call and fetched once at the end")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     if a.model_code == 18:
@@ -220,6 +240,13 @@ def main(argv=None):
         torch.cuda.synchronize()
         extra["frames_per_sec_with_score_maps"] = a.frames / (time.perf_counter() - t0)
         extra["score_extrema"] = [float(v) for v in sm["score_extrema"].cpu()]
+    if a.fused_metrics:
+        run_gaze_video(m, lr[:3], gt[:3], a.sigma, a.fv_size, a.seed, fused_metrics=True)   # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run_gaze_video(m, lr, gt, a.sigma, a.fv_size, a.seed, regional_dcn=a.regional_dcn > 0, rg=a.regional_dcn, fused_metrics=True)
+        torch.cuda.synchronize()
+        extra["frames_per_sec_with_fused_region_metrics"] = a.frames / (time.perf_counter() - t0)
     model = "" if a.model_code == 18 else f", {type(m).__name__}"
     print(json.dumps({"workload": f"BASELINE config 3 shape: {a.frames} streamed frames {a.lr_h}x{a.lr_w} -> x8, sigma_T={a.sigma}, fp32, synthetic{model}",
                       "frames_per_sec_with_region_metrics": a.frames / dt, "frames_per_sec_model_only": a.frames / dt_model, **extra, **res}))

@@ -87,6 +87,39 @@ def calc_psnr_and_ssim_regions(sr, hr, masks):
     return out
 
 
+def frame_metrics_table(sr, hr, masks=None, luma=False):
+    """float64 device tensor [n, 1+m, 4] = (PSNR, SSIM, PSNR-Y, SSIM-Y) of every frame of sr / hr [n,C,H,W] for the whole frame (row 0)
+    and each of m <= 7 region masks (rows 1..m), from one fused pass over the batch (crfp_frame_metrics_f32): what
+    calc_psnr_and_ssim_cuda(sr[i:i+1], hr[i:i+1], mask) gives per frame and region and, with luma (C == 3), the same on
+    bgr2ycbcr(y_only=True) of both images, each with its own range conversion, both picked on the device.  masks: None, a list of m
+    tensors broadcastable to [n,1,H,W], or one [n,m,H,W] tensor (bool, or non-zero = inside).  An empty region is NaN in its row (the
+    per-region functions divide by zero there); without luma columns 2 and 3 are NaN.  The call does not synchronise."""
+    sr, hr = _dev(sr, "sr"), _dev(hr, "hr")
+    if sr.dim() != 4 or sr.shape != hr.shape:
+        raise ValueError(f"sr / hr must be [n,C,H,W] of one shape, got {tuple(sr.shape)} and {tuple(hr.shape)}")
+    n, c, h, w = sr.shape
+    if masks is None:
+        m, m8 = 0, None
+    else:
+        if torch.is_tensor(masks):
+            if masks.dim() != 4 or masks.shape[0] != n or tuple(masks.shape[2:]) != (h, w):
+                raise ValueError(f"masks must be [n,m,H,W] = [{n},m,{h},{w}], got {tuple(masks.shape)}")
+            mm = masks.to(sr.device)
+        else:
+            mm = [k.to(sr.device) for k in masks]
+            mm = torch.cat([(k if k.dtype == torch.bool else k != 0).expand(n, 1, h, w) for k in mm], 1) if mm else None
+        m = 0 if mm is None else mm.shape[1]
+        m8 = None if m == 0 else (mm if mm.dtype == torch.bool else mm != 0).contiguous().view(torch.uint8)
+    L = _lib.lib()
+    out = torch.empty((n, 1 + m, 4), dtype=torch.float64, device=sr.device)
+    ws_bytes = L.crfp_frame_metrics_workspace_bytes(n, m, h, w)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=sr.device)
+    with torch.cuda.device(sr.device):
+        _lib.check(L.crfp_frame_metrics_f32(sr.data_ptr(), hr.data_ptr(), None if m8 is None else m8.data_ptr(), out.data_ptr(), n, c, m, h, w,
+                                            _lib.METRICS_LUMA if luma else 0, ws.data_ptr(), ws_bytes, _stream()), "crfp_frame_metrics_f32")
+    return out
+
+
 def window_scores(sr, hr, kernel_size=10, stride=5):
     """Raw per-window (psnr [dB], ssim) maps, [Hr,Wr] for [C,H,W] input and [n,Hr,Wr] for [n,C,H,W], of every kernel_size x
     kernel_size window at `stride`, each window scored as an image of its own (zero padding at the window's border).  The range

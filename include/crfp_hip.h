@@ -34,6 +34,7 @@
  *                             one-frame-per-call variants model/CRFP_test.py:1184-1486 MRCF_simple_v13 / :1805-2113 v15
  *   crfp_psnr_partial_f32     utils.py:166-185,242-254,328-330 (psnr_cuda / bgr2ycbcr(y_only))
  *   crfp_window_scores_f32    test_video.py:23-63 foveated_metric (per-window PSNR / SSIM maps)
+ *   crfp_frame_metrics_f32    trainer.py:348-369 / test_video.py:360-370 (per-frame, per-region PSNR / SSIM / PSNR-Y / SSIM-Y)
  *   crfp_spynet_forward       model/CRFP.py:554-741 SPyNet.forward (+ SPyNetBasicModule, `conv` :145-152)
  *   crfp_convkxk_f32          model/CRFP.py:145-152 `conv`: ReLU -> nn.Conv2d(k, stride 1, pad k/2)
  *   crfp_upsample_bilinear_ac_f32  F.interpolate(..., bilinear, align_corners=True) (model/CRFP.py:647-651)
@@ -179,6 +180,21 @@ int crfp_psnr_ssim_partial_f32(const float* a, const float* b, const unsigned ch
  * a null pointer, a bad size or a short workspace is CRFP_E_BADARG.  Each output element is written once (no atomics). */
 size_t crfp_window_scores_workspace_bytes(int n);
 int crfp_window_scores_f32(const float* hr, const float* sr, float* psnr, float* ssim, int n, int c, int h, int w, int k, int stride,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* The eval figures of a batch in one fused pass: for every frame, and for the whole frame (row 0) plus each of m byte masks (rows
+ * 1..m; non-zero = inside), PSNR, SSIM, PSNR-Y, SSIM-Y as logged by trainer.py:348-369 and test_video.py:360-370 (utils.py:166-185,
+ * 242-254; luma = 24.966 c0 + 128.553 c1 + 65.481 c2 + 16 in fp32 on the channels as they arrive, utils.py:328-330).  sr, hr:
+ * [n,c,h,w] fp32; masks: [n,m,h,w] bytes or NULL when m == 0; out: [n,1+m,4] doubles, each written once.  The range conversion of
+ * utils.py:244-250 is decided on the device, per frame and separately for RGB (span of hr) and for luma (span of luma(hr)); PSNR is
+ * -20 log10(sqrt(se / (msum c))), or -20 log10(sqrt((1/255)^2 / (c h w))) when that mse is 0 (c = 1 for luma), SSIM the masked mean
+ * of the 11 x 11 gaussian map.  An empty region is NaN in all four columns (the reference divides by zero there); without
+ * CRFP_METRICS_LUMA columns 2 and 3 are NaN.  A batch equals n calls bit for bit; no atomics, no host synchronisation, the workspace
+ * needs no initialisation.  Errors: null pointer, n < 1, c outside 1..4, m outside 0..7, null masks with m > 0, LUMA with c != 3
+ * (CRFP_E_BADARG); a short or missing workspace (CRFP_E_WORKSPACE).  No lower size limit: a frame smaller than the filter is legal. */
+#define CRFP_METRICS_LUMA 1 /* also score luma (c == 3): columns 2 and 3 */
+size_t crfp_frame_metrics_workspace_bytes(int n, int m, int h, int w);
+int crfp_frame_metrics_f32(const float* sr, const float* hr, const uint8_t* masks, double* out, int n, int c, int m, int h, int w, int flags,
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- CRFP_DSV engine (mid_channels=32, hr_dcn=True, offset_prop=True; y_only selectable).

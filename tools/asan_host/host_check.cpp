@@ -124,6 +124,53 @@ int main() {
                 }
         EXPECT(crfp_stub_launches() == l0 + 2 * 3 * 4 * 4 * 2);
     }
+    // the frame metrics table: sizing, every refusal before the first launch, three launches per accepted call
+    {
+        const uint8_t* const k16 = reinterpret_cast<const uint8_t*>(16);
+        double* const d16 = reinterpret_cast<double*>(16);
+        const size_t probe = 256 * 4 * sizeof(float), cell = 5 * sizeof(double);
+        EXPECT(crfp_frame_metrics_workspace_bytes(1, 0, 16, 64) == probe + cell);                  // exactly one tile
+        EXPECT(crfp_frame_metrics_workspace_bytes(1, 0, 17, 65) == probe + 4 * cell);
+        EXPECT(crfp_frame_metrics_workspace_bytes(5, 3, 70, 150) == 5 * (probe + 15 * 4 * cell));
+        EXPECT(crfp_frame_metrics_workspace_bytes(1, 7, 1, 1) == probe + 8 * cell);
+        EXPECT(crfp_frame_metrics_workspace_bytes(2, 3, 1440, 2560) == 2 * (probe + 3600 * 4 * cell));
+        EXPECT(crfp_frame_metrics_workspace_bytes(0, 0, 8, 8) == 0 && crfp_frame_metrics_workspace_bytes(1, 8, 8, 8) == 0);
+        EXPECT(crfp_frame_metrics_workspace_bytes(1, -1, 8, 8) == 0 && crfp_frame_metrics_workspace_bytes(1, 0, 0, 8) == 0);
+        EXPECT(crfp_frame_metrics_workspace_bytes(1, 0, 8, -2) == 0);
+        EXPECT(crfp_frame_metrics_workspace_bytes(1, 0, 2147483647, 2147483647) > 0);              // no overflow on the way to a size
+        const size_t wsb = crfp_frame_metrics_workspace_bytes(2, 3, 24, 31);
+        const long l0 = crfp_stub_launches();
+        EXPECT(crfp_frame_metrics_f32(nullptr, p16, k16, d16, 2, 3, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(crfp_frame_metrics_f32(p16, nullptr, k16, d16, 2, 3, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, nullptr, 2, 3, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, nullptr, d16, 2, 3, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);    // m > 0 without masks
+        EXPECT(std::strstr(crfp_last_error_string(), "masks") != nullptr);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 0, 3, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 0, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 5, 3, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 3, -1, 24, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 3, 8, 24, 31, 0, p16, (size_t)1 << 30, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 3, 3, 0, 31, 0, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 1, 3, 24, 31, CRFP_METRICS_LUMA, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "LUMA") != nullptr);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 4, 3, 24, 31, CRFP_METRICS_LUMA, p16, wsb, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 3, 3, 24, 31, 2, p16, wsb, nullptr) == CRFP_E_BADARG);        // unknown flag
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 3, 3, 24, 31, 0, p16, wsb - 1, nullptr) == CRFP_E_WORKSPACE);  // one byte short
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 2, 3, 3, 24, 31, 0, nullptr, wsb, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_frame_metrics_f32(p16, p16, k16, d16, 70000, 3, 0, 24, 31, 0, p16, (size_t)1 << 40, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_stub_launches() == l0);
+        int accepted = 0;
+        for (int c : {1, 3, 4})
+            for (int m : {0, 3, 7})
+                for (const auto& g : {std::initializer_list<int>{1, 1}, {7, 9}, {16, 64}, {17, 65}, {1440, 2560}}) {
+                    const int h = g.begin()[0], w = g.begin()[1];
+                    const size_t need = crfp_frame_metrics_workspace_bytes(2, m, h, w);
+                    EXPECT(crfp_frame_metrics_f32(p16, p16, m ? k16 : nullptr, d16, 2, c, m, h, w, c == 3 ? CRFP_METRICS_LUMA : 0, p16, need, nullptr) == 0);
+                    ++accepted;
+                }
+        EXPECT(crfp_stub_launches() == l0 + 3 * accepted);
+    }
     // ---- whole engine calls on the stub runtime (tools/asan_host/hip_stub.cpp: every HIP call succeeds, no kernel runs): the host side of a
     // call -- argument checks, Layout arenas, the launch-argument tables of ~50 launches per frame, the fork / join of the side stream, the
     // per-thread stream table and crfp_shutdown() -- under the sanitizers.  Device pointers are fabricated and never dereferenced on the host.
