@@ -105,12 +105,12 @@ _CLIP = _PACK | {"batch_workspace_bytes", "batch_status_offset", "forward_batch"
 _STREAM = _CLIP | {"stream_batch"}                                                  # + one frame per call
 _DSV = _STREAM | {"fnet_forward", "debug_fetch"}
 _NUMEL = frozenset(("param_numel",))   # shapes do not depend on the storage type
-# dsv: CRFP_DSV.  cra: CRFP_DSV_CRA, its own parameter table, clip forward only.  simple / dense: the CRFP_simple / CRFP wirings -- CRFP_DSV's
-# parameter names with their own shapes -- clip forward and the one-frame-per-call form (MRCF_simple_v13 / v15).  rt: the regional benchmark
-# wiring, fp32 storage only, with a forward call and a workspace query of its own.
+# dsv: CRFP_DSV.  cra: CRFP_DSV_CRA, its own parameter table, clip forward and the one-frame-per-call form (MRCF_simple_v18_cra).  simple /
+# dense: the CRFP_simple / CRFP wirings -- CRFP_DSV's parameter names with their own shapes -- clip forward and the one-frame-per-call form
+# (MRCF_simple_v13 / v15).  rt: the regional benchmark wiring, fp32 storage only, with a forward call and a workspace query of its own.
 FAMILIES = {
     "dsv": Family("crfp_dsv_", "dsv", NUM_PARAMS, "CRFP_DSV", _DSV, _DSV - _NUMEL),
-    "cra": Family("crfp_cra_", "cra", CRA_NUM_PARAMS, "CRFP_DSV_CRA", _CLIP, _CLIP - _NUMEL),
+    "cra": Family("crfp_cra_", "cra", CRA_NUM_PARAMS, "CRFP_DSV_CRA", _STREAM, _STREAM - _NUMEL),
     "simple": Family("crfp_simple_", "dsv", NUM_PARAMS, "CRFP_simple", _STREAM, _STREAM - _NUMEL),
     "dense": Family("crfp_dense_", "dsv", NUM_PARAMS, "CRFP", _STREAM, _STREAM - _NUMEL),
     "rt": Family("crfp_rt_", "rt", RT_NUM_PARAMS, "MRCF_simple_v18", _PACK | {"workspace_bytes", "forward_clip"}, frozenset()),

@@ -1508,15 +1508,22 @@ int CRFP_API(crfp_dsv_forward_clip)(const void* packed, int flags, const float* 
 
 // One frame of n independent sequences in lock-step (the reference's streaming forward carries the batch axis too, model/CRFP_test.py:2250-2451):
 // lr / lr_prev [n,3,h,w], fv [n,3,8h,8w], mk [n,1,8h,8w], out [n,3|1,8h,8w]; the workspace holds the n recurrent states.
-// wiring: W_DSV (MRCF_simple_v18) or W_SIMPLE / W_DENSE (MRCF_simple_v13 / v15, model/CRFP_test.py:1184-1486 / 1805-2113: CRFP_simple / CRFP
-// with the state kept between calls).  Same clip kernels, same buffer sets, same two schedules for every wiring.
+// wiring: W_DSV (MRCF_simple_v18), W_SIMPLE / W_DENSE (MRCF_simple_v13 / v15, model/CRFP_test.py:1184-1486 / 1805-2113: CRFP_simple / CRFP
+// with the state kept between calls) or W_CRA (MRCF_simple_v18_cra, :2480-2861: CRFP_DSV_CRA likewise).  Same clip kernels, same buffer sets,
+// same two schedules for every wiring.
+// W_CRA: the four-level fovea encoder needs neither the state nor the flow, so it is in frame_pre's part 1 and goes wherever the fovea blend
+// goes.  Its level features c_lv[par][k] belong to buffer set par like x_hr[par] -- written by the pre-work of call i, read by frame i's
+// cra_blend launches on the caller's stream -- and fall under the same ordering rules, the early start below included.  Its temporaries
+// (c_s1, c_a, c_b) have one copy: only frame_pre touches them, and two frame_pre of one sequence never overlap (same stream, or a fork / join
+// between them).  c_y / c_f belong to Runner::frame (the caller's stream).
 static int stream_batch_impl(int wiring, const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
                              const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
                              size_t workspace_bytes, void* stream) {
     const int y_only = flags & CRFP_DSV_Y_ONLY;
     if (n < 1) { set_error("dsv_stream_batch: n = %d", n); return CRFP_E_BADARG; }
     // v13 / v15 compute the regional mask's x0.25 resample fg_lv0 (model/CRFP_test.py:1357-1359, 1978-1980) but never read it; only v18
-    // scales by it (:2347,2361,2375).  `fg` is accepted and ignored there, for any n: no fg_prep launch, no fg branch in Runner::frame.
+    // scales by it (:2347,2361,2375).  v18_cra's forward takes `fgs` and never reads it at all (:2620-2834).  `fg` is accepted and ignored for
+    // these three wirings, for any n: no fg_prep launch, no fg branch in Runner::frame.
     if (wiring != W_DSV) fg = nullptr;
     if (fg && n > 1) { set_error("dsv_stream_batch: the regional mask `fg` is supported for one sequence per call (n = 1)"); return CRFP_E_UNSUPPORTED; }
     if (n > kFlatFrames) { set_error("dsv_stream_batch: at most %d sequences per call (got %d)", kFlatFrames, n); return CRFP_E_UNSUPPORTED; }
@@ -1596,8 +1603,8 @@ static int stream_batch_impl(int wiring, const void* packed, int flags, const fl
         hipEvent_t ev_start = ss.event(0), ev_side = ss.event(1);
         if (!ss.ok) return fail("hipEventCreate");
         if (hipEventRecord(ev_start, main_s) != hipSuccess) return fail("record");
-        // Early start is safe only behind a call whose side work waited for ITS fork event: set par was last read by frame i - 2 on the
-        // caller's stream, which that wait ordered in front of everything the side stream did since.
+        // Early start is safe only behind a call whose side work waited for ITS fork event: set par (W_CRA: its three fovea levels too) was
+        // last read by frame i - 2 on the caller's stream, which that wait ordered in front of everything the side stream did since.
         const bool early = ctx->chained;
         R.s = ss.s;
         forked = true;
@@ -1682,6 +1689,15 @@ int CRFP_API(crfp_dense_stream_batch)(const void* packed, int flags, const float
                           const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
                           size_t workspace_bytes, void* stream) {
     return stream_batch_impl(W_DENSE, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
+}
+
+// The same call for the reference's streaming MRCF_simple_v18_cra (the CRFP_DSV_CRA wiring): packed = crfp_cra_pack_weights' buffer, workspace
+// sized by crfp_cra_batch_workspace_bytes(n, 1, h, w); flags, n <= 32 and status words as crfp_dsv_stream_batch; `fg` is accepted and ignored
+// for any n.
+int CRFP_API(crfp_cra_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return stream_batch_impl(W_CRA, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
 }
 
 int CRFP_API(crfp_dsv_stream_frame)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,

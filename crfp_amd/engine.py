@@ -111,8 +111,8 @@ def embed_mid32(state_dict, mid: int, wiring: str = "dsv", y_only: bool = False)
 
 # why a handle does not run an operation its family's row lacks (or, for a clip handle, holds back)
 _REFUSALS = {
-    "stream_batch": "a clip handle; the one-frame-per-call schedules are DSVEngine's and, for CRFP_simple / CRFP, SimpleStreamEngine's / "
-                    "DenseStreamEngine's (none for CRFP_DSV_CRA)",
+    "stream_batch": "a clip handle; the one-frame-per-call schedules are DSVEngine's and, for CRFP_DSV_CRA / CRFP_simple / CRFP, "
+                    "CRAStreamEngine's / SimpleStreamEngine's / DenseStreamEngine's",
     "fnet_forward": "use the model's flow network modules ({model}.compute_flow)",
     "debug_fetch": "debug_fetch reads the CRFP_DSV workspace layout",
 }
@@ -323,8 +323,8 @@ class DSVEngine(_Handle):
         """lr[3,h,w], fv[3,8h,8w], mk[1,8h,8w], optional regional mask fg[1,8h,8w] -> [3|1,8h,8w]; the first
         call after clear_states() starts a sequence.  With a leading batch axis -- lr[n,3,h,w], fv[n,3,8h,8w], mk[n,1,8h,8w] -> [n,3|1,8h,8w] --
         the n sequences advance in lock-step in ONE call (the family's stream_batch: n <= 32, no fg), per sequence bit-identical to n engines.
-        SimpleStreamEngine / DenseStreamEngine (the reference's MRCF_simple_v13 / v15) accept ``fg`` for any n and it has no effect: these
-        two models never read it.
+        CRAStreamEngine / SimpleStreamEngine / DenseStreamEngine (the reference's MRCF_simple_v18_cra / v13 / v15) accept ``fg`` for any n
+        and it has no effect: these three models never read it.
         With ``inputs_resident = True`` the library reads lr / fv / mk on its own side stream WITHOUT waiting for the caller's stream
         (that is the point: frame i's flow network runs beside frame i - 1).  The tensors must therefore be complete when this
         method is called: nothing still queued on the current torch stream may be writing them (a non_blocking host-to-device copy, a
@@ -462,10 +462,11 @@ class RuntimeEngine(_Handle):
 
 
 class CRAEngine(DSVEngine):
-    """The reference's CRFP_DSV_CRA wiring (crfp_cra_* entry points, include/crfp_hip.h).  Clip forward only: the reference's streaming form
-    of this wiring (MRCF_simple_v18_cra) is commented out in test_video.py:187."""
+    """The reference's CRFP_DSV_CRA wiring (crfp_cra_* entry points, include/crfp_hip.h).  A clip handle: the wiring's one-frame-per-call
+    schedule (the reference's MRCF_simple_v18_cra) is CRAStreamEngine's."""
 
     WIRING = "cra"
+    _withheld = frozenset({"stream_batch"})
 
 
 class SimpleEngine(CRAEngine):
@@ -481,6 +482,14 @@ class DenseEngine(SimpleEngine):
     state as a third input of every residual block."""
 
     WIRING = "dense"
+
+
+class CRAStreamEngine(CRAEngine):
+    """CRAEngine plus the one-frame-per-call schedule of the reference's streaming MRCF_simple_v18_cra (model/CRFP_test.py:2480-2861):
+    ``stream_frame`` / ``clear_states`` -- the copy of the previous frame, the ``inputs_resident`` checks and the overflow policies
+    ("fallback" refused) -- on crfp_cra_stream_batch.  ``fg`` is accepted for any n and has no effect: the model never reads it."""
+
+    _withheld = frozenset()
 
 
 class SimpleStreamEngine(SimpleEngine):

@@ -192,13 +192,20 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--model-code", type=int, default=18, choices=(13, 15, 18),
                     help="the streaming model test_video.py builds for this code: 13 MRCF_simple_v13, 15 MRCF_simple_v15, 18 MRCF_simple_v18")
+    ap.add_argument("--cra", action="store_true",
+                    help="with --model-code 18: MRCF_simple_v18_cra, the streaming form of the cross-resolution wiring CRFP_DSV_CRA")
     ap.add_argument("--score-maps", action="store_true",
                     help="also time the stream with the per-window score maps of the output and of the bilinear x8 baseline")
     ap.add_argument("--fused-metrics", action="store_true",
                     help="also time the stream with the four regions of a frame scored by one fused call and fetched once at the end")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
-    if a.model_code == 18:
+    if a.cra and a.model_code != 18:
+        ap.error("--cra selects MRCF_simple_v18_cra: it goes with --model-code 18")
+    if a.cra:   # its own parameter table: weights seeded from it, as for the ablation wirings
+        m = CRFP.MRCF_simple_v18_cra(device=dev, mid_channels=32, y_only=False, hr_dcn=True, offset_prop=True)
+        sd = synth.make_state_dict_like({k: tuple(v.shape) for k, v in m.state_dict().items()}, 7)
+    elif a.model_code == 18:
         sd = synth.make_state_dict(7)
         m = CRFP.MRCF_simple_v18(device=dev, mid_channels=32)
     else:   # the ablation wirings have other shapes under the same keys: weights seeded from the model's own table
@@ -247,7 +254,7 @@ def main(argv=None):
         run_gaze_video(m, lr, gt, a.sigma, a.fv_size, a.seed, regional_dcn=a.regional_dcn > 0, rg=a.regional_dcn, fused_metrics=True)
         torch.cuda.synchronize()
         extra["frames_per_sec_with_fused_region_metrics"] = a.frames / (time.perf_counter() - t0)
-    model = "" if a.model_code == 18 else f", {type(m).__name__}"
+    model = "" if a.model_code == 18 and not a.cra else f", {type(m).__name__}"
     print(json.dumps({"workload": f"BASELINE config 3 shape: {a.frames} streamed frames {a.lr_h}x{a.lr_w} -> x8, sigma_T={a.sigma}, fp32, synthetic{model}",
                       "frames_per_sec_with_region_metrics": a.frames / dt, "frames_per_sec_model_only": a.frames / dt_model, **extra, **res}))
 

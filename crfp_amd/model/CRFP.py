@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from crfp_amd import ops
 from crfp_amd.dcn_v2 import DCNv2
-from crfp_amd.engine import CRAEngine, DenseEngine, DenseStreamEngine, DSVEngine, PackedModel, SimpleEngine, SimpleStreamEngine
+from crfp_amd.engine import CRAEngine, CRAStreamEngine, DenseEngine, DenseStreamEngine, DSVEngine, PackedModel, SimpleEngine, SimpleStreamEngine
 from . import LTE
 
 
@@ -368,13 +368,22 @@ class CRFP_DSV(nn.Module, _ClipEngine):
         than one frame end in AttributeError (:336); ``hr_dcn=False`` builds 32-channel dcn_3 / forward_resblocks_3 and feeds them
         last_channels-wide tensors, a channel-count RuntimeError on the first frame (:1668).  Tensors between operators are NCHW torch
         tensors on the device; concatenations ride as the second input of the consuming conv where the operator has one."""
+        return self._composed(lrs, fvs, mks)[0]
+
+    def _composed(self, lrs, fvs, mks, state=None, prev_lr=None):
+        """forward_composed's loop from a given recurrent state -- (the 8x state [n, last, 8h, 8w], the three carried level tensors) -- and the
+        LR frame [n, 3, h, w] in front of lrs[:, 0] (both None: a clip starts from nothing) -> (out [n, t, 3|1, 8h, 8w], the state after the
+        last frame).  The streaming model of the CRFP_DSV_CRA wiring carries the two between calls."""
         if lrs.dim() != 5 or not lrs.is_cuda:
             raise RuntimeError("crfp_amd: forward_composed needs CUDA/HIP tensors lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], mks[n,t,1,8h,8w]")
         n, t, _, h, w = lrs.shape
         m, l = self.mid_channels, self.last_channels
         lrs = lrs.float().contiguous()
         mkf = mks.to(torch.float32)
-        flows, _ = self.compute_flow(lrs) if t > 1 else (None, None)
+        # flows[:, i] belongs to frame i + 1 of the clip; with a previous frame it is prepended and frame i uses flows[:, i]
+        ext = lrs if prev_lr is None else torch.cat((prev_lr.float()[:, None], lrs), 1)
+        shift = 1 if prev_lr is None else 0
+        flows = self.compute_flow(ext)[0] if ext.shape[1] > 1 else None
         flat = lrs.reshape(n * t, 3, h, w)
         up8_all = ops.upsample_bilinear(flat, scale_factor=8)                               # :1538
         x_lr = self.encoder_lr(flat, islr=True)[2].view(n, t, m, h, w)                      # :1540
@@ -385,10 +394,14 @@ class CRFP_DSV(nn.Module, _ClipEngine):
         state2 = lrs.new_zeros(n, m, 2 * h, 2 * w)              # the 2x-resolution view of the state (zero before the first frame)
         state8 = lrs.new_zeros(n, l, 8 * h, 8 * w)
         carry = [lrs.new_zeros(n, m - keep, 2 * h, 2 * w) for _ in levels]
+        first = state is None
+        if not first:
+            state, carry = state[0], list(state[1])
         outs = []
         for i in range(t):
             cur = self.upsample(x_lr[:, i].contiguous())
-            if i == 0:
+            if first:
+                first = False
                 # no history yet: [features | zero state | zero carry] through each level's residual block (:1634-1667)
                 for k, (_, block) in enumerate(levels):
                     y = self._after_level(k, block(torch.cat((cur, state2, carry[k]), 1)), side, i, mkf)
@@ -396,7 +409,7 @@ class CRFP_DSV(nn.Module, _ClipEngine):
                 up = torch.nn.functional.leaky_relu(self.upsample_post(cur), 0.1)
                 state = self.forward_resblocks_3(torch.cat((up, state8), 1))
             else:
-                flow = flows[:, i - 1].contiguous()
+                flow = flows[:, i - shift].contiguous()
                 f2 = ops.upsample_bilinear(flow, scale_factor=2, mul=2.0).permute(0, 2, 3, 1).contiguous()     # [n, 2h, 2w, 2], (x, y)
                 f8 = ops.upsample_bilinear(flow, scale_factor=8, mul=8.0).permute(0, 2, 3, 1).contiguous()
                 prev8 = state
@@ -420,7 +433,7 @@ class CRFP_DSV(nn.Module, _ClipEngine):
             lr = lrs[:, i]
             base = (0.299 * lr[:, 0] + 0.587 * lr[:, 1] + 0.114 * lr[:, 2]).unsqueeze(1) if self.y_only else lr
             outs.append(_run(self.conv_last, state) + ops.upsample_bilinear(base.contiguous(), scale_factor=8))
-        return torch.stack(outs, dim=1)
+        return torch.stack(outs, dim=1), (state, carry)
 
     # hooks of forward_composed that the CRFP_DSV_CRA wiring overrides
     def _encode_hr(self, x6, n, t):
@@ -469,9 +482,10 @@ class CRFP_DSV_CRA(CRFP_DSV):
     factory line): CRFP_DSV plus a cross-resolution fusion of the fovea into every 2x level.  ``encoder_hr`` is the four-level
     ``LTE_simple_hr_ps``; after each level's residual block the 32 features are replaced, under the x0.25-resampled fovea mask, by
     ``conv_tttf_k(cat(features, fovea level k))`` (:2533-2535,2549-2551,2565-2567 and the first-frame twins).  Same constructor,
-    same state_dict table as the reference (tests/golden/dsv_flags.npz).  mid_channels = 32 with both flags on runs the one-call engine
-    schedule of this wiring (``crfp_cra_forward_batch``, crfp_amd.engine.CRAEngine: clip forward, lock-step batches, both storage
-    types); every other constructor combination runs ``forward_composed`` (per-operator HIP calls), as in CRFP_DSV."""
+    same state_dict table as the reference (tests/golden/dsv_flags.npz).  mid_channels 32, or 16 embedded, with both flags on runs the
+    one-call engine schedule of this wiring (``crfp_cra_forward_batch``, crfp_amd.engine.CRAEngine: clip forward, lock-step batches, both
+    storage types); every other constructor combination runs ``forward_composed`` (per-operator HIP calls), as in CRFP_DSV.  One frame per
+    call is MRCF_simple_v18_cra's."""
 
     _engine_class = CRAEngine
 
@@ -496,7 +510,7 @@ class CRFP_DSV_CRA(CRFP_DSV):
         return self.spynet(lrs[:, 1:].reshape(-1, c, h, w).contiguous(), lrs[:, :-1].reshape(-1, c, h, w).contiguous()).view(n, t - 1, 2, h, w), None
 
     def forward_stream(self, lrs, fvs, mks, fgs=None):
-        raise NotImplementedError("crfp_amd: the one-frame-per-call interface belongs to the plain CRFP_DSV wiring (model/CRFP_test.py)")
+        raise NotImplementedError("crfp_amd: CRFP_DSV_CRA is the clip model; its one-frame-per-call form is MRCF_simple_v18_cra")
 
     def _encode_hr(self, x6, n, t):
         lv0, lv1, lv2, lv3 = self.encoder_hr(x6)
@@ -517,7 +531,7 @@ class CRFP_simple(nn.Module, _ClipEngine):
     ``hr_dcn=False`` runs dcn_3 / forward_resblocks_3 at 2x resolution in mid_channels and up-samples afterwards (:1066-1078),
     ``offset_prop=False`` drops the offset hand-down (:1032-1033).  The dense variant feeds each residual block the warped previous
     state as a third input (:1311,1316,1321).  Same constructor and state_dict table as the reference (tests/golden/dsv_flags.npz).
-    mid_channels = 32 with both flags on runs the one-call engine schedule of the wiring (``crfp_simple_forward_batch`` /
+    mid_channels 32, or 16 embedded, with both flags on runs the one-call engine schedule of the wiring (``crfp_simple_forward_batch`` /
     ``crfp_dense_forward_batch``, crfp_amd.engine.SimpleEngine / DenseEngine: clip forward, lock-step batches, both storage types);
     every other constructor combination runs ``forward_composed`` (per-operator HIP calls)."""
 
@@ -666,16 +680,17 @@ class MRCF_simple_v18(CRFP_DSV):
 
 
 class _AblationStream:
-    """One frame (or several) per call for the CRFP_simple / CRFP wirings: the reference's MRCF_simple_v13 / v15 (model/CRFP_test.py:1184-1486,
-    1805-2113) are those two models with the recurrent state and the previous LR frame kept on the model between calls, the previous frame
-    prepended to the flow pairs, and a ``fgs`` argument they compute a resample of but never use (:1357-1359, 1978-1980).  mid_channels 32
+    """One frame (or several) per call for the CRFP_simple / CRFP / CRFP_DSV_CRA wirings: the reference's MRCF_simple_v13 / v15 / v18_cra
+    (model/CRFP_test.py:1184-1486, 1805-2113, 2480-2861) are those models with the recurrent state and the previous LR frame kept on the model
+    between calls, the previous frame prepended to the flow pairs, and a ``fgs`` argument they never use (v13 / v15 compute a resample of it,
+    :1357-1359, 1978-1980; v18_cra does not read it).  The clip model supplies ``_composed(lrs, fvs, mks, state, prev_lr)``.  mid_channels 32
     (16: embedded) with both flags on streams through the wiring's one-frame-per-call engine call (n > 1 sequences in lock-step, one call per
     frame; ``storage`` and ``inputs_resident`` as on MRCF_simple_v18); every other constructor combination streams through the per-operator
     composition with the state carried between calls."""
 
     def __init__(self, device, mid_channels=16, y_only=False, hr_dcn=True, offset_prop=True, spynet_pretrained=None):
         super().__init__(device, mid_channels, y_only, hr_dcn, offset_prop, spynet_pretrained)
-        self._stream_state = self._stream_prev = None   # composed path: state [n, last, 8h, 8w] and the last LR frame [n, 3, h, w]
+        self._stream_state = self._stream_prev = None   # composed path: the clip model's recurrent state and the last LR frame [n, 3, h, w]
 
     def clear_states(self):
         self._stream_state = self._stream_prev = None
@@ -712,3 +727,19 @@ class MRCF_simple_v15(_AblationStream, CRFP):
     """The reference's streaming CRFP (model/CRFP_test.py:1805-2113; test_video.py's model code 15): see _AblationStream."""
 
     _engine_class = DenseStreamEngine
+
+
+class MRCF_simple_v18_cra(_AblationStream, CRFP_DSV_CRA):
+    """The reference's streaming CRFP_DSV_CRA (model/CRFP_test.py:2480-2861: MRCF_simple_v18's constructor over CRFP_DSV_CRA's module table, the
+    8x state, the three carried level tensors and the previous LR frame kept between calls): see _AblationStream.  The engine path is
+    ``crfp_cra_stream_batch`` (crfp_amd.engine.CRAStreamEngine); the composition carries CRFP_DSV_CRA's state between calls."""
+
+    _engine_class = CRAStreamEngine
+
+    def __init__(self, device, mid_channels=16, y_only=False, hr_dcn=True, offset_prop=True, split_ratio=3,
+                 spynet_pretrained=None):
+        if split_ratio != 3:
+            raise NotImplementedError("split_ratio 3 only (the reference's shipped configuration)")
+        super().__init__(device, mid_channels, y_only, hr_dcn, offset_prop, spynet_pretrained)
+
+    forward_stream = _AblationStream.forward

@@ -287,10 +287,20 @@ size_t crfp_cra_batch_workspace_bytes(int n, int t, int h, int w);
 size_t crfp_cra_batch_status_offset(int n, int t, int h, int w);
 int crfp_cra_forward_batch(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
                            float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+/* Streaming form of the wiring: the reference's one-frame-per-call MRCF_simple_v18_cra (model/CRFP_test.py:2480-2861), i.e. CRFP_DSV_CRA
+ * with the state kept between calls.  Arguments, flags (CRFP_DSV_INPUTS_RESIDENT, CRFP_DSV_SINGLE_STREAM, CRFP_DSV_Y_ONLY and -- fp32 entry
+ * only -- CRFP_DSV_STRICT_F32), the n <= 32 limit and the status words of crfp_dsv_stream_batch; packed weights are crfp_cra_pack_weights',
+ * the workspace is sized by crfp_cra_batch_workspace_bytes(n, 1, h, w) and its status words sit at crfp_cra_batch_status_offset(n, 1, h, w).
+ * `fg` is accepted and ignored for any n: the reference's forward takes `fgs` and never reads it.  Streaming a clip one frame per call gives
+ * crfp_cra_forward_batch's bits.  The _bf16 twin is declared with the other bf16-storage entry points below. */
+int crfp_cra_stream_batch(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* ---- CRFP_simple / CRFP engines: the reference's two ablation wirings in front of CRFP_DSV -- CRFP_simple ("v13", model/CRFP.py:816-1099)
- * and CRFP ("v15", :1101-1385) -- as one-call schedules, for mid_channels = 32 with hr_dcn = offset_prop = True (round 6; every other
- * constructor combination stays a per-operator composition in the Python mirror).  Against CRFP_DSV: `upsample` keeps all 32 features
+ * and CRFP ("v15", :1101-1385) -- as one-call schedules, for mid_channels 32, or 16 embedded (the Python mirror places the narrower model's
+ * parameters inside the 32-channel table at pack time), with hr_dcn = offset_prop = True (round 6; every other constructor combination stays
+ * a per-operator composition in the Python mirror).  Against CRFP_DSV: `upsample` keeps all 32 features
  * (:875) and nothing is carried beside a level; the previous state is warped at 8x FIRST and both versions are brought to 2x by
  * `downsample` (:1021-1026); `crfp_dense_*` (the reference's class CRFP) additionally feeds every residual block the warped previous state
  * as a third input (:1311,1316).  Parameters: CRFP_DSV_NUM_PARAMS device pointers under CRFP_DSV's state_dict keys, in its order
@@ -353,6 +363,9 @@ size_t crfp_cra_batch_workspace_bytes_bf16(int n, int t, int h, int w);
 size_t crfp_cra_batch_status_offset_bf16(int n, int t, int h, int w);
 int crfp_cra_forward_batch_bf16(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
                                 float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+int crfp_cra_stream_batch_bf16(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
+                               const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
+                               size_t workspace_bytes, void* stream);
 size_t crfp_simple_packed_weight_bytes_bf16(int y_only);
 int crfp_simple_pack_weights_bf16(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream);
 size_t crfp_simple_batch_workspace_bytes_bf16(int n, int t, int h, int w);

@@ -224,15 +224,17 @@ int main() {
             EXPECT(crfp_dsv_stream_batch(pk, 0, lrs, lrs, fvs, mks, nullptr, out, 0, 3, h, w, wsp, crfp_dsv_batch_workspace_bytes(3, 1, h, w), stream) == 0);
             EXPECT(crfp_dsv_stream_batch(pk, 0, lrs, lrs, fvs, mks, mks, out, 0, 3, h, w, wsp, crfp_dsv_batch_workspace_bytes(3, 1, h, w), stream) != 0);   // fg needs n = 1
             EXPECT(crfp_dsv_stream_batch(pk, 0, lrs, lrs, fvs, mks, nullptr, out, 0, 33, h, w, wsp, (size_t)1 << 44, stream) != 0);                          // n <= 32
-            // the streaming forms of the CRFP_simple / CRFP wirings (MRCF_simple_v13 / v15): the same calls on their own workspaces
-            decltype(&crfp_simple_stream_batch) abl[] = {crfp_simple_stream_batch, crfp_dense_stream_batch, crfp_simple_stream_batch_bf16, crfp_dense_stream_batch_bf16};
-            decltype(&crfp_simple_batch_workspace_bytes) abl_ws[] = {crfp_simple_batch_workspace_bytes, crfp_dense_batch_workspace_bytes,
-                                                                      crfp_simple_batch_workspace_bytes_bf16, crfp_dense_batch_workspace_bytes_bf16};
-            for (int k = 0; k < 4; ++k) {
+            // the streaming forms of the CRFP_simple / CRFP / CRFP_DSV_CRA wirings (MRCF_simple_v13 / v15 / v18_cra): the same calls on their own workspaces
+            decltype(&crfp_simple_stream_batch) abl[] = {crfp_simple_stream_batch, crfp_dense_stream_batch, crfp_cra_stream_batch,
+                                                         crfp_simple_stream_batch_bf16, crfp_dense_stream_batch_bf16, crfp_cra_stream_batch_bf16};
+            decltype(&crfp_simple_batch_workspace_bytes) abl_ws[] = {crfp_simple_batch_workspace_bytes, crfp_dense_batch_workspace_bytes, crfp_cra_batch_workspace_bytes,
+                                                                      crfp_simple_batch_workspace_bytes_bf16, crfp_dense_batch_workspace_bytes_bf16,
+                                                                      crfp_cra_batch_workspace_bytes_bf16};
+            for (int k = 0; k < 6; ++k) {
                 const auto sb = abl[k];
                 const size_t w1 = abl_ws[k](1, 1, h, w), w3 = abl_ws[k](3, 1, h, w);
                 EXPECT(sb(pk, 0, lrs, nullptr, fvs, mks, nullptr, out, 1, 1, h, w, wsp, w1, stream) == 0);                                // first frame
-                EXPECT(sb(pk, k < 2 ? CRFP_DSV_STRICT_F32 : 0, lrs, lrs, fvs, mks, nullptr, out, 0, 1, h, w, wsp, w1, stream) == 0);       // next frame
+                EXPECT(sb(pk, k < 3 ? CRFP_DSV_STRICT_F32 : 0, lrs, lrs, fvs, mks, nullptr, out, 0, 1, h, w, wsp, w1, stream) == 0);       // next frame
                 EXPECT(sb(pk, CRFP_DSV_SINGLE_STREAM, lrs, lrs, fvs, mks, mks, out, 0, 1, h, w, wsp, w1, stream) == 0);                   // fg: ignored
                 EXPECT(sb(pk, CRFP_DSV_INPUTS_RESIDENT, lrs, nullptr, fvs, mks, nullptr, out, 1, 1, h, w, wsp, w1, stream) == 0);         // resident
                 for (int j = 0; j < 3; ++j)
@@ -242,12 +244,12 @@ int main() {
                 EXPECT(sb(pk, CRFP_DSV_INPUTS_RESIDENT, lrs, nullptr, fvs, mks, mks, out, 1, 3, h, w, wsp, w3, stream) == 0);
                 EXPECT(sb(pk, CRFP_DSV_INPUTS_RESIDENT, lrs, nullptr, fvs, mks, nullptr, out, 0, 3, h, w, wsp, w3, stream) == 0);
                 EXPECT(sb(pk, 0, lrs, lrs, fvs, mks, nullptr, out, 0, 33, h, w, wsp, (size_t)1 << 44, stream) == CRFP_E_UNSUPPORTED);    // n <= 32
-                const size_t dsv_ws = k < 2 ? crfp_dsv_batch_workspace_bytes(1, 1, h, w) : crfp_dsv_batch_workspace_bytes_bf16(1, 1, h, w);
+                const size_t dsv_ws = k < 3 ? crfp_dsv_batch_workspace_bytes(1, 1, h, w) : crfp_dsv_batch_workspace_bytes_bf16(1, 1, h, w);
                 EXPECT(dsv_ws < w1 && sb(pk, 0, lrs, lrs, fvs, mks, nullptr, out, 0, 1, h, w, wsp, dsv_ws, stream) == CRFP_E_WORKSPACE);   // CRFP_DSV-sized
                 void* const fresh = dev + (7ull << 36) + ((size_t)(k * 8 + (h & 7)) << 30);   // a workspace no sequence started on
                 EXPECT(sb(pk, CRFP_DSV_INPUTS_RESIDENT, lrs, nullptr, fvs, mks, nullptr, out, 0, 1, h, w, fresh, w1, stream) == CRFP_E_BADARG);   // resident, no first call
                 EXPECT(sb(pk, 0, lrs, nullptr, fvs, mks, nullptr, out, 0, 1, h, w, wsp, w1, stream) == CRFP_E_BADARG);                   // no previous frame
-                if (k >= 2) EXPECT(sb(pk, CRFP_DSV_STRICT_F32, lrs, lrs, fvs, mks, nullptr, out, 0, 1, h, w, wsp, w1, stream) == CRFP_E_UNSUPPORTED);
+                if (k >= 3) EXPECT(sb(pk, CRFP_DSV_STRICT_F32, lrs, lrs, fvs, mks, nullptr, out, 0, 1, h, w, wsp, w1, stream) == CRFP_E_UNSUPPORTED);
             }
         }
         EXPECT(crfp_rt_forward_clip(pk, 0, lrs, fvs, out, 5, 135, 240, 96, 96, 720, 720, wsp, crfp_rt_workspace_bytes(5, 135, 240, 96, 96, 720, 720), stream) == 0);
