@@ -14,19 +14,16 @@
 //   * the i == 0 branch's zero tensors (:1637,1666) -> K-restricted weight packs (0*w == 0 exactly)
 //   * fovea blend + LeakyReLU (:1674-1675) and conv_last + bilinear base (:1678-1683) -> epilogues
 //   * everything the fovea select discards (:1543-1547 -> :1672-1675 away from the mask) -> mask-gated launches (Runner::mask_gate_enabled)
-#include "crfp_common.h"
+// The host machinery under the schedule -- packed items, pack loop, per-thread stream tables, ConvArgs binding -- is engine_host.h, shared
+// with the regional engine (engine_rt.hip); the conv table, the wirings, the Layout and the schedules are this file's own.
+#include "engine_host.h"
 
-#include <cstdlib>
 #include <algorithm>
-#include <cstring>
-#include <mutex>
 #include <string>
 #include <unordered_map>
-#include <vector>
 
 namespace CRFP_NS {
 
-struct ConvDef { const char* stem; int cout, cin; };
 // order == reference state_dict order (weight, bias per entry); checked against the imported
 // reference by tests/golden/make_golden.py through crfp_amd/synth.py
 constexpr int kNumDsvConvs = 59, kNumCraConvs = 72;
@@ -97,18 +94,7 @@ static int conv_cout(int ci, int y_only, int wiring = W_DSV) {
     return kConvs[ci].cout;
 }
 
-// ------------------------------------------------------------------ packed items
-enum ItemType { T_MFMA = 0, T_NARROW = 1, T_DCN8 = 2, T_RAW = 3 };
-struct Item {
-    int type = T_MFMA;
-    ConvArgs c;
-    NarrowArgs nw;
-    int w1 = -1, w2 = -1;
-    size_t off_w = 0, off_b = 0, n_w = 0, n_b = 0;  // float offsets / counts inside the packed buffer
-    size_t off_s = 0, n_s = 0;                       // split-bf16 weight image (T_MFMA only), in floats
-    const char* name = "";
-};
-
+// ------------------------------------------------------------------ packed items (Item: engine_host.h)
 enum ItemId {
     IT_F0 = 0,  // .. IT_F0+13 : FNet
     IT_ENC_LR0 = 14, IT_ENC_LR1, IT_UPS, IT_DOWN,
@@ -123,66 +109,6 @@ enum ItemId {
 enum { L_FUSE = 0, L_DB0, L_DB1, L_OM, L_DCNW, L_RB0, L_RB0F, L_RB1, L_RB2, L_OMF };
 static inline int it_lvl(int lvl, int which) { return IT_LVL0 + 10 * lvl + which; }
 
-struct SrcSpec { int kind, nch; };
-
-static ConvArgs make_mfma(int y_only, int wiring, int ci, int ci2, std::vector<SrcSpec> srcs, int store, int ps_r, int act,
-                          float post_scale, int cbase_override = -1) {
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    int kq = 0, cbase = 0;
-    a.nsrc = 0;
-    for (auto& s : srcs) {
-        ConvSrc& d = a.src[a.nsrc++];
-        d.kind = s.kind;
-        d.nch = s.nch;
-        d.nq = src_quads(s.kind, s.nch);
-        d.cbase = cbase;
-        if (s.kind != SRC_ZERO) cbase += s.nch;
-        kq += d.nq;
-    }
-    (void)cbase_override;
-    if (kq & 3) {  // K is consumed in chunks of 4 quads (16 channels) by the split-bf16 main loop
-        ConvSrc& d = a.src[a.nsrc++];
-        d.kind = SRC_ZERO;
-        d.nq = 4 - (kq & 3);
-        d.nch = d.nq;
-        d.cbase = cbase;
-        kq += d.nq;
-    }
-    a.kq = kq;
-    a.cin_total = conv_cin(ci, wiring);
-    a.cout = conv_cout(ci, y_only, wiring) + (ci2 >= 0 ? conv_cout(ci2, y_only, wiring) : 0);
-    a.store = store;
-    a.ps_r = ps_r;
-    a.act = act;
-    a.post_scale = post_scale;
-    a.ctiles = (conv_packed_rows(a.cout, store, ps_r) + 31) / 32;
-    return a;
-}
-
-static NarrowArgs make_narrow(int y_only, int wiring, int ci, int ci2, std::vector<SrcSpec> srcs, int act, int epi) {
-    NarrowArgs a;
-    memset(&a, 0, sizeof(a));
-    int kq = 0, cbase = 0;
-    for (auto& s : srcs) {
-        ConvSrc& d = a.src[a.nsrc++];
-        d.kind = s.kind;
-        d.nch = s.nch;
-        d.nq = src_quads(s.kind, s.nch);
-        d.cbase = cbase;
-        cbase += s.nch;
-        kq += d.nq;
-    }
-    a.kq = kq;
-    a.cin_total = conv_cin(ci, wiring);
-    a.cout = conv_cout(ci, y_only, wiring) + (ci2 >= 0 ? conv_cout(ci2, y_only, wiring) : 0);
-    a.act = act;
-    a.epi = epi;
-    a.y_only = y_only;
-    a.post_scale = 1.0f;
-    return a;
-}
-
 struct Model {
     Item items[IT_COUNT];
     size_t total_floats = 0;
@@ -193,27 +119,13 @@ struct Model {
     bool abl() const { return wiring >= W_SIMPLE; }     // CRFP_simple / CRFP: all 32 features travel through the levels, no carried ones
     bool dense() const { return wiring == W_DENSE; }
 
-    void add_mfma(int id, const char* name, int ci, int ci2, std::vector<SrcSpec> srcs, int store, int ps_r, int act,
-                  float post_scale = 1.0f) {
-        Item& it = items[id];
-        it.type = T_MFMA;
-        it.name = name;
-        it.w1 = ci;
-        it.w2 = ci2;
-        it.c = make_mfma(y_only, wiring, ci, ci2, srcs, store, ps_r, act, post_scale);
-        it.n_w = conv_packed_weight_floats(it.c);
-        it.n_b = (size_t)it.c.ctiles * 32;
-        it.n_s = conv_split_weight_bytes(it.c) / sizeof(float);
+    // cout of an item: of both convs of a paired one
+    int cout_of(int ci, int ci2) const { return conv_cout(ci, y_only, wiring) + (ci2 >= 0 ? conv_cout(ci2, y_only, wiring) : 0); }
+    void add_mfma(int id, const char* name, int ci, int ci2, const std::vector<SrcSpec>& srcs, int store, int ps_r, int act, float post_scale = 1.0f) {
+        CRFP_NS::add_mfma(items[id], name, ci, ci2, conv_cin(ci, wiring), cout_of(ci, ci2), srcs, store, ps_r, act, post_scale);
     }
-    void add_narrow(int id, const char* name, int ci, int ci2, std::vector<SrcSpec> srcs, int act, int epi) {
-        Item& it = items[id];
-        it.type = T_NARROW;
-        it.name = name;
-        it.w1 = ci;
-        it.w2 = ci2;
-        it.nw = make_narrow(y_only, wiring, ci, ci2, srcs, act, epi);
-        it.n_w = narrow_packed_weight_floats(it.nw);
-        it.n_b = 4;
+    void add_narrow(int id, const char* name, int ci, int ci2, const std::vector<SrcSpec>& srcs, int act, int epi) {
+        CRFP_NS::add_narrow(items[id], name, ci, ci2, conv_cin(ci, wiring), cout_of(ci, ci2), y_only, srcs, act, epi);
     }
 
     Model(int y_only_, bool use_s3_, int wiring_ = W_DSV) : y_only(y_only_), use_s3(use_s3_), cra(wiring_ == W_CRA), wiring(wiring_) {
@@ -303,18 +215,7 @@ struct Model {
             // conv_tttf_k(cat(level features (32), fovea level (16))) (:2533): the blend with the resampled mask is its own small pass
             for (int k = 0; k < 3; ++k) add_mfma(IT_C_T0 + k, "conv_mfma:cra.tttf_level", CI_C_T0 + k, -1, {{Q, 32}, {Q, 16}}, ST_Q4, 0, CRFP_ACT_NONE);
         }
-        size_t cur = 0;
-        for (int i = 0; i < IT_COUNT; ++i) {
-            Item& it = items[i];
-            if (it.w1 < 0) continue;
-            it.off_w = cur;
-            cur += (it.n_w + 63) / 64 * 64;
-            it.off_b = cur;
-            cur += (it.n_b + 63) / 64 * 64;
-            it.off_s = cur;
-            cur += (it.n_s + 63) / 64 * 64;
-        }
-        total_floats = cur;
+        total_floats = assign_offsets(items, IT_COUNT);
     }
 };
 
@@ -529,88 +430,45 @@ struct StreamCtx {
     bool kept = false;     // the previous call left its LR frame in the workspace
     bool chained = false;  // the previous call was a two-stream resident call: its side work waited for everything before it on the caller's stream
 };
-struct SideStream {
+// (the tables, their registry and the lease of a thread: StreamTables, engine_host.h)
+struct SideStream : EventPool {   // events are indexed: event(k) is the same event in every call
     hipStream_t s = nullptr;
-    std::vector<hipEvent_t> ev;
     std::unordered_map<const void*, StreamCtx> ctx;
-    bool ok = true;
-    hipEvent_t event(size_t i) {
-        while (ev.size() <= i) {
-            hipEvent_t e;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ok = false; return nullptr; }
-            ev.push_back(e);
-        }
-        return ev[i];
-    }
-    void destroy() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        ev.clear();
-        ctx.clear();
-        if (s) (void)hipStreamDestroy(s);
-        s = nullptr;
-        ok = true;
-    }
+    void forget() { ctx.clear(); }   // sequences of an exiting thread
+    void destroy() { ctx.clear(); EventPool::destroy(&s, 1); }
 };
-constexpr int kMaxDevices = 64;
-// One table per host thread, taken on first use from a process-wide registry: crfp_shutdown() walks ALL tables, so the streams and
-// events of worker threads that have exited are released as well (a thread_local destructor would have to call into the HIP
-// runtime while the process may already be tearing it down).  Round 5: a thread that exits hands its table back to a
-// free list -- its destructor makes NO HIP call, it only forgets the per-sequence notes -- and the next new thread reuses it with its
-// stream and events, so a thread-per-request host no longer grows the registry by one table (64 slots, a stream, an event pool) per
-// thread.  The registry itself is heap-allocated and never destroyed: worker threads may outlive the static destructors.
-struct SideTable { SideStream dev[kMaxDevices]; };
-struct SideRegistry { std::mutex mu; std::vector<SideTable*> all, idle; };
-static SideRegistry& side_registry() { static SideRegistry* r = new SideRegistry(); return *r; }
-struct SideLease {
-    SideTable* t = nullptr;
-    ~SideLease() {
-        if (!t) return;
-        for (int d = 0; d < kMaxDevices; ++d) t->dev[d].ctx.clear();   // sequences of the exiting thread: the next owner starts clean
-        SideRegistry& r = side_registry();
-        std::lock_guard<std::mutex> lk(r.mu);
-        r.idle.push_back(t);
-    }
-};
-static thread_local SideLease g_side_tl;
-static SideStream* side_table() {
-    if (!g_side_tl.t) {
-        SideRegistry& r = side_registry();
-        std::lock_guard<std::mutex> lk(r.mu);
-        if (!r.idle.empty()) { g_side_tl.t = r.idle.back(); r.idle.pop_back(); }
-        else { g_side_tl.t = new SideTable(); r.all.push_back(g_side_tl.t); }
-    }
-    return g_side_tl.t->dev;
-}
-static void destroy_all_side_streams() {   // caller: no crfp_dsv_* call in flight on any thread
-    SideRegistry& r = side_registry();
-    std::lock_guard<std::mutex> lk(r.mu);
-    for (SideTable* t : r.all)
-        for (int d = 0; d < kMaxDevices; ++d) t->dev[d].destroy();
-}
+typedef StreamTables<SideStream> SideTables;
 #ifndef CRFP_ACT_BF16
-extern "C" int crfp_debug_side_tables(void) {   // tests: how many per-thread tables the fp32 engine's registry holds
-    SideRegistry& r = side_registry();
-    std::lock_guard<std::mutex> lk(r.mu);
-    return (int)r.all.size();
-}
+extern "C" int crfp_debug_side_tables(void) { return SideTables::count(); }   // tests: how many per-thread tables the fp32 engine's registry holds
 #endif
-// streams and events belong to the device that was current when they were created; a device index outside the table
-// gets no side stream (the caller then runs the single-stream schedule) instead of aliasing another device's slot
-static SideStream* side_slot() {   // the calling thread's table entry for the current device; creates nothing
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-    return &side_table()[dev];
-}
+static SideStream* side_slot() { return SideTables::current(); }   // the calling thread's table entry for the current device; creates nothing
 static SideStream* side_stream() {
     SideStream* ss = side_slot();
     if (!ss) return nullptr;
     if (!ss->s && ss->ok && hipStreamCreateWithFlags(&ss->s, hipStreamNonBlocking) != hipSuccess) ss->ok = false;
     return ss->ok ? ss : nullptr;
 }
-static bool side_stream_enabled() {
-    static const bool on = !(getenv("CRFP_SIDE_STREAM") && atoi(getenv("CRFP_SIDE_STREAM")) == 0);   // read once
-    return on;
-}
+// Every exit of a two-stream call after its fork joins the side stream back into the caller's stream: the caller may free or reuse its
+// tensors and the workspace as soon as its stream has drained, also after an error.  ev: index of the join event; note: the sequence's
+// host note, which a failed call invalidates (may be null)
+struct SideJoin {
+    SideStream& ss;
+    hipStream_t main_s;
+    size_t ev;
+    const char* who;
+    StreamCtx* note;
+    bool forked = false;
+    void join() {
+        hipEvent_t ej = ss.event(ev);
+        if (forked && ej && hipEventRecord(ej, ss.s) == hipSuccess) (void)hipStreamWaitEvent(main_s, ej, 0);
+    }
+    int fail(const char* what) {
+        join();
+        if (note) note->kept = note->chained = false;
+        set_error("%s: %s failed", who, what);
+        return 1;
+    }
+};
 
 struct Runner {
     const Model& M;
@@ -626,7 +484,7 @@ struct Runner {
 
     // Status words: one per clip of the call.  Batch item n of a launch raises word ovf_off + (n + ovf_add) / ovf_div (ovf_word(),
     // crfp_common.h): the per-frame launches carry one item per clip (div 1); the clip-level stages set their own mapping (clip_stage).
-    int ovf_div = 1, ovf_add = 0, ovf_off = 0, ovf_skip0 = 0;
+    int ovf_div = 1, ovf_add = 0, ovf_off = 0;
     // null in strict mode: no kernel forms fp16 operands, the guard has nothing to watch (the words stay 0)
     unsigned* ovf() const {
         static const bool env_strict = precision_env_strict(0);
@@ -638,48 +496,24 @@ struct Runner {
     static const float* adv(const float* p, long long elems) { return adv(const_cast<float*>(p), elems); }
     Q4 q(size_t off, int nq, int H, int W) const { Q4 r; r.p = F(off); r.nq = nq; r.H = H; r.W = W; return r; }
 
-    struct SrcBind { const float* p; long long bs; int pad = 0; };
-    struct DstBind { float* p; long long bs; int q0, q1; int pad = 0; };
-
+    // the launch-time plan of item id: its tensors, weights and status word (bind_conv), the status-word mapping and the precision
+    ConvArgs plan(int id, int N, int H, int W, const std::vector<SrcBind>& srcs, const std::vector<DstBind>& dsts, int dstH = 0, int dstW = 0) const {
+        ConvArgs a = bind_conv(M.items[id], packed, N, H, W, srcs, dsts, ovf());
+        a.dstH = dstH; a.dstW = dstW;
+        a.ovf_div = ovf_div; a.ovf_add = ovf_add;
+        a.strict = strict;
+        return a;
+    }
     // s3: the output goes (only, when dsts is empty) to an SRC_S3 image
     void mfma(int id, int N, int H, int W, std::vector<SrcBind> srcs, std::vector<DstBind> dsts, int dstH = 0, int dstW = 0,
               const float* resid = nullptr, long long resid_bs = 0, const float* flow = nullptr, long long flow_bs = 0,
               float* s3 = nullptr, long long s3_bs = 0, int dst_f32 = 0, int src_bgroup = 0) {
         if (rc) return;
-        const Item& it = M.items[id];
-        ConvArgs a = it.c;
+        ConvArgs a = plan(id, N, H, W, srcs, dsts, dstH, dstW);
         a.src_bgroup = src_bgroup;
-        for (size_t i = 0; i < srcs.size(); ++i) { a.src[i].p = srcs[i].p; a.src[i].bstride = srcs[i].bs; a.src[i].pad = srcs[i].pad; }
-        a.ndst = (int)dsts.size();
-        for (size_t i = 0; i < dsts.size(); ++i) {
-            a.dst[i].p = dsts[i].p; a.dst[i].bstride = dsts[i].bs; a.dst[i].q0 = dsts[i].q0; a.dst[i].q1 = dsts[i].q1;
-            a.dst[i].pad = dsts[i].pad;
-        }
-        a.N = N; a.H = H; a.W = W; a.dstH = dstH; a.dstW = dstW;
         a.resid = resid; a.resid_bstride = resid_bs; a.flow = flow; a.flow_bstride = flow_bs;
         a.s3_dst = s3; a.s3_bstride = s3_bs; a.dst_f32 = dst_f32;
-        a.wpk = packed + it.off_w;
-        a.bpk = packed + it.off_b;
-        a.wsplit = packed + it.off_s;
-        a.ovf = ovf(); a.ovf_div = ovf_div; a.ovf_add = ovf_add; a.ovf_skip0 = ovf_skip0;
-        a.strict = strict;
-        rc = launch_conv_mfma(a, it.name, s);
-    }
-    // the launch-time plan of item id as mfma() builds it
-    ConvArgs plan(int id, int N, int H, int W, const std::vector<SrcBind>& srcs, const std::vector<DstBind>& dsts, int dstH, int dstW) const {
-        const Item& it = M.items[id];
-        ConvArgs a = it.c;
-        for (size_t i = 0; i < srcs.size(); ++i) { a.src[i].p = srcs[i].p; a.src[i].bstride = srcs[i].bs; a.src[i].pad = srcs[i].pad; }
-        a.ndst = (int)dsts.size();
-        for (size_t i = 0; i < dsts.size(); ++i) {
-            a.dst[i].p = dsts[i].p; a.dst[i].bstride = dsts[i].bs; a.dst[i].q0 = dsts[i].q0; a.dst[i].q1 = dsts[i].q1;
-            a.dst[i].pad = dsts[i].pad;
-        }
-        a.N = N; a.H = H; a.W = W; a.dstH = dstH; a.dstW = dstW;
-        a.wpk = packed + it.off_w; a.bpk = packed + it.off_b; a.wsplit = packed + it.off_s;
-        a.ovf = ovf(); a.ovf_div = ovf_div; a.ovf_add = ovf_add; a.ovf_skip0 = ovf_skip0;
-        a.strict = strict;
-        return a;
+        rc = launch_conv_mfma(a, M.items[id].name, s);
     }
     // two independent convs of the same shape as ONE launch where the build can (conv_mfma.hip, launch_conv_mfma_dual)
     void mfma_dual(int idA, std::vector<SrcBind> srcsA, std::vector<DstBind> dstsA, int idB, std::vector<SrcBind> srcsB, std::vector<DstBind> dstsB,
@@ -688,30 +522,14 @@ struct Runner {
         ConvArgs a = plan(idA, N, H, W, srcsA, dstsA, dstH, dstW), b = plan(idB, N, H, W, srcsB, dstsB, dstH, dstW);
         rc = launch_conv_mfma_dual(a, M.items[idA].name, b, M.items[idB].name, name_both, s);
     }
-    // fills the per-launch fields of a packed MFMA item's plan (what mfma() passes to launch_conv_mfma)
-    ConvArgs bind(int id, int N, int H, int W, const std::vector<SrcBind>& srcs, const std::vector<DstBind>& dsts, const float* resid = nullptr,
-                  long long resid_bs = 0) const {
-        const Item& it = M.items[id];
-        ConvArgs a = it.c;
-        for (size_t i = 0; i < srcs.size(); ++i) { a.src[i].p = srcs[i].p; a.src[i].bstride = srcs[i].bs; a.src[i].pad = srcs[i].pad; }
-        a.ndst = (int)dsts.size();
-        for (size_t i = 0; i < dsts.size(); ++i) {
-            a.dst[i].p = dsts[i].p; a.dst[i].bstride = dsts[i].bs; a.dst[i].q0 = dsts[i].q0; a.dst[i].q1 = dsts[i].q1;
-            a.dst[i].pad = dsts[i].pad;
-        }
-        a.N = N; a.H = H; a.W = W;
-        a.resid = resid; a.resid_bstride = resid_bs;
-        a.wpk = packed + it.off_w; a.bpk = packed + it.off_b; a.wsplit = packed + it.off_s;
-        a.ovf = ovf(); a.ovf_div = ovf_div; a.ovf_add = ovf_add;
-        a.strict = strict;
-        return a;
-    }
 #ifdef CRFP_ACT_BF16
     // conv idA -> conv idB in one launch (conv3x3_bf16_pair_kernel): idA's output has no other reader and is never written
     void mfma_pair(int idA, int idB, const char* name, int N, int H, int W, std::vector<SrcBind> srcsA, std::vector<DstBind> dstsB,
                    const float* residB = nullptr, long long residB_bs = 0) {
         if (rc) return;
-        const ConvArgs a = bind(idA, N, H, W, srcsA, {}), b = bind(idB, N, H, W, {{nullptr, 0}}, dstsB, residB, residB_bs);
+        const ConvArgs a = plan(idA, N, H, W, srcsA, {});
+        ConvArgs b = plan(idB, N, H, W, {{nullptr, 0}}, dstsB);
+        b.resid = residB; b.resid_bstride = residB_bs;
         rc = launch_conv_pair(a, b, name, s);
     }
 #endif
@@ -822,7 +640,6 @@ struct Runner {
 #else
     static constexpr bool state_from_epilogue() { return CRFP_STATE_FROM_EPILOGUE != 0; }
 #endif
-#define RUN(expr) do { if (!rc) rc = (expr); } while (0)
 
     // The fovea blend is a select under the mask (model/CRFP.py:1543-1544,1674-1675): what is computed only to be deselected -- the x8
     // frame stack, encoder_hr and conv_tttf away from the fovea -- is skipped tile by tile, same output bits.  CRFP_MASK_GATE=0: dense launches
@@ -874,7 +691,7 @@ struct Runner {
             const int ks = (strict || env_strict || rc) ? 1 : conv_auto_ksplit(in.H, in.W, it.c.ctiles, it.c.kq);
             if (ks < 2) { mfma_q(IT_F0 + i, nb, in, out); return 1; }
             const long long pb = out.bs();   // floats of one (pair, slice): the layer's quads
-            ConvArgs a = plan(IT_F0 + i, nb, in.H, in.W, {{in.p, in.bs()}}, {{F(L.fpart), pb, 0, out.nq}}, 0, 0);
+            ConvArgs a = plan(IT_F0 + i, nb, in.H, in.W, {{in.p, in.bs()}}, {{F(L.fpart), pb, 0, out.nq}});
             a.ksplit = ks;
             ki.part = F(L.fpart); ki.pb = pb; ki.ks = ks; ki.act = it.c.act;
             ki.ovf = ovf(); ki.ovf_div = ovf_div; ki.ovf_add = ovf_add;
@@ -938,7 +755,7 @@ struct Runner {
     void clip_stage(const float* lq, int i0, int i1, int parts) {
         const long long lqf = lr_frame_floats(), lr_f = 3LL * L.h * L.w, fq = (long long)L.h * L.w * 4;
         const int t = L.t, B = L.B;
-        struct Restore { Runner& r; int d, a, o; ~Restore() { r.ovf_div = d; r.ovf_add = a; r.ovf_off = o; r.ovf_skip0 = 0; } } restore{*this, ovf_div, ovf_add, ovf_off};
+        struct Restore { Runner& r; int d, a, o; ~Restore() { r.ovf_div = d; r.ovf_add = a; r.ovf_off = o; } } restore{*this, ovf_div, ovf_add, ovf_off};
         if (L.flat) {   // i0 == 0, i1 == t: one pass over the B * t frames / the B * (t - 1) frame pairs of the clips
             ovf_div = t;           // item n of encoder_lr's launches is frame n of the flattened sequence
             ovf_add = 0;
@@ -1229,146 +1046,51 @@ __global__ void round_bf16_copy_kernel(const float* __restrict__ src, float* __r
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = (float)(__bf16)src[i];
 }
-namespace crfp_bf16 { void shutdown_side_streams() { destroy_all_side_streams(); } }
+namespace crfp_bf16 {
+void shutdown_side_streams() { SideTables::destroy_all(); }
+int round_bf16_copy(const float* src, float* dst, int n, hipStream_t s) {
+    round_bf16_copy_kernel<<<(n + 255) / 256, 256, 0, s>>>(src, dst, n);
+    return hipGetLastError() != hipSuccess ? 1 : 0;
+}
+}  // namespace crfp_bf16
 #else
 namespace crfp_bf16 { void shutdown_side_streams(); }
 namespace crfp { void rt_shutdown_streams(); }   // engine_rt.hip
 #endif
 
-extern "C" {
-
-#ifndef CRFP_ACT_BF16
-const char* crfp_dsv_param_name(int index) {
-    static thread_local std::string s;
-    if (index < 0 || index >= CRFP_DSV_NUM_PARAMS) return nullptr;
-    s = std::string(kConvs[index / 2].stem) + (index % 2 ? ".bias" : ".weight");
+// ------------------------------------------------------------------ parameter tables
+// A wiring's parameters are its reference model's state_dict, (weight, bias) per conv.  CRFP_simple / CRFP: the keys and their order are
+// CRFP_DSV's (crfp_dsv_param_name), four weights have other shapes; CRFP_DSV_CRA: its own order (kCraOrder).
+static int num_params(int wiring) { return wiring == W_CRA ? CRFP_CRA_NUM_PARAMS : CRFP_DSV_NUM_PARAMS; }
+static int param_conv(int wiring, int index) { return wiring == W_CRA ? kCraOrder[index / 2] : index / 2; }   // index into kConvs
+static const char* param_name(int wiring, int index, std::string& s) {
+    if (index < 0 || index >= num_params(wiring)) return nullptr;
+    s = std::string(kConvs[param_conv(wiring, index)].stem) + (index % 2 ? ".bias" : ".weight");
     return s.c_str();
 }
-
-int crfp_dsv_param_numel(int index, int y_only) {
-    if (index < 0 || index >= CRFP_DSV_NUM_PARAMS) return CRFP_E_BADARG;
-    const int ci = index / 2, co = conv_cout(ci, y_only);
-    return index % 2 ? co : co * kConvs[ci].cin * 9;
-}
-
-const char* crfp_cra_param_name(int index) {
-    static thread_local std::string s;
-    if (index < 0 || index >= CRFP_CRA_NUM_PARAMS) return nullptr;
-    s = std::string(kConvs[kCraOrder[index / 2]].stem) + (index % 2 ? ".bias" : ".weight");
-    return s.c_str();
-}
-
-int crfp_cra_param_numel(int index, int y_only) {
-    if (index < 0 || index >= CRFP_CRA_NUM_PARAMS) return CRFP_E_BADARG;
-    const int ci = kCraOrder[index / 2], co = conv_cout(ci, y_only);
-    return index % 2 ? co : co * kConvs[ci].cin * 9;
-}
-
-// CRFP_simple / CRFP: the state_dict keys and their order are CRFP_DSV's (crfp_dsv_param_name); four weights have other shapes
-static int abl_param_numel(int wiring, int index, int y_only) {
-    if (index < 0 || index >= CRFP_DSV_NUM_PARAMS) return CRFP_E_BADARG;
-    const int ci = index / 2, co = conv_cout(ci, y_only, wiring);
+static int param_numel(int wiring, int index, int y_only) {
+    if (index < 0 || index >= num_params(wiring)) return CRFP_E_BADARG;
+    const int ci = param_conv(wiring, index), co = conv_cout(ci, y_only, wiring);
     return index % 2 ? co : co * conv_cin(ci, wiring) * 9;
 }
-int crfp_simple_param_numel(int index, int y_only) { return abl_param_numel(W_SIMPLE, index, y_only); }
-int crfp_dense_param_numel(int index, int y_only) { return abl_param_numel(W_DENSE, index, y_only); }
 
-#endif  // parameter tables: exported once
-
-}  // extern "C"
-
-// params: 2 * kNumCraConvs pointers in kConvs order (the CRFP_DSV wiring reads the first 2 * kNumDsvConvs)
-static int pack_weights_impl(const Model& M, const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
-    if (packed_bytes < M.total_floats * sizeof(float)) { set_error("pack_weights: packed buffer too small"); return CRFP_E_WORKSPACE; }
-    hipStream_t s = (hipStream_t)stream;
-    float* pk = (float*)packed;
-    for (int i = 0; i < IT_COUNT; ++i) {
-        const Item& it = M.items[i];
-        if (it.w1 < 0) continue;
-        const float* w = params[2 * it.w1];
-        const float* b = params[2 * it.w1 + 1];
-        const float* w2 = it.w2 >= 0 ? params[2 * it.w2] : nullptr;
-        const float* b2 = it.w2 >= 0 ? params[2 * it.w2 + 1] : nullptr;
-        const int split = conv_cout(it.w1, y_only, M.wiring);
-        int rc = 0;
-        switch (it.type) {
-            case T_MFMA:
-                rc = launch_conv_pack(it.c, w, b, w2, b2, split, pk + it.off_w, pk + it.off_b, s);
-                if (!rc) rc = launch_conv_pack_split(it.c, w, w2, split, pk + it.off_s, s);
-                break;
-            case T_NARROW: rc = launch_narrow_pack(it.nw, w, b, w2, b2, split, pk + it.off_w, pk + it.off_b, s); break;
-            case T_DCN8:
-                if (!kActBf16) rc = launch_dcn_g8_pack(w, pk + it.off_w, s, false);   // fp32 MFMA image (strict mode, fp32 build)
-                if (!rc) rc = launch_dcn_g8_pack(w, pk + it.off_w + 36 * 2 * 32 * 4, s, true);
-                if (!rc && hipMemcpyAsync(pk + it.off_b, b, 32 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = 1;
-                break;
-            default:
-#ifdef CRFP_ACT_BF16
-                round_bf16_copy_kernel<<<((int)it.n_w + 255) / 256, 256, 0, s>>>(w, pk + it.off_w, (int)it.n_w);
-                if (hipGetLastError() != hipSuccess) rc = 1;
-#else
-                if (hipMemcpyAsync(pk + it.off_w, w, it.n_w * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = 1;
-#endif
-                if (!rc && hipMemcpyAsync(pk + it.off_b, b, it.n_b * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = 1;
+// params: num_params(wiring) device pointers in the order of the wiring's parameter table
+static int pack_weights_impl(int wiring, const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
+    if (!params || !packed) { set_error("pack_weights: null argument"); return CRFP_E_BADARG; }
+    const float* eng[2 * kNumCraConvs];   // in kConvs order
+    for (int i = 0; i < num_params(wiring); ++i) {
+        if (!params[i]) {
+            set_error("pack_weights: parameter %d (%s) is null", i, wiring == W_CRA ? crfp_cra_param_name(i) : crfp_dsv_param_name(i));
+            return CRFP_E_BADARG;
         }
-        if (rc) return rc;
+        eng[2 * param_conv(wiring, i) + i % 2] = params[i];
     }
-    return 0;
-}
-
-extern "C" {
-
-size_t CRFP_API(crfp_dsv_packed_weight_bytes)(int y_only) { return model_for(y_only).total_floats * sizeof(float); }
-size_t CRFP_API(crfp_cra_packed_weight_bytes)(int y_only) { return model_for(y_only, false, W_CRA).total_floats * sizeof(float); }
-size_t CRFP_API(crfp_simple_packed_weight_bytes)(int y_only) { return model_for(y_only, false, W_SIMPLE).total_floats * sizeof(float); }
-size_t CRFP_API(crfp_dense_packed_weight_bytes)(int y_only) { return model_for(y_only, false, W_DENSE).total_floats * sizeof(float); }
-
-int CRFP_API(crfp_dsv_pack_weights)(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
-    if (!params || !packed) { set_error("pack_weights: null argument"); return CRFP_E_BADARG; }
-    for (int i = 0; i < CRFP_DSV_NUM_PARAMS; ++i)
-        if (!params[i]) { set_error("pack_weights: parameter %d (%s) is null", i, crfp_dsv_param_name(i)); return CRFP_E_BADARG; }
-    return pack_weights_impl(model_for(y_only), params, y_only, packed, packed_bytes, stream);
-}
-
-// params: CRFP_CRA_NUM_PARAMS device pointers in the order of the reference's CRFP_DSV_CRA state_dict (crfp_cra_param_name)
-int CRFP_API(crfp_cra_pack_weights)(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
-    if (!params || !packed) { set_error("pack_weights: null argument"); return CRFP_E_BADARG; }
-    const float* eng[2 * kNumCraConvs];
-    for (int j = 0; j < kNumCraConvs; ++j)
-        for (int k = 0; k < 2; ++k) {
-            if (!params[2 * j + k]) { set_error("pack_weights: parameter %d (%s) is null", 2 * j + k, crfp_cra_param_name(2 * j + k)); return CRFP_E_BADARG; }
-            eng[2 * kCraOrder[j] + k] = params[2 * j + k];
-        }
-    return pack_weights_impl(model_for(y_only, false, W_CRA), eng, y_only, packed, packed_bytes, stream);
-}
-
-// params: CRFP_DSV_NUM_PARAMS device pointers in the order of the reference's CRFP_simple / CRFP state_dict (= crfp_dsv_param_name)
-static int abl_pack_weights(int wiring, const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
-    if (!params || !packed) { set_error("pack_weights: null argument"); return CRFP_E_BADARG; }
-    for (int i = 0; i < CRFP_DSV_NUM_PARAMS; ++i)
-        if (!params[i]) { set_error("pack_weights: parameter %d (%s) is null", i, crfp_dsv_param_name(i)); return CRFP_E_BADARG; }
-    return pack_weights_impl(model_for(y_only, false, wiring), params, y_only, packed, packed_bytes, stream);
-}
-int CRFP_API(crfp_simple_pack_weights)(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
-    return abl_pack_weights(W_SIMPLE, params, y_only, packed, packed_bytes, stream);
-}
-int CRFP_API(crfp_dense_pack_weights)(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
-    return abl_pack_weights(W_DENSE, params, y_only, packed, packed_bytes, stream);
+    const Model& M = model_for(y_only, false, wiring);
+    if (int rc = check_packed_size("pack_weights", M.total_floats, packed_bytes)) return rc;
+    return pack_items(M.items, IT_COUNT, eng, [&](int ci) { return conv_cout(ci, y_only, wiring); }, (float*)packed, (hipStream_t)stream);
 }
 
 static bool dims_ok(int n, int t, int h, int w) { return n >= 1 && t >= 1 && h >= 8 && w >= 8 && (long long)n * t <= (1 << 20); }
-
-size_t CRFP_API(crfp_dsv_batch_workspace_bytes)(int n, int t, int h, int w) {
-    if (!dims_ok(n, t, h, w)) return 0;
-    return Layout(n, t, h, w).bytes();
-}
-size_t CRFP_API(crfp_dsv_workspace_bytes)(int t, int h, int w) { return CRFP_API(crfp_dsv_batch_workspace_bytes)(1, t, h, w); }
-size_t CRFP_API(crfp_cra_batch_workspace_bytes)(int n, int t, int h, int w) {
-    if (!dims_ok(n, t, h, w)) return 0;
-    return Layout(n, t, h, w, W_CRA).bytes();
-}
-size_t CRFP_API(crfp_simple_batch_workspace_bytes)(int n, int t, int h, int w) { return dims_ok(n, t, h, w) ? Layout(n, t, h, w, W_SIMPLE).bytes() : 0; }
-size_t CRFP_API(crfp_dense_batch_workspace_bytes)(int n, int t, int h, int w) { return dims_ok(n, t, h, w) ? Layout(n, t, h, w, W_DENSE).bytes() : 0; }
 
 static int check_common(const void* packed, int n, int t, int h, int w, void* ws, size_t ws_bytes, const Layout& L) {
     if (!packed || !ws) { set_error("dsv: null packed weights or workspace"); return CRFP_E_BADARG; }
@@ -1376,20 +1098,6 @@ static int check_common(const void* packed, int n, int t, int h, int w, void* ws
     if (ws_bytes < L.bytes()) { set_error("dsv: workspace %zu < required %zu bytes", ws_bytes, L.bytes()); return CRFP_E_WORKSPACE; }
     return 0;
 }
-
-size_t CRFP_API(crfp_dsv_batch_status_offset)(int n, int t, int h, int w) {
-    if (!dims_ok(n, t, h, w)) return 0;
-    return Layout(n, t, h, w).status;
-}
-size_t CRFP_API(crfp_dsv_status_offset)(int t, int h, int w) { return CRFP_API(crfp_dsv_batch_status_offset)(1, t, h, w); }
-size_t CRFP_API(crfp_cra_batch_status_offset)(int n, int t, int h, int w) {
-    if (!dims_ok(n, t, h, w)) return 0;
-    return Layout(n, t, h, w, W_CRA).status;
-}
-size_t CRFP_API(crfp_simple_batch_status_offset)(int n, int t, int h, int w) { return dims_ok(n, t, h, w) ? (size_t)Layout(n, t, h, w, W_SIMPLE).status : 0; }
-size_t CRFP_API(crfp_dense_batch_status_offset)(int n, int t, int h, int w) { return dims_ok(n, t, h, w) ? (size_t)Layout(n, t, h, w, W_DENSE).status : 0; }
-
-}  // extern "C"
 
 // n clips in lock-step through the recurrent chain (reference model/CRFP.py:1510-1535: every op of forward() carries the batch
 // axis n): ONE launch per layer and frame step over all n clips, so a 360 x 640 map that is a single round of workgroups for one
@@ -1427,28 +1135,21 @@ static int forward_batch_impl(int wiring, const void* packed, int flags, const f
     // two-stream schedule: the side stream runs FNet and the state-independent part of every frame up to two
     // frames ahead of the recurrent chain on the caller's stream
     SideStream& ss = *ssp;
-    bool forked = false;
-    // every exit after the fork joins the side stream back into the caller's stream: the caller may free or reuse
-    // lrs / fvs / mks / workspace as soon as its stream has drained, also after an error
-    auto join = [&]() {
-        hipEvent_t ej = ss.event(0);
-        if (forked && ej && hipEventRecord(ej, ss.s) == hipSuccess) (void)hipStreamWaitEvent(main_s, ej, 0);
-    };
-    auto fail = [&](const char* what) { join(); set_error("dsv_forward_clip: %s failed", what); return 1; };
+    SideJoin J{ss, main_s, 0, "dsv_forward_clip", nullptr};
     hipEvent_t ev_start = ss.event(0), ev_xlr = ss.event(1);
-    if (!ss.ok) return fail("hipEventCreate");
+    if (!ss.ok) return J.fail("hipEventCreate");
     // the status word and the recurrent state are cleared BEFORE the fork: the side stream's first kernel (frame 0's fovea
     // blend) may raise the overflow bit, and a memset racing with it on the other stream could wipe that
     R.reset_state();
     const float* lq = R.lr_to_q4(lrs, n * t, 0, t);   // before the fork: FNet on the side stream reads it as well
     if (R.rc) return R.rc;
-    if (hipEventRecord(ev_start, main_s) != hipSuccess || hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return fail("fork");
-    forked = true;
+    if (hipEventRecord(ev_start, main_s) != hipSuccess || hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return J.fail("fork");
+    J.forked = true;
     R.clip_stage(lq, 0, TC < t ? TC : t, 1);   // encoder_lr of the first chunk (flat: of every frame) on the caller's stream, beside frame 0's fovea blend
-    if (hipEventRecord(ev_xlr, main_s) != hipSuccess) return fail("record");
+    if (hipEventRecord(ev_xlr, main_s) != hipSuccess) return J.fail("record");
     for (int i = 0; i < t && !R.rc; ++i) {
         hipEvent_t pre_done = ss.event(2 + 2 * i), main_done = ss.event(3 + 2 * i);
-        if (!ss.ok) return fail("hipEventCreate");
+        if (!ss.ok) return J.fail("hipEventCreate");
         // side: pre-work of frame i into set i&1 (free once the recurrent part of frame i-2 is done)
         R.s = ss.s;
         // FNet (all pairs, 0.7 ms) goes BEHIND frame 0's pre-work: frame 0 needs no flow, and with FNet first the caller's
@@ -1458,53 +1159,19 @@ static int forward_batch_impl(int wiring, const void* packed, int flags, const f
         // later chunks of a long clip: both clip-level stages on the side stream, in front of the chunk's first frame (the stores'
         // previous contents were last read by this stream's own earlier pre-work)
         if (i > 0 && i % TC == 0) R.clip_stage(lq, i, i + TC < t ? i + TC : t, 3);
-        if (i >= 2 && hipStreamWaitEvent(ss.s, ss.event(3 + 2 * (i - 2)), 0) != hipSuccess) return fail("wait");
+        if (i >= 2 && hipStreamWaitEvent(ss.s, ss.event(3 + 2 * (i - 2)), 0) != hipSuccess) return J.fail("wait");
         const Runner::FrameIO io = R.frame_io(i, lrs, fvs, mks, out, y_only);
         R.frame_pre(i & 1, i == 0, io, i == 0 ? ev_xlr : nullptr);
-        if (hipEventRecord(pre_done, ss.s) != hipSuccess) return fail("record");
+        if (hipEventRecord(pre_done, ss.s) != hipSuccess) return J.fail("record");
         // main: recurrent part of frame i
         R.s = main_s;
-        if (hipStreamWaitEvent(main_s, pre_done, 0) != hipSuccess) return fail("wait");
+        if (hipStreamWaitEvent(main_s, pre_done, 0) != hipSuccess) return J.fail("wait");
         R.frame(i & 1, i == 0, io);
-        if (hipEventRecord(main_done, main_s) != hipSuccess) return fail("record");
+        if (hipEventRecord(main_done, main_s) != hipSuccess) return J.fail("record");
     }
-    if (R.rc) join();   // a launch failed mid-clip: the last pre_done wait may not have been enqueued
+    if (R.rc) J.join();   // a launch failed mid-clip: the last pre_done wait may not have been enqueued
     return R.rc;
 }
-
-extern "C" {
-
-int CRFP_API(crfp_dsv_forward_batch)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
-                           float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_batch_impl(W_DSV, packed, flags, lrs, fvs, mks, out, n, t, h, w, workspace, workspace_bytes, stream);
-}
-
-// The same call for the reference's CRFP_DSV_CRA wiring (model/CRFP.py:2314-2664): packed = crfp_cra_pack_weights' buffer, workspace sized by
-// crfp_cra_batch_workspace_bytes.  Schedule, status words and flags as crfp_dsv_forward_batch; the four-level fovea encoder is
-// state-independent and runs with the rest of a frame's pre-work on the side stream.
-int CRFP_API(crfp_cra_forward_batch)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
-                           float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_batch_impl(W_CRA, packed, flags, lrs, fvs, mks, out, n, t, h, w, workspace, workspace_bytes, stream);
-}
-
-// The same call for the reference's ablation wirings CRFP_simple (model/CRFP.py:816-1099) and CRFP (:1101-1385) at mid_channels = 32 with
-// hr_dcn and offset_prop on: packed = crfp_simple_pack_weights' / crfp_dense_pack_weights' buffer, workspace sized by the wiring's own query.
-// Schedule, flags and status words as crfp_dsv_forward_batch.
-int CRFP_API(crfp_simple_forward_batch)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
-                           float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_batch_impl(W_SIMPLE, packed, flags, lrs, fvs, mks, out, n, t, h, w, workspace, workspace_bytes, stream);
-}
-int CRFP_API(crfp_dense_forward_batch)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
-                           float* out, int n, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_batch_impl(W_DENSE, packed, flags, lrs, fvs, mks, out, n, t, h, w, workspace, workspace_bytes, stream);
-}
-
-int CRFP_API(crfp_dsv_forward_clip)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
-                          float* out, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-    return CRFP_API(crfp_dsv_forward_batch)(packed, flags, lrs, fvs, mks, out, 1, t, h, w, workspace, workspace_bytes, stream);
-}
-
-}  // extern "C"
 
 // One frame of n independent sequences in lock-step (the reference's streaming forward carries the batch axis too, model/CRFP_test.py:2250-2451):
 // lr / lr_prev [n,3,h,w], fv [n,3,8h,8w], mk [n,1,8h,8w], out [n,3|1,8h,8w]; the workspace holds the n recurrent states.
@@ -1594,32 +1261,27 @@ static int stream_batch_impl(int wiring, const void* packed, int flags, const fl
             return R.rc;
         }
         SideStream& ss = *ssp;
-        bool forked = false;
-        auto join = [&]() {
-            hipEvent_t ej = ss.event(1);
-            if (forked && ej && hipEventRecord(ej, ss.s) == hipSuccess) (void)hipStreamWaitEvent(main_s, ej, 0);
-        };
-        auto fail = [&](const char* what) { join(); ctx->kept = ctx->chained = false; set_error("dsv_stream_batch: %s failed", what); return 1; };
-        hipEvent_t ev_start = ss.event(0), ev_side = ss.event(1);
-        if (!ss.ok) return fail("hipEventCreate");
-        if (hipEventRecord(ev_start, main_s) != hipSuccess) return fail("record");
+        SideJoin J{ss, main_s, 1, "dsv_stream_batch", ctx};
+            hipEvent_t ev_start = ss.event(0), ev_side = ss.event(1);
+        if (!ss.ok) return J.fail("hipEventCreate");
+        if (hipEventRecord(ev_start, main_s) != hipSuccess) return J.fail("record");
         // Early start is safe only behind a call whose side work waited for ITS fork event: set par (W_CRA: its three fovea levels too) was
         // last read by frame i - 2 on the caller's stream, which that wait ordered in front of everything the side stream did since.
         const bool early = ctx->chained;
         R.s = ss.s;
-        forked = true;
-        if (!early && hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return fail("fork");
+        J.forked = true;
+        if (!early && hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return J.fail("fork");
         keep_and_get(&cur, &prev);
         R.fnet(B, cur, lr_f, prev, lr_f, R.flow_lr_slot());
         R.encode_lr(B, cur, lr_f);
         io.flow_lr = R.flow_lr_slot();
         R.frame_pre(par, false, io, nullptr, 3);   // incl. the two flow up-samplings (set par as well)
-        if (early && hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return fail("fork");
+        if (early && hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return J.fail("fork");
         R.downsample_state();   // needs the state frame i - 1 wrote
         R.down_done = true;
-        if (hipEventRecord(ev_side, ss.s) != hipSuccess) return fail("record");
+        if (hipEventRecord(ev_side, ss.s) != hipSuccess) return J.fail("record");
         R.s = main_s;
-        if (hipStreamWaitEvent(main_s, ev_side, 0) != hipSuccess) return fail("join");
+        if (hipStreamWaitEvent(main_s, ev_side, 0) != hipSuccess) return J.fail("join");
         R.frame(par, false, io, fg);
         ctx->kept = ctx->chained = R.rc == 0;
         return R.rc;
@@ -1639,67 +1301,85 @@ static int stream_batch_impl(int wiring, const void* packed, int flags, const fl
     // caller's stream; encoder_lr, the fovea blend, encoder_hr and the upsample conv run beside them on the side stream.
     // The caller's kernels are enqueued first (enqueue order across streams matters).
     SideStream& ss = *ssp;
-    bool forked = false;
-    auto join = [&]() {
-        hipEvent_t ej = ss.event(1);
-        if (forked && ej && hipEventRecord(ej, ss.s) == hipSuccess) (void)hipStreamWaitEvent(main_s, ej, 0);
-    };
-    auto fail = [&](const char* what) { join(); set_error("dsv_stream_batch: %s failed", what); return 1; };
+    SideJoin J{ss, main_s, 1, "dsv_stream_batch", nullptr};
     hipEvent_t ev_start = ss.event(0), ev_side = ss.event(1);
-    if (!ss.ok) return fail("hipEventCreate");
+    if (!ss.ok) return J.fail("hipEventCreate");
     const float* lq = R.lr_to_q4(lr, B, 0, 1);   // before the fork: read on both streams
     const float* lqp = R.lr_to_q4(lr_prev, B, B, 1);
-    if (hipEventRecord(ev_start, main_s) != hipSuccess) return fail("record");
+    if (hipEventRecord(ev_start, main_s) != hipSuccess) return J.fail("record");
     R.fnet(B, lq, lr_f, lqp, lr_f, R.F(L.flow_lr));
     io.flow_lr = R.F(L.flow_lr);
     R.frame_pre(0, false, io, nullptr, 2);
     R.s = ss.s;
-    if (hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return fail("fork");
-    forked = true;
+    if (hipStreamWaitEvent(ss.s, ev_start, 0) != hipSuccess) return J.fail("fork");
+    J.forked = true;
     R.encode_lr(B, lq, lr_f);
     R.frame_pre(0, false, io, nullptr, 1);
     // downsample(state) needs nothing of this call: it runs here, beside FNet's small kernels, instead of in front of the recurrent chain
     // (same box, 24 calls: bf16 27.74 -> 27.40 ms, fp32 45.81 -> 45.23 ms, same bits; profiles/r03_stream_down_side_ab.txt)
     R.downsample_state();
     R.down_done = true;
-    if (hipEventRecord(ev_side, ss.s) != hipSuccess) return fail("record");
+    if (hipEventRecord(ev_side, ss.s) != hipSuccess) return J.fail("record");
     R.s = main_s;
-    if (hipStreamWaitEvent(main_s, ev_side, 0) != hipSuccess) return fail("join");
+    if (hipStreamWaitEvent(main_s, ev_side, 0) != hipSuccess) return J.fail("join");
     R.frame(0, false, io, fg);
     return R.rc;
 }
 
+// ------------------------------------------------------------------ the C ABI of a wiring
+// One set of entry points per wiring, all over the same implementations: crfp_<x>_packed_weight_bytes / _pack_weights (params: the wiring's
+// parameter table, crfp_<x>_param_name / _param_numel), _batch_workspace_bytes / _batch_status_offset, _forward_batch and _stream_batch.
+//   dsv:    CRFP_DSV; streaming: MRCF_simple_v18, the only wiring that reads the regional mask `fg`
+//   cra:    the reference's CRFP_DSV_CRA wiring (model/CRFP.py:2314-2664; streaming: MRCF_simple_v18_cra): packed = crfp_cra_pack_weights' buffer,
+//           params in the order of ITS state_dict (crfp_cra_param_name); the four-level fovea encoder is state-independent and runs with the rest
+//           of a frame's pre-work on the side stream
+//   simple, dense: the reference's ablation wirings CRFP_simple (model/CRFP.py:816-1099) and CRFP (:1101-1385) at mid_channels = 32 with hr_dcn and
+//           offset_prop on (streaming: MRCF_simple_v13 / v15); parameter names are CRFP_DSV's (crfp_dsv_param_name)
+// Every wiring's workspace is sized by its own query; schedule, flags, n <= 32 streamed sequences and status words are crfp_dsv_*'s; `fg` is
+// accepted and ignored by every wiring but dsv, for any n.
+#ifndef CRFP_ACT_BF16   // parameter tables: exported once
+#define CRFP_PARAM_NAME_EXPORT(X, WIRING) \
+    const char* crfp_##X##_param_name(int index) { static thread_local std::string s; return param_name(WIRING, index, s); }
+#define CRFP_PARAM_NUMEL_EXPORT(X, WIRING) \
+    int crfp_##X##_param_numel(int index, int y_only) { return param_numel(WIRING, index, y_only); }
+#else
+#define CRFP_PARAM_NAME_EXPORT(X, WIRING)
+#define CRFP_PARAM_NUMEL_EXPORT(X, WIRING)
+#endif
+#define CRFP_WIRING_EXPORTS(X, WIRING) \
+    CRFP_PARAM_NUMEL_EXPORT(X, WIRING) \
+    size_t CRFP_API(crfp_##X##_packed_weight_bytes)(int y_only) { return model_for(y_only, false, WIRING).total_floats * sizeof(float); } \
+    int CRFP_API(crfp_##X##_pack_weights)(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) { \
+        return pack_weights_impl(WIRING, params, y_only, packed, packed_bytes, stream); \
+    } \
+    size_t CRFP_API(crfp_##X##_batch_workspace_bytes)(int n, int t, int h, int w) { return dims_ok(n, t, h, w) ? Layout(n, t, h, w, WIRING).bytes() : 0; } \
+    size_t CRFP_API(crfp_##X##_batch_status_offset)(int n, int t, int h, int w) { return dims_ok(n, t, h, w) ? (size_t)Layout(n, t, h, w, WIRING).status : 0; } \
+    int CRFP_API(crfp_##X##_forward_batch)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks, float* out, int n, int t, \
+                                           int h, int w, void* workspace, size_t workspace_bytes, void* stream) { \
+        return forward_batch_impl(WIRING, packed, flags, lrs, fvs, mks, out, n, t, h, w, workspace, workspace_bytes, stream); \
+    } \
+    int CRFP_API(crfp_##X##_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv, const uint8_t* mk, \
+                                          const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace, size_t workspace_bytes, \
+                                          void* stream) { \
+        return stream_batch_impl(WIRING, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream); \
+    }
+
 extern "C" {
 
-int CRFP_API(crfp_dsv_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
-                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return stream_batch_impl(W_DSV, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
-}
+CRFP_PARAM_NAME_EXPORT(dsv, W_DSV)
+CRFP_PARAM_NAME_EXPORT(cra, W_CRA)
+CRFP_WIRING_EXPORTS(dsv, W_DSV)
+CRFP_WIRING_EXPORTS(cra, W_CRA)
+CRFP_WIRING_EXPORTS(simple, W_SIMPLE)
+CRFP_WIRING_EXPORTS(dense, W_DENSE)
 
-// The same call for the reference's streaming MRCF_simple_v13 / v15 (the CRFP_simple / CRFP wirings): packed = the wiring's packed weights,
-// workspace sized by crfp_{simple,dense}_batch_workspace_bytes(n, 1, h, w); flags, n <= 32 and status words as crfp_dsv_stream_batch; `fg` is
-// accepted and ignored for any n.
-int CRFP_API(crfp_simple_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
-                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return stream_batch_impl(W_SIMPLE, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
+// one clip / one sequence per call
+size_t CRFP_API(crfp_dsv_workspace_bytes)(int t, int h, int w) { return CRFP_API(crfp_dsv_batch_workspace_bytes)(1, t, h, w); }
+size_t CRFP_API(crfp_dsv_status_offset)(int t, int h, int w) { return CRFP_API(crfp_dsv_batch_status_offset)(1, t, h, w); }
+int CRFP_API(crfp_dsv_forward_clip)(const void* packed, int flags, const float* lrs, const float* fvs, const uint8_t* mks,
+                          float* out, int t, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
+    return CRFP_API(crfp_dsv_forward_batch)(packed, flags, lrs, fvs, mks, out, 1, t, h, w, workspace, workspace_bytes, stream);
 }
-int CRFP_API(crfp_dense_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
-                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return stream_batch_impl(W_DENSE, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
-}
-
-// The same call for the reference's streaming MRCF_simple_v18_cra (the CRFP_DSV_CRA wiring): packed = crfp_cra_pack_weights' buffer, workspace
-// sized by crfp_cra_batch_workspace_bytes(n, 1, h, w); flags, n <= 32 and status words as crfp_dsv_stream_batch; `fg` is accepted and ignored
-// for any n.
-int CRFP_API(crfp_cra_stream_batch)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
-                          const uint8_t* mk, const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return stream_batch_impl(W_CRA, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream);
-}
-
 int CRFP_API(crfp_dsv_stream_frame)(const void* packed, int flags, const float* lr, const float* lr_prev, const float* fv,
                           const uint8_t* mk, const uint8_t* fg, float* out, int first, int h, int w, void* workspace,
                           size_t workspace_bytes, void* stream) {
@@ -1708,7 +1388,7 @@ int CRFP_API(crfp_dsv_stream_frame)(const void* packed, int flags, const float* 
 
 #ifndef CRFP_ACT_BF16
 int crfp_shutdown(void) {
-    destroy_all_side_streams();
+    SideTables::destroy_all();
     crfp_bf16::shutdown_side_streams();
     crfp::rt_shutdown_streams();
     return 0;

@@ -17,21 +17,18 @@
 //     Frame 0 uses the separate forward_resblocks_k_ modules on the full frame (:8617-8637).
 //   * the fovea arrives as an (Hf, Wf) crop fed twice to encoder_hr (:8507); conv_tttf runs on the top-left (Hf, Wf) crop of the 8x
 //     features (zero padding at the crop's own border) and its result is pasted back before the LeakyReLU (:8645-8648).
-// fp32 storage, default (split-fp16) precision only.
-#include "crfp_common.h"
+// fp32 storage, default (split-fp16) precision only.  The host machinery under the schedule -- packed items, pack loop, per-thread stream
+// tables, ConvArgs binding -- is engine_host.h, shared with the CRFP_DSV engine; the conv table, the Layout, the three-lane schedule and its
+// FNet pass (no K slices) are this file's own.
+#include "engine_host.h"
 
 #ifndef CRFP_ACT_BF16
 
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <mutex>
-#include <vector>
 
 namespace crfp {
 namespace rt {
 
-struct ConvDef { const char* stem; int cout, cin; };
 // state_dict order of crfp_amd.model.CRFP_runtime.MRCF_simple_v18 (mid_channels = 32) = the reference's (:8364-8467)
 static const ConvDef kRt[79] = {
     {"spynet.encoder1.0", 32, 6}, {"spynet.encoder1.2", 32, 32}, {"spynet.encoder2.0", 64, 32},
@@ -71,15 +68,6 @@ constexpr int RT_CI_LAST = 78;
 static int rt_cout(int ci, int y_only) { return (ci == RT_CI_LAST && y_only) ? 1 : kRt[ci].cout; }
 static int ci_dcn(int lvl, int which) { static const int base[3] = {13, 19, 25}; return base[lvl] + which; }   // 0 fuse .. 5 dcn (engine.hip)
 
-enum ItemType { T_MFMA = 0, T_NARROW = 1, T_DCN8 = 2, T_RAW = 3 };
-struct Item {
-    int type = T_MFMA;
-    ConvArgs c;
-    NarrowArgs nw;
-    int w1 = -1, w2 = -1;
-    size_t off_w = 0, off_b = 0, n_w = 0, n_b = 0, off_s = 0, n_s = 0;
-    const char* name = "";
-};
 enum {
     RI_F0 = 0, RI_ENC_LR0 = 14, RI_ENC_LR1, RI_UPS, RI_DOWN,
     RI_LVL0,                                   // per level 8: FUSE, DB0, DB1, OMF, DCNW, C1 (64 -> 32), B1 (32 -> 16), B2 (16 -> 32 + x)
@@ -92,52 +80,17 @@ enum { L_FUSE = 0, L_DB0, L_DB1, L_OMF, L_DCNW, L_C1, L_B1, L_B2 };
 static int it_lvl(int l, int which) { return RI_LVL0 + 8 * l + which; }
 static int it_first(int l, int which) { return RI_FIRST0 + 3 * l + which; }
 
-struct SrcSpec { int kind, nch; };
-
 struct Model {
     Item items[RI_COUNT];
     size_t total_floats = 0;
     int y_only;
 
-    void add_mfma(int id, const char* name, int ci, int ci2, std::vector<SrcSpec> srcs, int store, int ps_r, int act, float post_scale = 1.0f) {
-        Item& it = items[id];
-        it.type = T_MFMA; it.name = name; it.w1 = ci; it.w2 = ci2;
-        ConvArgs& a = it.c;
-        memset(&a, 0, sizeof(a));
-        int kq = 0, cbase = 0;
-        for (auto& s : srcs) {
-            ConvSrc& d = a.src[a.nsrc++];
-            d.kind = s.kind; d.nch = s.nch; d.nq = src_quads(s.kind, s.nch); d.cbase = cbase;
-            cbase += s.nch; kq += d.nq;
-        }
-        if (kq & 3) {   // K is consumed in 16-channel chunks
-            ConvSrc& d = a.src[a.nsrc++];
-            d.kind = SRC_ZERO; d.nq = 4 - (kq & 3); d.nch = d.nq; d.cbase = cbase; kq += d.nq;
-        }
-        a.kq = kq; a.cin_total = kRt[ci].cin;
-        a.cout = rt_cout(ci, y_only) + (ci2 >= 0 ? rt_cout(ci2, y_only) : 0);
-        a.store = store; a.ps_r = ps_r; a.act = act; a.post_scale = post_scale;
-        a.ctiles = (conv_packed_rows(a.cout, store, ps_r) + 31) / 32;
-        it.n_w = conv_packed_weight_floats(a);
-        it.n_b = (size_t)a.ctiles * 32;
-        it.n_s = conv_split_weight_bytes(a) / sizeof(float);
+    int cout_of(int ci, int ci2) const { return rt_cout(ci, y_only) + (ci2 >= 0 ? rt_cout(ci2, y_only) : 0); }
+    void add_mfma(int id, const char* name, int ci, int ci2, const std::vector<SrcSpec>& srcs, int store, int ps_r, int act, float post_scale = 1.0f) {
+        crfp::add_mfma(items[id], name, ci, ci2, kRt[ci].cin, cout_of(ci, ci2), srcs, store, ps_r, act, post_scale);
     }
-    void add_narrow(int id, const char* name, int ci, int ci2, std::vector<SrcSpec> srcs, int act, int epi) {
-        Item& it = items[id];
-        it.type = T_NARROW; it.name = name; it.w1 = ci; it.w2 = ci2;
-        NarrowArgs& a = it.nw;
-        memset(&a, 0, sizeof(a));
-        int kq = 0, cbase = 0;
-        for (auto& s : srcs) {
-            ConvSrc& d = a.src[a.nsrc++];
-            d.kind = s.kind; d.nch = s.nch; d.nq = src_quads(s.kind, s.nch); d.cbase = cbase;
-            cbase += s.nch; kq += d.nq;
-        }
-        a.kq = kq; a.cin_total = kRt[ci].cin;
-        a.cout = rt_cout(ci, y_only) + (ci2 >= 0 ? rt_cout(ci2, y_only) : 0);
-        a.act = act; a.epi = epi; a.y_only = y_only; a.post_scale = 1.0f;
-        it.n_w = narrow_packed_weight_floats(a);
-        it.n_b = 4;
+    void add_narrow(int id, const char* name, int ci, int ci2, const std::vector<SrcSpec>& srcs, int act, int epi) {
+        crfp::add_narrow(items[id], name, ci, ci2, kRt[ci].cin, cout_of(ci, ci2), y_only, srcs, act, epi);
     }
 
     explicit Model(int y_only_) : y_only(y_only_) {
@@ -187,15 +140,7 @@ struct Model {
         add_narrow(RI_R3F_B2, "conv_narrow:rt.res3_first.bneck2_add", 58, -1, {{Q, 2}}, CRFP_ACT_NONE, NE_PLAIN);
         add_narrow(RI_TTTF, "conv_narrow:rt.tttf_crop", 42, -1, {{Q, 4}, {Q, 4}}, CRFP_ACT_LRELU01, NE_PLAIN);
         add_narrow(RI_LAST, "conv_narrow:last_plus_base", RT_CI_LAST, -1, {{Q, 4}}, CRFP_ACT_NONE, NE_LAST);
-        size_t cur = 0;
-        for (int i = 0; i < RI_COUNT; ++i) {
-            Item& it = items[i];
-            if (it.w1 < 0) continue;
-            it.off_w = cur; cur += (it.n_w + 63) / 64 * 64;
-            it.off_b = cur; cur += (it.n_b + 63) / 64 * 64;
-            it.off_s = cur; cur += (it.n_s + 63) / 64 * 64;
-        }
-        total_floats = cur;
+        total_floats = assign_offsets(items, RI_COUNT);
     }
 };
 static const Model& model_for(int y_only) {
@@ -317,64 +262,28 @@ __global__ void rt_lrelu_paste_kernel(float4* __restrict__ feat, int H, int W, c
 // Three non-blocking streams + an event pool per (host thread, device), created lazily by the first crfp_rt_forward_clip on that device
 // and destroyed by crfp_shutdown(): the same contract as the CRFP_DSV engine's side stream (crfp_hip.h).  Every call joins all of them
 // back into the caller's stream before it returns.
-struct Lanes {
+// (the tables, their registry and the lease of a thread: StreamTables, engine_host.h)
+struct Lanes : EventPool {   // events are handed out in order and taken back at the start of every call
     hipStream_t s[3] = {nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> ev;
     size_t used = 0;
-    bool ok = true;
     hipEvent_t next_event() {
-        if (used == ev.size()) {
-            hipEvent_t e;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ok = false; return nullptr; }
-            ev.push_back(e);
-        }
-        return ev[used++];
+        hipEvent_t e = event(used);
+        if (e) ++used;
+        return e;
     }
     bool create() {
         for (int i = 0; i < 3 && ok; ++i)
             if (!s[i] && hipStreamCreateWithFlags(&s[i], hipStreamNonBlocking) != hipSuccess) ok = false;
         return ok;
     }
-    void destroy() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        ev.clear(); used = 0;
-        for (int i = 0; i < 3; ++i) { if (s[i]) (void)hipStreamDestroy(s[i]); s[i] = nullptr; }
-        ok = true;
-    }
+    void forget() {}   // nothing here belongs to a thread
+    void destroy() { used = 0; EventPool::destroy(s, 3); }
 };
-constexpr int kRtMaxDevices = 64;
-// per-thread tables leased from a process-wide registry with a free list, as the CRFP_DSV side streams (engine.hip): crfp_shutdown()
-// releases every thread's lanes, an exiting thread hands its table to the next new one without calling HIP
-struct LaneTable { Lanes dev[kRtMaxDevices]; };
-struct LaneRegistry { std::mutex mu; std::vector<LaneTable*> all, idle; };
-static LaneRegistry& lane_registry() { static LaneRegistry* r = new LaneRegistry(); return *r; }
-struct LaneLease {
-    LaneTable* t = nullptr;
-    ~LaneLease() {
-        if (!t) return;
-        LaneRegistry& r = lane_registry();
-        std::lock_guard<std::mutex> lk(r.mu);
-        r.idle.push_back(t);
-    }
-};
-static thread_local LaneLease g_lanes_tl;
-static Lanes* lane_table() {
-    if (!g_lanes_tl.t) {
-        LaneRegistry& r = lane_registry();
-        std::lock_guard<std::mutex> lk(r.mu);
-        if (!r.idle.empty()) { g_lanes_tl.t = r.idle.back(); r.idle.pop_back(); }
-        else { g_lanes_tl.t = new LaneTable(); r.all.push_back(g_lanes_tl.t); }
-    }
-    return g_lanes_tl.t->dev;
-}
 static Lanes* lanes_for_current_device() {
-    static const bool on = !(getenv("CRFP_SIDE_STREAM") && atoi(getenv("CRFP_SIDE_STREAM")) == 0);   // read once
-    int dev = 0;
-    if (!on || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kRtMaxDevices) return nullptr;
-    Lanes& l = lane_table()[dev];
-    if (!l.create()) return nullptr;
-    l.used = 0;
-    return &l;
+    Lanes* l = side_stream_enabled() ? StreamTables<Lanes>::current() : nullptr;
+    if (!l || !l->create()) return nullptr;
+    l->used = 0;
+    return l;
 }
 
 // ------------------------------------------------------------------ the schedule
@@ -385,27 +294,16 @@ struct Runner {
     const Layout& L;
     hipStream_t s;
     int rc = 0;
-#define RUN(expr) do { if (!rc) rc = (expr); } while (0)
     float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
     unsigned* ovf() const { return reinterpret_cast<unsigned*>(ws + L.status); }
-    struct SrcBind { const float* p; long long bs; int pad = 0; };
-    struct DstBind { float* p; long long bs; int q0, q1; int pad = 0; };
 
     void mfma(int id, int N, int H, int W, std::vector<SrcBind> srcs, std::vector<DstBind> dsts, int dstH = 0, int dstW = 0,
               const float* resid = nullptr, const float* flow = nullptr, float* s3 = nullptr, int dst_f32 = 0) {
         if (rc) return;
-        const Item& it = M.items[id];
-        ConvArgs a = it.c;
-        for (size_t i = 0; i < srcs.size(); ++i) { a.src[i].p = srcs[i].p; a.src[i].bstride = srcs[i].bs; a.src[i].pad = srcs[i].pad; }
-        a.ndst = (int)dsts.size();
-        for (size_t i = 0; i < dsts.size(); ++i) {
-            a.dst[i].p = dsts[i].p; a.dst[i].bstride = dsts[i].bs; a.dst[i].q0 = dsts[i].q0; a.dst[i].q1 = dsts[i].q1; a.dst[i].pad = dsts[i].pad;
-        }
-        a.N = N; a.H = H; a.W = W; a.dstH = dstH; a.dstW = dstW;
+        ConvArgs a = bind_conv(M.items[id], packed, N, H, W, srcs, dsts, ovf());   // no batch strides, no status-word mapping: one clip
+        a.dstH = dstH; a.dstW = dstW;
         a.resid = resid; a.flow = flow; a.s3_dst = s3; a.dst_f32 = dst_f32;
-        a.wpk = packed + it.off_w; a.bpk = packed + it.off_b; a.wsplit = packed + it.off_s;
-        a.ovf = ovf();
-        rc = launch_conv_mfma(a, it.name, s);
+        rc = launch_conv_mfma(a, M.items[id].name, s);
     }
     void mfma_q(int id, int N, const float* in, int nqi, float* out, int nqo, int H, int W) {
         mfma(id, N, H, W, {{in, (long long)nqi * H * W * 4}}, {{out, (long long)nqo * H * W * 4, 0, nqo}});
@@ -619,16 +517,10 @@ struct Runner {
         for (int l = 0; l < 3; ++l) wait(e_l[l]);                                                        // the carried features of this frame are complete
         frame_done[par] = rec();
     }
-#undef RUN
 };
 
 }  // namespace rt
-void rt_shutdown_streams() {
-    rt::LaneRegistry& r = rt::lane_registry();
-    std::lock_guard<std::mutex> lk(r.mu);
-    for (rt::LaneTable* t : r.all)
-        for (int d = 0; d < rt::kRtMaxDevices; ++d) t->dev[d].destroy();
-}
+void rt_shutdown_streams() { StreamTables<rt::Lanes>::destroy_all(); }
 }  // namespace crfp
 
 using namespace crfp;
@@ -654,38 +546,10 @@ size_t crfp_rt_packed_weight_bytes(int y_only) { return model_for(y_only).total_
 int crfp_rt_pack_weights(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream) {
     const Model& M = model_for(y_only);
     if (!params || !packed) { set_error("rt_pack_weights: null argument"); return CRFP_E_BADARG; }
-    if (packed_bytes < M.total_floats * sizeof(float)) { set_error("rt_pack_weights: packed buffer too small"); return CRFP_E_WORKSPACE; }
+    if (int rc = check_packed_size("rt_pack_weights", M.total_floats, packed_bytes)) return rc;
     for (int i = 0; i < CRFP_RT_NUM_PARAMS; ++i)
         if (!params[i]) { set_error("rt_pack_weights: parameter %d (%s) is null", i, crfp_rt_param_name(i)); return CRFP_E_BADARG; }
-    hipStream_t s = (hipStream_t)stream;
-    float* pk = (float*)packed;
-    for (int i = 0; i < RI_COUNT; ++i) {
-        const Item& it = M.items[i];
-        if (it.w1 < 0) continue;
-        const float* w = params[2 * it.w1];
-        const float* b = params[2 * it.w1 + 1];
-        const float* w2 = it.w2 >= 0 ? params[2 * it.w2] : nullptr;
-        const float* b2 = it.w2 >= 0 ? params[2 * it.w2 + 1] : nullptr;
-        const int split = rt_cout(it.w1, y_only);
-        int rc = 0;
-        switch (it.type) {
-            case T_MFMA:
-                rc = launch_conv_pack(it.c, w, b, w2, b2, split, pk + it.off_w, pk + it.off_b, s);
-                if (!rc) rc = launch_conv_pack_split(it.c, w, w2, split, pk + it.off_s, s);
-                break;
-            case T_NARROW: rc = launch_narrow_pack(it.nw, w, b, w2, b2, split, pk + it.off_w, pk + it.off_b, s); break;
-            case T_DCN8:
-                rc = launch_dcn_g8_pack(w, pk + it.off_w, s, false);
-                if (!rc) rc = launch_dcn_g8_pack(w, pk + it.off_w + 36 * 2 * 32 * 4, s, true);
-                if (!rc && hipMemcpyAsync(pk + it.off_b, b, 32 * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = 1;
-                break;
-            default:
-                if (hipMemcpyAsync(pk + it.off_w, w, it.n_w * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = 1;
-                if (!rc && hipMemcpyAsync(pk + it.off_b, b, it.n_b * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) rc = 1;
-        }
-        if (rc) return rc;
-    }
-    return 0;
+    return pack_items(M.items, RI_COUNT, params, [&](int ci) { return rt_cout(ci, y_only); }, (float*)packed, (hipStream_t)stream);
 }
 
 static int rt_check_dims(int t, int h, int w, int fh, int fw, int wph, int wpw) {
