@@ -423,6 +423,15 @@ int crfp_frame_metrics_f32(const float* sr, const float* hr, const uint8_t* mask
     return launch_frame_metrics(sr, hr, masks, out, n, c, m, h, w, flags & CRFP_METRICS_LUMA, workspace, (hipStream_t)stream);
 }
 
+int crfp_gaze_prep_f32(const float* gt, const int32_t* rows, float* fv, uint8_t* mk, uint8_t* regions, uint8_t* fg, int n, int c, int h, int w,
+                       int dilate, void* stream) {
+    if (!rows || !mk || !regions || !fg) { set_error("gaze_prep: null pointer (rows, mk, regions and fg are required)"); return CRFP_E_BADARG; }
+    if ((gt == nullptr) != (fv == nullptr)) { set_error("gaze_prep: gt and fv go together (both given, or both null for the masks alone)"); return CRFP_E_BADARG; }
+    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("gaze_prep: bad argument (need n, c, h, w >= 1)"); return CRFP_E_BADARG; }
+    if (dilate < 0) { set_error("gaze_prep: dilate must be >= 0, got %d", dilate); return CRFP_E_BADARG; }
+    return launch_gaze_prep(gt, rows, fv, mk, regions, fg, n, c, h, w, dilate, (hipStream_t)stream);
+}
+
 int crfp_psnr_partial_f32(const float* a, const float* b, double* acc, int n, int c, int h, int w, void* stream) {
     if (!a || !b || !acc || n < 1 || c < 1 || h < 1 || w < 1) { set_error("psnr_partial: bad argument"); return CRFP_E_BADARG; }
     return launch_psnr_partial(a, b, acc, n, c, h, w, (hipStream_t)stream);

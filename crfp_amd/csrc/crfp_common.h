@@ -474,5 +474,8 @@ long long frame_metrics_tiles(int H, int W);
 size_t frame_metrics_workspace_bytes(int N, int M, int H, int W);
 int launch_frame_metrics(const float* sr, const float* hr, const uint8_t* masks, double* out, int N, int C, int M, int H, int W, int luma,
                          void* workspace, hipStream_t s);
+// gaze.hip: the gaze rig's masks, regions stack and fovea frame of n frames from their rectangle rows (CRFP_GAZE_ROW_INTS ints each)
+int launch_gaze_prep(const float* gt, const int* rows, float* fv, uint8_t* mk, uint8_t* regions, uint8_t* fg, int N, int C, int H, int W,
+                     int dilate, hipStream_t s);
 
 }  // namespace CRFP_NS

@@ -11,6 +11,9 @@ Per frame n (one model call, state kept on the device between calls):
     mk_past = union of the last three mk_out, as it was BEFORE this frame's ring is pushed (:371-375);
     fg = the regional-DCN box of rg x rg pixels around the window centre, or all ones (:351-358).
   * metrics = utils.calc_psnr_and_ssim_cuda(sr, gt, mask) for whole / fovea / outskirt / past (:360-370), arithmetic mean.
+  * rect_table / FusedRegionMasks (opt-in, ``fused_masks``): every mask above is a function of this frame's window, the three previous ones and
+    the regional box, so one crfp_gaze_prep_f32 call per frame writes mk, fovea / outskirt / past (already stacked for the metrics table), fg
+    and fv = gt inside mk from a rectangle table uploaded once per trajectory.
   * score maps (optional) = utils.foveated_metric(.., kernel_size=10, stride_size=5) of the model output and of a baseline frame
     against the ground truth (:381-384), and the running extrema the rig keeps from the baseline's call (:385-392).
 """
@@ -86,9 +89,66 @@ class RegionMasks:
         return out
 
 
+def rect_table(origins: Sequence[Tuple[int, int]], H: int, W: int, fv_size: int, fv_start: int = 0, regional_dcn: bool = False,
+               rg_h: int = 0, rg_w: int = 0) -> np.ndarray:
+    """The rows crfp_gaze_prep_f32 reads, int32 [N, 24], for the whole trajectory `origins` = [(cur_y, cur_x)] (window_origin's values): ints 0..3
+    the regional box y0, y1, x0, x1 (regional_box; the whole frame without regional DCN), then four entries y, x, h, w, flags -- frame n's window,
+    then those of frames n - 1, n - 2, n - 3; flags bit 0: the entry exists, bit 1: its window counts as mk (frame index >= fv_start)."""
+    from ._lib import GAZE_COUNTS, GAZE_EXISTS, GAZE_ROW_INTS
+    rows = np.zeros((len(origins), GAZE_ROW_INTS), dtype=np.int32)
+    for n, (cur_y, cur_x) in enumerate(origins):
+        rows[n, 0:4] = regional_box(cur_y, cur_x, fv_size, rg_h, rg_w, H, W) if regional_dcn else (0, H, 0, W)
+        for e in range(min(n, 3) + 1):
+            y, x = origins[n - e]
+            rows[n, 4 + 5 * e:9 + 5 * e] = (y, x, fv_size, fv_size, GAZE_EXISTS | (GAZE_COUNTS if n - e >= fv_start else 0))
+    return rows
+
+
+class FusedRegionMasks:
+    """RegionMasks from rectangles: the trajectory's rect_table is uploaded once and frame n is ONE crfp_gaze_prep_f32 call on row n (a device
+    pointer offset: nothing is uploaded or synchronised per frame).  `origins` = [(cur_y, cur_x)] of every frame."""
+
+    DILATE = 10   # dilate10's iterations
+
+    def __init__(self, H: int, W: int, fv_size: int, device, fv_start: int = 0, regional_dcn: bool = False,
+                 rg_h: int = 0, rg_w: int = 0, origins: Sequence[Tuple[int, int]] = ()):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("crfp_amd: FusedRegionMasks needs a CUDA/HIP device (this build has no CPU path)")
+        self.H, self.W, self.dev = H, W, device
+        self.rows_host = rect_table(origins, H, W, fv_size, fv_start, regional_dcn, rg_h, rg_w)
+        self.rows = torch.from_numpy(self.rows_host).to(device)
+
+    def frame(self, n: int, gt: Optional[torch.Tensor] = None) -> Dict[str, Optional[torch.Tensor]]:
+        """RegionMasks.frame's dict for frame n (bool views of the byte planes; "past" is None on frame 0) plus "regions" = the uint8
+        [1,3,H,W] stack fovea / outskirt / past that utils.frame_metrics_table takes and "fv" = gt [1,C,H,W] inside mk, 0 elsewhere (None
+        without gt).  Fresh tensors every call: the engine may still be reading the previous frame's."""
+        from . import _lib
+        from .ops import _dev, _stream
+        H, W = self.H, self.W
+        if not 0 <= n < self.rows.shape[0]:
+            raise IndexError(f"frame {n} is outside the trajectory of {self.rows.shape[0]} frames")
+        c, fv = 1, None
+        if gt is not None:
+            gt = _dev(gt, "gt")
+            if gt.dim() != 4 or gt.shape[0] != 1 or tuple(gt.shape[2:]) != (H, W) or gt.device != self.dev:
+                raise ValueError(f"gt must be [1,C,{H},{W}] on {self.dev}, got {tuple(gt.shape)} on {gt.device}")
+            c, fv = gt.shape[1], torch.empty_like(gt)
+        mk = torch.empty((1, 1, H, W), dtype=torch.uint8, device=self.dev)
+        fg = torch.empty((1, 1, H, W), dtype=torch.uint8, device=self.dev)
+        regions = torch.empty((1, 3, H, W), dtype=torch.uint8, device=self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(_lib.lib().crfp_gaze_prep_f32(None if gt is None else gt.data_ptr(), self.rows[n].data_ptr(),
+                                                     None if fv is None else fv.data_ptr(), mk.data_ptr(), regions.data_ptr(), fg.data_ptr(),
+                                                     1, c, H, W, self.DILATE, _stream()), "crfp_gaze_prep_f32")
+        rb = regions.view(torch.bool)
+        return {"mk": mk.view(torch.bool), "fovea": rb[:, 0:1], "outskirt": rb[:, 1:2], "past": rb[:, 2:3] if n > 0 else None,
+                "fg": fg.view(torch.bool), "fv": fv, "regions": regions}
+
+
 def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_size: int = 96, seed: int = 1234,
                    fv_start: int = 0, regional_dcn: bool = False, rg: int = 0, metric_fn=None, score_maps: bool = False,
-                   baseline: Optional[torch.Tensor] = None, fused_metrics: bool = False) -> Dict[str, object]:
+                   baseline: Optional[torch.Tensor] = None, fused_metrics: bool = False, fused_masks: bool = False) -> Dict[str, object]:
     """Stream `lr [N,3,h,w]` / `gt [N,3,8h,8w]` (device tensors, range [0,1]) through `model` (MRCF_simple_v18 interface:
     ``model(lrs=, fvs=, mks=, fgs=)`` one frame per call, ``clear_states()``) along a gaussian gaze trajectory and collect
     the rig's region metrics.  Returns per-region mean PSNR / SSIM, the trajectory and the outputs' checksum.
@@ -99,7 +159,9 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
     there is no baseline).  All of it stays on the device: no host synchronisation is added to the loop.
     fused_metrics: the four regions of a frame come from ONE utils.frame_metrics_table call (masks fovea / outskirt / past; frame 0
     passes an all-zero past whose row is dropped), the rows stay on the device and are fetched once after the loop: the loop
-    itself no longer synchronises.  Same dict."""
+    itself no longer synchronises.  Same dict.
+    fused_masks: the masks and fv of a frame come from ONE crfp_gaze_prep_f32 call (FusedRegionMasks) instead of the composed RegionMasks and
+    `gt * mk`; with fused_metrics its regions stack goes to the table as it is.  Same dict, same values."""
     regions_fn = None
     if fused_metrics:
         if metric_fn is not None:
@@ -110,7 +172,11 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
         metric_fn, regions_fn = U.calc_psnr_and_ssim_cuda, U.calc_psnr_and_ssim_regions
     N, _, H, W = gt.shape
     xs, ys = gaze_trajectory(N, H, W, sigma, np.random.RandomState(seed))
-    masks = RegionMasks(H, W, fv_size, gt.device, fv_start, regional_dcn, rg, rg)
+    origins = [window_origin(xs[n], ys[n], fv_size, H, W) for n in range(N)]
+    if fused_masks:
+        masks = FusedRegionMasks(H, W, fv_size, gt.device, fv_start, regional_dcn, rg, rg, origins=origins)
+    else:
+        masks = RegionMasks(H, W, fv_size, gt.device, fv_start, regional_dcn, rg, rg)
     regions = ("whole", "fovea", "outskirt", "past")
     acc = {r: [] for r in regions}
     traj = []
@@ -125,18 +191,25 @@ def run_gaze_video(model, lr: torch.Tensor, gt: torch.Tensor, sigma: float, fv_s
     model.clear_states()
     with torch.no_grad():
         for n in range(N):
-            cur_y, cur_x = window_origin(xs[n], ys[n], fv_size, H, W)
+            cur_y, cur_x = origins[n]
             traj.append((cur_y, cur_x))
-            m = masks.frame(n, cur_y, cur_x)
             g = gt[n:n + 1]
-            fv = g * m["mk"]
+            if fused_masks:
+                m = masks.frame(n, g)
+                fv = m["fv"]
+            else:
+                m = masks.frame(n, cur_y, cur_x)
+                fv = g * m["mk"]
             sr = model(lrs=lr[n:n + 1].unsqueeze(0), fvs=fv.unsqueeze(0), mks=m["mk"].unsqueeze(0), fgs=m["fg"].unsqueeze(0))
             sr = sr.reshape(1, -1, H, W)
             todo = [(r, mask) for r, mask in (("whole", ones), ("fovea", m["fovea"]), ("outskirt", m["outskirt"]),
                                               ("past", m["past"])) if mask is not None]   # frame 0 has no past ring
             if fused_metrics:   # one call for the four regions, nothing fetched inside the loop
-                past = m["past"] if m["past"] is not None else no_past
-                rows.append(U.frame_metrics_table(sr, g, torch.cat((m["fovea"], m["outskirt"], past), 1))[0])
+                if fused_masks:   # frame 0's past plane is all zero, as no_past is
+                    stack = m["regions"]
+                else:
+                    stack = torch.cat((m["fovea"], m["outskirt"], m["past"] if m["past"] is not None else no_past), 1)
+                rows.append(U.frame_metrics_table(sr, g, stack)[0])
             elif regions_fn is not None:   # one range probe and one host sync per frame
                 for (r, _), (p, s) in zip(todo, regions_fn(sr, g, [mask for _, mask in todo])):
                     acc[r].append((float(p), float(s)))
@@ -198,6 +271,8 @@ def main(argv=None):
                     help="also time the stream with the per-window score maps of the output and of the bilinear x8 baseline")
     ap.add_argument("--fused-metrics", action="store_true",
                     help="also time the stream with the four regions of a frame scored by one fused call and fetched once at the end")
+    ap.add_argument("--fused-masks", action="store_true",
+                    help="also time the stream with the masks and the fovea frame of a frame from one fused call, and the fused region metrics")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     if a.cra and a.model_code != 18:
@@ -254,6 +329,14 @@ def main(argv=None):
         run_gaze_video(m, lr, gt, a.sigma, a.fv_size, a.seed, regional_dcn=a.regional_dcn > 0, rg=a.regional_dcn, fused_metrics=True)
         torch.cuda.synchronize()
         extra["frames_per_sec_with_fused_region_metrics"] = a.frames / (time.perf_counter() - t0)
+    if a.fused_masks:
+        run_gaze_video(m, lr[:3], gt[:3], a.sigma, a.fv_size, a.seed, fused_metrics=True, fused_masks=True)   # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run_gaze_video(m, lr, gt, a.sigma, a.fv_size, a.seed, regional_dcn=a.regional_dcn > 0, rg=a.regional_dcn, fused_metrics=True,
+                       fused_masks=True)
+        torch.cuda.synchronize()
+        extra["frames_per_sec_with_fused_masks_and_metrics"] = a.frames / (time.perf_counter() - t0)
     model = "" if a.model_code == 18 and not a.cra else f", {type(m).__name__}"
     print(json.dumps({"workload": f"BASELINE config 3 shape: {a.frames} streamed frames {a.lr_h}x{a.lr_w} -> x8, sigma_T={a.sigma}, fp32, synthetic{model}",
                       "frames_per_sec_with_region_metrics": a.frames / dt, "frames_per_sec_model_only": a.frames / dt_model, **extra, **res}))

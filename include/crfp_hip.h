@@ -35,6 +35,7 @@
  *   crfp_psnr_partial_f32     utils.py:166-185,242-254,328-330 (psnr_cuda / bgr2ycbcr(y_only))
  *   crfp_window_scores_f32    test_video.py:23-63 foveated_metric (per-window PSNR / SSIM maps)
  *   crfp_frame_metrics_f32    trainer.py:348-369 / test_video.py:360-370 (per-frame, per-region PSNR / SSIM / PSNR-Y / SSIM-Y)
+ *   crfp_gaze_prep_f32        test_video.py:335-358,371-375 (fv / mk / mk_fv / mk_out / mk_past / fg of one streamed frame)
  *   crfp_spynet_forward       model/CRFP.py:554-741 SPyNet.forward (+ SPyNetBasicModule, `conv` :145-152)
  *   crfp_convkxk_f32          model/CRFP.py:145-152 `conv`: ReLU -> nn.Conv2d(k, stride 1, pad k/2)
  *   crfp_upsample_bilinear_ac_f32  F.interpolate(..., bilinear, align_corners=True) (model/CRFP.py:647-651)
@@ -196,6 +197,28 @@ int crfp_window_scores_f32(const float* hr, const float* sr, float* psnr, float*
 size_t crfp_frame_metrics_workspace_bytes(int n, int m, int h, int w);
 int crfp_frame_metrics_f32(const float* sr, const float* hr, const uint8_t* masks, double* out, int n, int c, int m, int h, int w, int flags,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* The gaze rig's per-frame inputs from rectangles, one streaming pass (test_video.py:335-358,371-375: the fovea frame and mask, the fovea /
+ * outskirt / past regions the metrics score and the regional-DCN box): what a host of crfp_dsv_stream_frame needs to turn a fovea window into
+ * that call's full-frame `fv`, `mk` and `fg`, and crfp_frame_metrics_f32's `masks`.  gt, fv: [n,c,h,w] fp32, both given or both NULL (masks
+ * only); mk, fg: [n,1,h,w] bytes; regions: [n,3,h,w] bytes, planes fovea, outskirt, past.  rows: DEVICE memory, n rows of
+ * CRFP_GAZE_ROW_INTS int32: ints 0..3 the regional box y0, y1, x0, x1 (half-open; the whole frame when there is none), then four entries of
+ * five ints y, x, h, w, flags -- entry 0 this frame's fovea window, entries 1..3 the previous frames' windows, newest first; flags bit 0
+ * (CRFP_GAZE_EXISTS): the entry exists, bit 1 (CRFP_GAZE_COUNTS): its window counts as mk (the rig: frame index >= fv_start).  With R_e = entry e's rectangle intersected with the frame and G_e = the rectangle grown by `dilate` pixels on all four sides
+ * intersected with the frame (the rig's ten 3x3 dilations of one rectangle: dilate = 10; both empty for an entry that does not exist or has
+ * h < 1 or w < 1), per pixel p:
+ *   fovea = p in R_0;  mk = COUNTS_0 and p in R_0;  outskirt = p in G_0 and not mk;
+ *   past = OR over e = 1..3 of (p in G_e and not (COUNTS_e and p in R_e));  fg = p in box;  fv = mk ? gt : +0.
+ * Mask bytes are exactly 0 or 1 and every output element is written once.  Rectangles are clipped to the frame on the device in 64-bit
+ * arithmetic: no row content addresses outside the planes.  gt is read only inside mk.  16-byte stores when w % 4 == 0 and every pointer is
+ * 16-byte aligned, an element-wise form otherwise.  Asynchronous on `stream`, no workspace, no atomics, nothing to initialise.  Errors
+ * (CRFP_E_BADARG, before any HIP call): n, c, h, w < 1, dilate < 0, null rows / mk / regions / fg, gt without fv or fv without gt;
+ * n > 65535 is CRFP_E_UNSUPPORTED. */
+#define CRFP_GAZE_ROW_INTS 24
+#define CRFP_GAZE_EXISTS 1
+#define CRFP_GAZE_COUNTS 2
+int crfp_gaze_prep_f32(const float* gt, const int32_t* rows, float* fv, uint8_t* mk, uint8_t* regions, uint8_t* fg, int n, int c, int h, int w,
+                       int dilate, void* stream);
 
 /* ---- CRFP_DSV engine (mid_channels=32, hr_dcn=True, offset_prop=True; y_only selectable).
  * Parameters arrive as CRFP_DSV_NUM_PARAMS device pointers in the order of the reference's

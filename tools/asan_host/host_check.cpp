@@ -171,6 +171,39 @@ int main() {
                 }
         EXPECT(crfp_stub_launches() == l0 + 3 * accepted);
     }
+    // the gaze rig's rectangle pass: every refusal before the first launch, one launch per accepted call, masks-only calls included
+    {
+        uint8_t* const k16 = reinterpret_cast<uint8_t*>(16);
+        const int32_t* const r16 = reinterpret_cast<const int32_t*>(16);
+        const long l0 = crfp_stub_launches();
+        EXPECT(crfp_gaze_prep_f32(p16, nullptr, p16, k16, k16, k16, 2, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, nullptr, k16, k16, 2, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, nullptr, k16, 2, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, nullptr, 2, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(nullptr, r16, p16, k16, k16, k16, 2, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);   // fv without gt
+        EXPECT(std::strstr(crfp_last_error_string(), "gt and fv") != nullptr);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, nullptr, k16, k16, k16, 2, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);   // gt without fv
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, k16, 0, 3, 24, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, k16, 2, 0, 24, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, k16, 2, 3, 0, 32, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, k16, 2, 3, 24, -1, 10, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, k16, 2, 3, 24, 32, -1, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "dilate") != nullptr);
+        EXPECT(crfp_gaze_prep_f32(p16, r16, p16, k16, k16, k16, 70000, 3, 24, 32, 10, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_gaze_prep_f32(nullptr, r16, nullptr, k16, k16, k16, 1, 1, 2147483647, 2147483647, 10, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_stub_launches() == l0);
+        int accepted = 0;
+        for (const auto& g : {std::initializer_list<int>{1, 1}, {23, 45}, {16, 64}, {1440, 2560}})
+            for (int c : {1, 3})
+                for (int masks_only : {0, 1})
+                    for (uint8_t* m : {k16, reinterpret_cast<uint8_t*>(20)}) {   // 16-byte aligned and not: both kernel forms
+                        EXPECT(crfp_gaze_prep_f32(masks_only ? nullptr : p16, r16, masks_only ? nullptr : p16, m, k16, k16, 2, c, g.begin()[0],
+                                                  g.begin()[1], 10, nullptr) == 0);
+                        ++accepted;
+                    }
+        EXPECT(crfp_stub_launches() == l0 + accepted);
+    }
     // ---- whole engine calls on the stub runtime (tools/asan_host/hip_stub.cpp: every HIP call succeeds, no kernel runs): the host side of a
     // call -- argument checks, Layout arenas, the launch-argument tables of ~50 launches per frame, the fork / join of the side stream, the
     // per-thread stream table and crfp_shutdown() -- under the sanitizers.  Device pointers are fabricated and never dereferenced on the host.
