@@ -2,9 +2,11 @@
 // the reference path (model/CRFP.py:303-317, 449-450, 532, 172-176, 257-261, 747-795; model/LTE.py:40-42).
 //
 // File map: shared epilogue (conv_epilogue_t) | fp32-MFMA kernel conv3x3_mfma_kernel (v_mfma_f32_32x32x2_f32: the per-op
-// C-ABI and the few convs with NCHW / ragged-K sources) | the split-operand kernels on the 16-bit MFMA: the DEFAULT
-// conv3x3_split_kernel<1,1,2> (f16x3; bf16x6 as <.,.,3>), and the opt-in experiments (pipelined
-// persistent, input-stationary, warp-specialised) | weight packers | launch_conv_mfma.
+// C-ABI and the few convs with NCHW / ragged-K sources) | the split-operand kernels: the DEFAULT
+// conv3x3_split_kernel<1,1,2> (f16x3; bf16x6 as <.,.,3>) and the 8-wave conv3x3_split8_kernel | the
+// bf16-storage kernels and the chunk-staging helpers two of them share | conv_mfma_lab.inc (lab library only: the main
+// loops that lost their A/B -- persistent, pipelined, input-stationary, warp-specialised -- their knobs and dispatch) |
+// weight packers | conv_work / prepare_plan and the four launchers.
 // The layout notes below are written for the fp32 kernel; the split kernels share orientation, lane map and epilogue.
 //
 // GEMM orientation:  D[cout][pixel] += A[cout][k] * B[k][pixel]
@@ -671,6 +673,53 @@ __device__ __forceinline__ void load_quad_batch_v(f32x4 (&r)[NIN], const ConvSrc
     }
 }
 
+// s_memtime phase stamps of conv3x3_split_body (CRFP_STAMP_PTR / CRFP_STAMP_NAME): lab library only, nothing in the product
+#ifdef CRFP_LAB
+#define SB_STAMP_ENTRY const long long t_entry = __builtin_amdgcn_s_memtime();
+#define SB_STAMP_BEGIN long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
+#define SB_STAMP(ACC) if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); ACC += t - t0; t0 = t; }
+// diagnostic: the load-landing wait is booked under C
+#define SB_STAMP_LANDED                                                                                   \
+    if (a.stamps) {                                                                                       \
+        long long t = __builtin_amdgcn_s_memtime(); tA += t - t0; t0 = t;                                 \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                  \
+        t = __builtin_amdgcn_s_memtime(); tC += t - t0; t0 = t;                                           \
+    }
+#define SB_STAMP_LOOP_END                                                                                 \
+    if (a.stamps) {                                                                                       \
+        const long long t = __builtin_amdgcn_s_memtime(); tD += t - t0; t0 = t;                           \
+        if (tid == 0) {                                                                                   \
+            long long* o = a.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8;               \
+            o[0] = tA; o[1] = tB; o[2] = tC; o[3] = tD; o[4] = t_entry; o[5] = t;                         \
+        }                                                                                                 \
+    }
+#define SB_STAMP_ACC_DONE                                                                                 \
+    long long te1 = 0, te2 = 0;                                                                           \
+    if (a.stamps) { asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[0][PT - 1][15])); te1 = __builtin_amdgcn_s_memtime(); }
+#define SB_STAMP_EPI_CTX                                                                                  \
+    if (a.stamps) { asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(ec.dpitch[0]), "s"(ec.ncq), "s"(ec.slope)); te2 = __builtin_amdgcn_s_memtime(); }
+#define SB_STAMP_EPI_DONE                                                                                 \
+    if (a.stamps) {                                                                                       \
+        const long long ti = __builtin_amdgcn_s_memtime();      /* epilogue issued (stores in flight) */  \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                  \
+        if (tid == 0) {                                                                                   \
+            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 2] = te1;   /* overwrites phase C (unused here) */ \
+            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 3] = te2;   /* overwrites phase D */ \
+            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 7] = ti;                      \
+            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 6] = __builtin_amdgcn_s_memtime(); \
+        }                                                                                                 \
+    }
+#else
+#define SB_STAMP_ENTRY
+#define SB_STAMP_BEGIN
+#define SB_STAMP(ACC)
+#define SB_STAMP_LANDED
+#define SB_STAMP_LOOP_END
+#define SB_STAMP_ACC_DONE
+#define SB_STAMP_EPI_CTX
+#define SB_STAMP_EPI_DONE
+#endif
+
 // The kernel's body: workgroup wg_x of wg_nx (the launch's work items: (tile, cout-tile group)) of batch item n of plan a.  A function so that
 // conv3x3_split_dual_kernel (below) can run TWO plans in one launch.
 // KS (round 6, FNet's small maps): blockIdx.z enumerates (batch item, K slice) -- slice z % a.ksplit walks chunks [slice * nchunks / ksplit, ...) of
@@ -678,9 +727,7 @@ __device__ __forceinline__ void load_quad_batch_v(f32x4 (&r)[NIN], const ConvSrc
 // act NONE / no residual / no guard); launch_ksplit_reduce or the pool / resize pass behind the layer adds the slices in order.
 template <int CT, int RPW, int NP, bool KS = false>
 __device__ __forceinline__ void conv3x3_split_body(const ConvArgs& a, const int wg_x, const int wg_nx, const int n) {
-#ifdef CRFP_LAB
-    const long long t_entry = __builtin_amdgcn_s_memtime();
-#endif
+    SB_STAMP_ENTRY
     constexpr int TH = 4 * RPW, LH = TH + 2, PT = 2 * RPW;
     constexpr int NEL = LH * LW;                 // halo pixels
     constexpr int NIN = (NEL + 255) / 256;       // halo pixels per thread; each carries the chunk's 4 quads
@@ -772,21 +819,13 @@ __device__ __forceinline__ void conv3x3_split_body(const ConvArgs& a, const int 
         }                                                                                                 \
     }
 
-#ifdef CRFP_LAB
-    long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
-#endif
+    SB_STAMP_BEGIN
     const int ch_begin = KS ? kslice * (nchunks / kslices) : 0, ch_end = KS ? ch_begin + nchunks / kslices : nchunks;
     CRFP_SPLIT_ISSUE(ch_begin)
     for (int ch = ch_begin; ch < ch_end; ++ch) {
         const int m0 = qm0, m1 = qm1, m2 = qm2, m3 = qm3;  // component masks of the chunk now in registers
         __syncthreads();  // every wave finished reading the previous chunk
-#ifdef CRFP_LAB
-        if (a.stamps) {
-            long long t = __builtin_amdgcn_s_memtime(); tA += t - t0; t0 = t;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            t = __builtin_amdgcn_s_memtime(); tC += t - t0; t0 = t;   // diagnostic: load-landing wait booked under C
-        }
-#endif
+        SB_STAMP_LANDED
         if (NP == 2 && (m0 & 16)) {   // SRC_S3 chunk (wave-uniform): the producer already split it -- copy, zero outside the image
 #pragma unroll
             for (int t = 0; t < NIN; ++t) {
@@ -834,13 +873,9 @@ __device__ __forceinline__ void conv3x3_split_body(const ConvArgs& a, const int 
             if (idx < CT * WPC) (&wlds[0][0])[idx] = rws[k];
         }
         __syncthreads();
-#ifdef CRFP_LAB
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tB += t - t0; t0 = t; }
-#endif
+        SB_STAMP(tB)
         if (ch + 1 < ch_end) CRFP_SPLIT_ISSUE(ch + 1)
-#ifdef CRFP_LAB
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tD += t - t0; t0 = t; }  // diagnostic: issue booked under D
-#endif
+        SB_STAMP(tD)   // diagnostic: issue booked under D
 #pragma unroll CRFP_SPLIT_TAP_UNROLL
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - 3 * ky;
@@ -859,21 +894,11 @@ __device__ __forceinline__ void conv3x3_split_body(const ConvArgs& a, const int 
                 for (int ct = 0; ct < CT; ++ct) split_mfma<NP>(acc[ct][pt], acl[ct][pt], wa[ct], bq);
             }
         }
-#ifdef CRFP_LAB
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tD += t - t0; t0 = t; }
-#endif
+        SB_STAMP(tD)
     }
 #undef CRFP_SPLIT_ISSUE
 #undef CRFP_QDESC
-#ifdef CRFP_LAB
-    if (a.stamps) {
-        const long long t = __builtin_amdgcn_s_memtime(); tD += t - t0; t0 = t;
-        if (tid == 0) {
-            long long* o = a.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8;
-            o[0] = tA; o[1] = tB; o[2] = tC; o[3] = tD; o[4] = t_entry; o[5] = t;
-        }
-    }
-#endif
+    SB_STAMP_LOOP_END
     if (NP == 2) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -882,27 +907,11 @@ __device__ __forceinline__ void conv3x3_split_body(const ConvArgs& a, const int 
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[ct][pt][e] += acl[ct][pt][e] * (1.0f / F16_RES_SCALE);
     }
-#ifdef CRFP_LAB
-    long long te1 = 0, te2 = 0;
-    if (a.stamps) { asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[0][PT - 1][15])); te1 = __builtin_amdgcn_s_memtime(); }
-#endif
+    SB_STAMP_ACC_DONE
     const EpiCtx ec = epi_ctx(a, n);
-#ifdef CRFP_LAB
-    if (a.stamps) { asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(ec.dpitch[0]), "s"(ec.ncq), "s"(ec.slope)); te2 = __builtin_amdgcn_s_memtime(); }
-#endif
+    SB_STAMP_EPI_CTX
     conv_epilogue<CT, PT, RPW, 2>(ec, acc, T0, tx0, ty0, wave, j, h);
-#ifdef CRFP_LAB
-    if (a.stamps) {
-        const long long ti = __builtin_amdgcn_s_memtime();      // epilogue issued (stores in flight)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) {
-            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 2] = te1;   // overwrites phase C (unused here)
-            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 3] = te2;   // overwrites phase D
-            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 7] = ti;
-            a.stamps[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + 6] = __builtin_amdgcn_s_memtime();
-        }
-    }
-#endif
+    SB_STAMP_EPI_DONE
 }
 
 template <int CT, int RPW, int NP>
@@ -941,6 +950,31 @@ __global__ __launch_bounds__(256, NP == 2 && CT == 1 && RPW == 1 ? 3 : 2) void c
 constexpr int S8_TH = 8;
 constexpr int S8_WPC = 9 * 3 * 64;
 
+// diagnostic timeline of conv3x3_split8_kernel (CRFP_STAMP_PTR / CRFP_STAMP_NAME, tools/stamp_conv8.py): absolute s_memtime of wave 0 at kernel
+// entry, first tile in LDS, end of chunk 0's MFMAs, end of the MFMA loop, epilogue stores issued, stores acknowledged.  Lab library only.
+#ifdef CRFP_LAB
+#define S8_STAMP_BEGIN long long ts[6] = {0, 0, 0, 0, 0, 0}; if (a.stamps) ts[0] = __builtin_amdgcn_s_memtime();
+#define S8_STAMP(I) if (a.stamps) ts[I] = __builtin_amdgcn_s_memtime();
+#define S8_STAMP_ACC(I) if (a.stamps) { asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[0][1][15])); ts[I] = __builtin_amdgcn_s_memtime(); }
+#define S8_STAMP_END                                                                                      \
+    if (a.stamps) {                                                                                       \
+        ts[4] = __builtin_amdgcn_s_memtime();                                                             \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                  \
+        ts[5] = __builtin_amdgcn_s_memtime();                                                             \
+        if (tid == 0) {                                                                                   \
+            long long* o = a.stamps + (long long)blockIdx.x * 8;                                          \
+            for (int q = 0; q < 6; ++q) o[q] = ts[q];                                                     \
+            o[6] = __builtin_amdgcn_s_getreg(6 << 11 | 4 << 6 | 20);   /* HW_REG_HW_ID (id 4), offset 0? -> unused placeholder */ \
+            o[7] = 1;                                                                                     \
+        }                                                                                                 \
+    }
+#else
+#define S8_STAMP_BEGIN
+#define S8_STAMP(I)
+#define S8_STAMP_ACC(I)
+#define S8_STAMP_END
+#endif
+
 // NW = 8: two workgroups per CU (the shipped form).  NW = 16 (A/B builds, -DCRFP_S8_NW=16): ONE 16-row workgroup per CU -- the 27.6 KB
 // weight stage is loaded once per CU instead of twice and the halo is 18 / 16 instead of 10 / 8 rows: 104 instead of 139 KB of ingest
 // per CU and chunk (profiles/r03_conv_split8_timeline.txt: the prologue is ingest-bound).
@@ -964,15 +998,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int n = blockIdx.z;
     const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
     const int H = a.H, W = a.W;
-#ifdef CRFP_LAB
-    // diagnostic timeline (CRFP_STAMP_PTR / CRFP_STAMP_NAME, tools/stamp_conv8.py): absolute s_memtime of wave 0 at kernel entry,
-    // first tile in LDS, end of chunk 0's MFMAs, end of the MFMA loop, epilogue stores issued, stores acknowledged
-    long long ts[6] = {0, 0, 0, 0, 0, 0};
-    if (a.stamps) ts[0] = __builtin_amdgcn_s_memtime();
-#define S8_STAMP(I) if (a.stamps) ts[I] = __builtin_amdgcn_s_memtime();
-#else
-#define S8_STAMP(I)
-#endif
+    S8_STAMP_BEGIN
 
     int cgy[S8_NIN], cgx[S8_NIN];
     bool sval[S8_NIN];
@@ -1094,13 +1120,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
                 acc[0][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wA, b0, acc[0][pt], 0, 0, 0);
             }
         }
-#ifdef CRFP_LAB
-        if (a.stamps && ch == 0) { asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[0][1][15])); ts[2] = __builtin_amdgcn_s_memtime(); }
-#endif
+        if (ch == 0) { S8_STAMP_ACC(2) }
     }
-#ifdef CRFP_LAB
-    if (a.stamps) { asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[0][1][15])); ts[3] = __builtin_amdgcn_s_memtime(); }
-#endif
+    S8_STAMP_ACC(3)
 #undef CRFP_S8_ISSUE
 #undef CRFP_QDESC
 #pragma unroll
@@ -1109,190 +1131,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
         for (int e = 0; e < 16; ++e) acc[0][pt][e] *= (1.0f / F16_RES_SCALE);
     const EpiCtx ec = epi_ctx(a, n);
     conv_epilogue<1, 2, 1, 2>(ec, acc, T0, tx0, ty0, wave, j, h);
-#ifdef CRFP_LAB
-    if (a.stamps) {
-        ts[4] = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ts[5] = __builtin_amdgcn_s_memtime();
-        if (tid == 0) {
-            long long* o = a.stamps + (long long)blockIdx.x * 8;
-            for (int q = 0; q < 6; ++q) o[q] = ts[q];
-            o[6] = __builtin_amdgcn_s_getreg(6 << 11 | 4 << 6 | 20);   // HW_REG_HW_ID (id 4), offset 0? -> unused placeholder
-            o[7] = 1;
-        }
-    }
-#endif
-#undef S8_STAMP
+    S8_STAMP_END
 }
-
-#ifdef CRFP_LAB
-// ---------------------------------------------------------------- f16x3s, persistent over 4-row tiles (lab: lost its A/B)
-// Measured, same box, bit-identical output: 32 -> 32 convs 25.0 -> 27.3 us, 64 -> 32 37.2 -> 41.2, block0 43.7 -> 48.8, the pixel-shuffle
-// heads 41.2 -> 40.1; clip 10.74 -> 11.06 ms.  What the cross-tile prefetch hides is less than what half-height tiles cost: 5 instead of
-// 3.5 ds_read_b128 per MFMA triple (one 32-pixel tile per wave re-reads the A fragments twice as often), the 27.6 KB weight stage per
-// 4 rows instead of per 8, a 6 / 4 instead of 10 / 8 halo.  CRFP_S8P=1 selects it in the lab library.
-// Same arithmetic, K order and accumulation order as conv3x3_split8_kernel (so the same bits), other work split: a tile is 4 rows x 64
-// pixels (wave w: row w / 2, pixel half w & 1 -- ONE 32-pixel MFMA tile per wave, 16 accumulator registers), a 360 x 640 map is 900 tiles,
-// and the 512 resident workgroups walk them with the chunk prefetch running ACROSS the tile boundary: the first chunk of tile i + 1 is in
-// flight during the last MFMAs and the stores of tile i, so a workgroup's second tile pays neither the load latency of a prologue nor
-// the store phase of the first one (profiles/r03_conv_split8_timeline.txt: 28 % + 20 % of a one-tile workgroup's lifetime).  Barriers
-// order LDS only (s_waitcnt lgkmcnt(0) + s_barrier): __syncthreads() would wait for the previous tile's stores to be acknowledged.
-constexpr int S8P_TH = 4, S8P_LH = S8P_TH + 2, S8P_NEL = S8P_LH * LW, S8P_NT = 512;
-constexpr int S8P_NIN = (S8P_NEL + S8P_NT - 1) / S8P_NT, S8P_NWS = (S8_WPC + S8P_NT - 1) / S8P_NT;
-__device__ __forceinline__ void s8p_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__global__ __launch_bounds__(S8P_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv3x3_split8p_kernel(const ConvArgs a, int items) {
-    __shared__ bf16x8 tile[2][2][S8P_NEL];       // [split part][quad pair][halo pixel]   25.3 KB
-    __shared__ bf16x8 wlds[S8_WPC];              // [(tap, image A/B/C)][lane]            27.6 KB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int row = wave >> 1, half = wave & 1;
-    const int tiles_x = (a.W + TW - 1) / TW;
-    const int ngrp = a.ctiles;
-    const int n = blockIdx.z;
-    const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
-    const int H = a.H, W = a.W;
-    const int G = gridDim.x;                     // a multiple of 8: every item of a workgroup lies in its XCD's band
-    int item = blockIdx.x;
-    if (item >= items) return;
-    const int nchunks = a.kq >> 2;
-    const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(a.wsplit_sa);
-    const EpiCtx ec = epi_ctx(a, n);
-
-    // load side: the (tile, chunk) whose global loads are in flight
-    int ltx0, lty0, lT0;
-    int cgy[S8P_NIN], cgx[S8P_NIN];
-    bool sval[S8P_NIN];
-    f32x4 rq0[S8P_NIN], rq1[S8P_NIN], rq2[S8P_NIN], rq3[S8P_NIN];
-    bf16x8 rws[S8P_NWS];
-    int qm0 = 0, qm1 = 0, qm2 = 0, qm3 = 0;
-#define S8P_SET_TILE(IT)                                                                                  \
-    {                                                                                                     \
-        const int bw_ = xcd_band_tile((IT), items);                                                       \
-        const int bt_ = bw_ / ngrp;                                                                       \
-        ltx0 = (bt_ % tiles_x) * TW; lty0 = (bt_ / tiles_x) * S8P_TH; lT0 = bw_ - bt_ * ngrp;             \
-        _Pragma("unroll") for (int t = 0; t < S8P_NIN; ++t) {                                             \
-            const int idx = min(tid + S8P_NT * t, S8P_NEL - 1);                                           \
-            const int r = idx / LW, c = idx - r * LW;                                                     \
-            const int gy = lty0 + r - 1, gx = ltx0 + c - 1;                                               \
-            sval[t] = tid + S8P_NT * t < S8P_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;               \
-            cgy[t] = min(max(gy, 0), H - 1);                                                              \
-            cgx[t] = min(max(gx, 0), W - 1);                                                              \
-        }                                                                                                 \
-    }
-#define S8P_QDESC(QB_, QRS, QCS, QM, QI, CH)                                                              \
-    const float* QB_; int QRS, QCS;                                                                       \
-    {                                                                                                     \
-        const QuadDesc d_ = a.qd[4 * (CH) + (QI)];                                                        \
-        QB_ = d_.base + (long long)ns * d_.bstride; QRS = d_.rs; QCS = d_.cs; QM = d_.mask;                \
-    }
-#define S8P_ISSUE(CH)                                                                                     \
-    {                                                                                                     \
-        S8P_QDESC(qb0, qrs0, qcs0, qm0, 0, CH) S8P_QDESC(qb1, qrs1, qcs1, qm1, 1, CH)                     \
-        S8P_QDESC(qb2, qrs2, qcs2, qm2, 2, CH) S8P_QDESC(qb3, qrs3, qcs3, qm3, 3, CH)                     \
-        _Pragma("unroll") for (int t = 0; t < S8P_NIN; ++t) {                                             \
-            rq0[t] = CRFP_LDACT(f32x4, qb0 + cgy[t] * qrs0 + cgx[t] * qcs0);                \
-            rq1[t] = CRFP_LDACT(f32x4, qb1 + cgy[t] * qrs1 + cgx[t] * qcs1);                \
-            rq2[t] = CRFP_LDACT(f32x4, qb2 + cgy[t] * qrs2 + cgx[t] * qcs2);                \
-            rq3[t] = CRFP_LDACT(f32x4, qb3 + cgy[t] * qrs3 + cgx[t] * qcs3);                \
-        }                                                                                                 \
-        _Pragma("unroll") for (int k = 0; k < S8P_NWS; ++k) {                                             \
-            const int idx = min(tid + S8P_NT * k, S8_WPC - 1);                                            \
-            rws[k] = wp[((long long)lT0 * nchunks + (CH)) * S8_WPC + idx];                                \
-        }                                                                                                 \
-    }
-
-    S8P_SET_TILE(item)
-    S8P_ISSUE(0)
-    for (;;) {
-        // compute side: this tile
-        const int tx0 = ltx0, ty0 = lty0, T0 = lT0;
-        f32x16 acc[1][1];
-        {   // the accumulator starts at 2^11 * bias
-            const float4* __restrict__ bp = reinterpret_cast<const float4*>(a.bpk);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 bq = bp[T0 * 8 + 2 * g + h];
-                acc[0][0][4 * g + 0] = bq.x * F16_RES_SCALE; acc[0][0][4 * g + 1] = bq.y * F16_RES_SCALE;
-                acc[0][0][4 * g + 2] = bq.z * F16_RES_SCALE; acc[0][0][4 * g + 3] = bq.w * F16_RES_SCALE;
-            }
-        }
-        const int next = item + G;
-        for (int ch = 0; ch < nchunks; ++ch) {
-            const int m0 = qm0, m1 = qm1, m2 = qm2, m3 = qm3;
-            s8p_lds_barrier();                   // every wave is done reading the previous stage
-            if (m0 & 16) {   // SRC_S3 chunk (wave-uniform): already split by its producer -- copy, zero outside the image
-#pragma unroll
-                for (int t = 0; t < S8P_NIN; ++t) {
-                    const int idx = tid + S8P_NT * t;
-                    if (idx < S8P_NEL) {
-                        const f32x4 z = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                        tile[0][0][idx] = __builtin_bit_cast(bf16x8, sval[t] ? rq0[t] : z);
-                        tile[0][1][idx] = __builtin_bit_cast(bf16x8, sval[t] ? rq1[t] : z);
-                        tile[1][0][idx] = __builtin_bit_cast(bf16x8, sval[t] ? rq2[t] : z);
-                        tile[1][1][idx] = __builtin_bit_cast(bf16x8, sval[t] ? rq3[t] : z);
-                    }
-                }
-            } else if ((m0 & m1 & m2 & m3) == 15) {
-#pragma unroll
-                for (int t = 0; t < S8P_NIN; ++t) {
-                    const int idx = tid + S8P_NT * t;
-                    if (idx < S8P_NEL) {
-                        const float sc = sval[t] ? F16_RES_SCALE : 0.0f;
-                        const unsigned km = sval[t] ? 0xffffffffu : 0u;
-                        bf16x8 pa, pb;
-                        split_f16x8_fast(rq0[t], rq1[t], sc, km, pa, pb);
-                        tile[0][0][idx] = pa; tile[1][0][idx] = pb;
-                        split_f16x8_fast(rq2[t], rq3[t], sc, km, pa, pb);
-                        tile[0][1][idx] = pa; tile[1][1][idx] = pb;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < S8P_NIN; ++t) {
-                    const int idx = tid + S8P_NT * t;
-                    if (idx < S8P_NEL) {
-                        bf16x8 pp[2];
-                        split_parts<2>(mask_quad(rq0[t], sval[t] ? m0 : 0), mask_quad(rq1[t], sval[t] ? m1 : 0), pp);
-                        tile[0][0][idx] = pp[0]; tile[1][0][idx] = pp[1];
-                        split_parts<2>(mask_quad(rq2[t], sval[t] ? m2 : 0), mask_quad(rq3[t], sval[t] ? m3 : 0), pp);
-                        tile[0][1][idx] = pp[0]; tile[1][1][idx] = pp[1];
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < S8P_NWS; ++k) {
-                const int idx = tid + S8P_NT * k;
-                if (idx < S8_WPC) wlds[idx] = rws[k];
-            }
-            s8p_lds_barrier();
-            if (ch + 1 < nchunks) S8P_ISSUE(ch + 1)
-            else if (next < items) { S8P_SET_TILE(next) S8P_ISSUE(0) }   // the next tile's first chunk: in flight during these MFMAs and the stores below
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int ky = tap / 3, kx = tap - 3 * ky;
-                const f16x8 wA = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 0) * 64 + lane]);
-                const f16x8 wB = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 1) * 64 + lane]);
-                const f16x8 wC = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 2) * 64 + lane]);
-                const int pix = (row + ky) * LW + half * 32 + j + kx;
-                const f16x8 b0 = __builtin_bit_cast(f16x8, tile[0][h][pix]);
-                const f16x8 b1 = __builtin_bit_cast(f16x8, tile[1][h][pix]);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wB, b0, acc[0][0], 0, 0, 0);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wC, b1, acc[0][0], 0, 0, 0);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wA, b0, acc[0][0], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[0][0][e] *= (1.0f / F16_RES_SCALE);
-        conv_epilogue<1, 1, 1, 2>(ec, acc, T0, tx0 + half * 32, ty0, row, j, h);
-        if (next >= items) break;
-        item = next;
-    }
-#undef S8P_ISSUE
-#undef S8P_QDESC
-#undef S8P_SET_TILE
-}
-#endif  // CRFP_LAB
 
 #endif  // !CRFP_ACT_BF16
 
@@ -1320,6 +1160,105 @@ __device__ __forceinline__ cu32x2 quad_words(cu32x2 r, int m, bool valid) {
     return cu32x2{r.x & k0, r.y & k1};
 }
 
+// ---------------------------------------------------------------- chunk staging shared by the 8-wave and the pair kernel
+// Both are: their tile decode | halo_coords | acc_from_bias | per 16-channel chunk { ChunkQuads::fetch + the load batch + issue_weights into
+// registers; stage_bf16 + stage_weights into LDS; their own MFMA tap loop } | conv_epilogue.  Templates on the kernel's thread count NT,
+// halo size NEL and halo slots per thread NIN, so each kernel keeps its own constants.
+// The other main loops (conv3x3_split_body, conv3x3_split8_kernel, conv3x3_bf16_kernel) carry the same pieces as their own text: written
+// with these helpers they computed the same bits at the same registers, LDS and occupancy, but hipcc scheduled them differently and
+// their launch sites came out 0.3 - 1.5 % slower (profiles/r13_conv_stage_ab.txt), so their instruction streams stay as they were.
+
+// halo pixels of this thread (rows of LW pixels, origin (ty0 - 1, tx0 - 1)): clamped coordinates -- every load is unconditional and in
+// range; pixels outside the image (sval false) are zeroed when the registers are converted, not when they are loaded
+template <int NT, int NEL, int NIN>
+__device__ __forceinline__ void halo_coords(int tid, int ty0, int tx0, int H, int W, int (&cgy)[NIN], int (&cgx)[NIN], bool (&sval)[NIN]) {
+#pragma unroll
+    for (int t = 0; t < NIN; ++t) {
+        const int idx = min(tid + NT * t, NEL - 1);
+        const int r = idx / LW, c = idx - r * LW;
+        const int gy = ty0 + r - 1, gx = tx0 + c - 1;
+        sval[t] = tid + NT * t < NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        cgy[t] = min(max(gy, 0), H - 1);
+        cgx[t] = min(max(gx, 0), W - 1);
+    }
+}
+
+// Branch-free issue: each K-quad of the chunk is described by wave-uniform (base, row stride, column
+// stride, component mask); all source kinds share one load form.  Nothing between issue and the LDS
+// write touches a loaded register (a use, a zero-init or a copy forces s_waitcnt and serialises the
+// prefetch behind memory latency -- measured: 5.7k cycles per issue with conditional loads).
+// The chunk's weights ride in the same prefetch batch: no global load (vmcnt is in-order!) may sit
+// inside the MFMA loop, or every tap would wait for the whole input prefetch to land.
+struct ChunkQuads {
+    const float* base[4];
+    int rs[4], cs[4], mask[4];
+    __device__ __forceinline__ void fetch(const ConvArgs& a, int ns, int ch) {   // the 4 quad descriptors of chunk ch, source item ns
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const QuadDesc d = a.qd[4 * ch + q];
+            base[q] = d.base + (long long)ns * d.bstride; rs[q] = d.rs; cs[q] = d.cs; mask[q] = d.mask;
+        }
+    }
+};
+// the NV weight vectors at wp (one chunk of one cout tile, or consecutive ones), index clamped: always a valid load
+template <int NT, int NV, int NWS>
+__device__ __forceinline__ void issue_weights(bf16x8 (&rws)[NWS], const bf16x8* __restrict__ wp, int tid) {
+#pragma unroll
+    for (int k = 0; k < NWS; ++k) rws[k] = wp[min(tid + NT * k, NV - 1)];
+}
+template <int NT, int NV, int NWS>
+__device__ __forceinline__ void stage_weights(bf16x8* wlds, const bf16x8 (&rws)[NWS], int tid) {
+#pragma unroll
+    for (int k = 0; k < NWS; ++k) {
+        const int idx = tid + NT * k;
+        if (idx < NV) wlds[idx] = rws[k];
+    }
+}
+
+// the PT accumulators of cout tile T start at the bias: its loads are the first of the kernel and long landed when the MFMAs begin
+template <int PT>
+__device__ __forceinline__ void acc_from_bias(f32x16 (&acc)[PT], const float* bpk, int T, int h) {
+    const float4* __restrict__ bp = reinterpret_cast<const float4*>(bpk);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 bq = bp[T * 8 + 2 * g + h];
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) {
+            acc[pt][4 * g + 0] = bq.x; acc[pt][4 * g + 1] = bq.y;
+            acc[pt][4 * g + 2] = bq.z; acc[pt][4 * g + 3] = bq.w;
+        }
+    }
+}
+
+// registers -> the bf16 halo image in LDS ([quad pair][halo pixel], 8 bf16 = 16 B each): a plain copy where the chunk holds 16 real bf16
+// channels (wave-uniform), quad_words otherwise; zero outside the image
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+template <int NT, int NEL, int NIN>
+__device__ __forceinline__ void stage_bf16(u32x4_t (&tile)[2][NEL], const cu32x2 (&rq)[4][NIN], const int (&m)[4], const bool (&sval)[NIN], int tid) {
+    if ((m[0] & m[1] & m[2] & m[3]) == 15 && !((m[0] | m[1] | m[2] | m[3]) & 32)) {
+#pragma unroll
+        for (int t = 0; t < NIN; ++t) {
+            const int idx = tid + NT * t;
+            if (idx < NEL) {
+                const unsigned km = sval[t] ? 0xffffffffu : 0u;
+                tile[0][idx] = u32x4_t{rq[0][t].x & km, rq[0][t].y & km, rq[1][t].x & km, rq[1][t].y & km};
+                tile[1][idx] = u32x4_t{rq[2][t].x & km, rq[2][t].y & km, rq[3][t].x & km, rq[3][t].y & km};
+            }
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < NIN; ++t) {
+            const int idx = tid + NT * t;
+            if (idx < NEL) {
+                const cu32x2 w0 = quad_words(rq[0][t], m[0], sval[t]), w1 = quad_words(rq[1][t], m[1], sval[t]);
+                const cu32x2 w2 = quad_words(rq[2][t], m[2], sval[t]), w3 = quad_words(rq[3][t], m[3], sval[t]);
+                tile[0][idx] = u32x4_t{w0.x, w0.y, w1.x, w1.y};
+                tile[1][idx] = u32x4_t{w2.x, w2.y, w3.x, w3.y};
+            }
+        }
+    }
+}
+
 #ifndef CRFP_BF16_LB
 #define CRFP_BF16_LB 5   // workgroups per CU the register allocation aims at.  Round 4, same box, 4-clip lock-step batch: 4 -> 5 takes the kernel
                          // sum per clip 5.67 -> 5.60 ms (32 -> 32 convs 9.4 -> 8.9 us), one-clip calls unchanged; 6 spills (40 B) and loses 6 %
@@ -1331,7 +1270,6 @@ __global__ __launch_bounds__(256, RPW == 1 ? CRFP_BF16_LB : 3) void conv3x3_bf16
     constexpr int NIN = (NEL + 255) / 256;       // halo pixels per thread; each carries the chunk's 4 quads
     constexpr int WPC = 9 * 64;                  // weight vectors per (cout tile, chunk)
     constexpr int NWS = (WPC + 255) / 256;
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     __shared__ u32x4_t tile[2][NEL];             // [quad pair][halo pixel]: 8 bf16 = 16 B
     __shared__ bf16x8 wlds[WPC];                 // [tap][lane]: this chunk's A fragments
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1466,7 +1404,6 @@ constexpr int B8_NT = 512, B8_TH = 8, B8_LH = B8_TH + 2, B8_NEL = B8_LH * LW, B8
 constexpr int B8_WPC = 9 * 64, B8_NWS = (2 * B8_WPC + B8_NT - 1) / B8_NT;
 
 __global__ __launch_bounds__(B8_NT, 2) void conv3x3_bf16x8_kernel(const ConvArgs a) {
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     __shared__ u32x4_t tile[2][2][B8_NEL];       // [chunk of the stage][quad pair][halo pixel]: 8 bf16 = 16 B      42.2 KB
     __shared__ bf16x8 wlds[2 * B8_WPC];          // [chunk][tap][lane]                                             18.4 KB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1479,51 +1416,28 @@ __global__ __launch_bounds__(B8_NT, 2) void conv3x3_bf16x8_kernel(const ConvArgs
     const int T0 = bwork - btile * ngrp;
     const int n = blockIdx.z;
     const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
-    const int H = a.H, W = a.W;
 
     int cgy[B8_NIN], cgx[B8_NIN];
     bool sval[B8_NIN];
-#pragma unroll
-    for (int t = 0; t < B8_NIN; ++t) {
-        const int idx = min(tid + B8_NT * t, B8_NEL - 1);
-        const int r = idx / LW, c = idx - r * LW;
-        const int gy = ty0 + r - 1, gx = tx0 + c - 1;
-        sval[t] = tid + B8_NT * t < B8_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        cgy[t] = min(max(gy, 0), H - 1);
-        cgx[t] = min(max(gx, 0), W - 1);
-    }
+    halo_coords<B8_NT, B8_NEL, B8_NIN>(tid, ty0, tx0, a.H, a.W, cgy, cgx, sval);
 
     f32x16 acc[1][2];
-    {   // accumulators start at the bias
-        const float4* __restrict__ bp = reinterpret_cast<const float4*>(a.bpk);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 bq = bp[T0 * 8 + 2 * g + h];
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt) {
-                acc[0][pt][4 * g + 0] = bq.x; acc[0][pt][4 * g + 1] = bq.y;
-                acc[0][pt][4 * g + 2] = bq.z; acc[0][pt][4 * g + 3] = bq.w;
-            }
-        }
-    }
+    acc_from_bias<2>(acc[0], a.bpk, T0, h);
 
     const int nchunks = a.kq >> 2, nstages = (nchunks + 1) >> 1;
     const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(a.wsplit16);
     cu32x2 rq[2][4][B8_NIN];   // [chunk of the stage][quad][halo slot]
-    int qm[2][4];
+    ChunkQuads cq[2];
     bf16x8 rws[B8_NWS];
-    // loads of stage ST: its one or two chunks' quads (per-quad descriptors) and weight fragments (consecutive in the packed image)
+    // loads of stage ST: its one or two chunks' quads, quad by quad, and weight fragments (consecutive in the packed image; the chunk index
+    // is clamped: an odd chunk count repeats the last one, unused)
 #define CRFP_B8_ISSUE(ST)                                                                                 \
     {                                                                                                     \
         _Pragma("unroll") for (int c2 = 0; c2 < 2; ++c2) {                                                \
-            const int ch_ = min(2 * (ST) + c2, nchunks - 1);                                              \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                               \
-                const QuadDesc d_ = a.qd[4 * ch_ + q];                                                    \
-                const float* qb_ = d_.base + (long long)ns * d_.bstride;                                   \
-                qm[c2][q] = d_.mask;                                                                      \
+            cq[c2].fetch(a, ns, min(2 * (ST) + c2, nchunks - 1));                                         \
+            _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                 \
                 _Pragma("unroll") for (int t = 0; t < B8_NIN; ++t)                                        \
-                    rq[c2][q][t] = CRFP_LDACT(cu32x2, qb_ + cgy[t] * d_.rs + cgx[t] * d_.cs); \
-            }                                                                                             \
+                    rq[c2][q][t] = CRFP_LDACT(cu32x2, cq[c2].base[q] + cgy[t] * cq[c2].rs[q] + cgx[t] * cq[c2].cs[q]); \
         }                                                                                                 \
         _Pragma("unroll") for (int k = 0; k < B8_NWS; ++k) {                                              \
             const int idx = min(tid + B8_NT * k, 2 * B8_WPC - 1);                                         \
@@ -1537,36 +1451,8 @@ __global__ __launch_bounds__(B8_NT, 2) void conv3x3_bf16x8_kernel(const ConvArgs
         const bool two = 2 * st + 1 < nchunks;   // the last stage of an odd chunk count holds one chunk
         __syncthreads();
 #pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2) {
-            const int m0 = qm[c2][0], m1 = qm[c2][1], m2 = qm[c2][2], m3 = qm[c2][3];
-            if ((m0 & m1 & m2 & m3) == 15 && !((m0 | m1 | m2 | m3) & 32)) {
-#pragma unroll
-                for (int t = 0; t < B8_NIN; ++t) {
-                    const int idx = tid + B8_NT * t;
-                    if (idx < B8_NEL) {
-                        const unsigned km = sval[t] ? 0xffffffffu : 0u;
-                        tile[c2][0][idx] = u32x4_t{rq[c2][0][t].x & km, rq[c2][0][t].y & km, rq[c2][1][t].x & km, rq[c2][1][t].y & km};
-                        tile[c2][1][idx] = u32x4_t{rq[c2][2][t].x & km, rq[c2][2][t].y & km, rq[c2][3][t].x & km, rq[c2][3][t].y & km};
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < B8_NIN; ++t) {
-                    const int idx = tid + B8_NT * t;
-                    if (idx < B8_NEL) {
-                        const cu32x2 w0 = quad_words(rq[c2][0][t], m0, sval[t]), w1 = quad_words(rq[c2][1][t], m1, sval[t]);
-                        const cu32x2 w2 = quad_words(rq[c2][2][t], m2, sval[t]), w3 = quad_words(rq[c2][3][t], m3, sval[t]);
-                        tile[c2][0][idx] = u32x4_t{w0.x, w0.y, w1.x, w1.y};
-                        tile[c2][1][idx] = u32x4_t{w2.x, w2.y, w3.x, w3.y};
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < B8_NWS; ++k) {
-            const int idx = tid + B8_NT * k;
-            if (idx < 2 * B8_WPC) wlds[idx] = rws[k];
-        }
+        for (int c2 = 0; c2 < 2; ++c2) stage_bf16<B8_NT>(tile[c2], rq[c2], cq[c2].mask, sval, tid);
+        stage_weights<B8_NT, 2 * B8_WPC>(wlds, rws, tid);
         __syncthreads();
         if (st + 1 < nstages) CRFP_B8_ISSUE(st + 1)
 #pragma unroll
@@ -1618,7 +1504,6 @@ struct PairB {          // what conv B adds to conv A's plan: its weights, bias,
 };
 
 __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvArgs a, const PairB b) {
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     __shared__ u32x4_t tileA[2][P2_NEL];         // conv A: [quad pair][input halo pixel] of the current chunk; then conv B's weights
     __shared__ u32x4_t mid[2][2][P2_MEL];        // conv A's output = conv B's input: [chunk][quad pair][pixel], 8 bf16 each
     __shared__ bf16x8 wlds[P2_WPC];              // conv A: [tap][lane] of the current chunk
@@ -1632,15 +1517,8 @@ __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvA
 
     int cgy[P2_NIN], cgx[P2_NIN];
     bool sval[P2_NIN];
-#pragma unroll
-    for (int t = 0; t < P2_NIN; ++t) {
-        const int idx = min(tid + P2_NT * t, P2_NEL - 1);
-        const int r = idx / P2_LW, c = idx - r * P2_LW;
-        const int gy = ty0 + r - 2, gx = tx0 + c - 2;
-        sval[t] = tid + P2_NT * t < P2_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        cgy[t] = min(max(gy, 0), H - 1);
-        cgx[t] = min(max(gx, 0), W - 1);
-    }
+    static_assert(P2_LW == LW, "halo_coords walks rows of LW pixels");
+    halo_coords<P2_NT, P2_NEL, P2_NIN>(tid, ty0 - 1, tx0 - 1, H, W, cgy, cgx, sval);   // conv A's input: two halo rings
     // the two zero columns behind each intermediate row (read by conv B's taps of the two discarded output columns)
     if (tid < 4 * P2_IH * 2) {
         const int pl = tid / (P2_IH * 2), rc = tid - pl * (P2_IH * 2);
@@ -1650,56 +1528,34 @@ __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvA
     // conv A: wave w owns the 32-pixel tiles w, w + 8 (and w + 16 for w < 4) of the 10 x 64 region; tile t = row t >> 1, half t & 1
     const int ntA = wave < 4 ? 3 : 2;
     f32x16 accA[3];
-    {
-        const float4* __restrict__ bp = reinterpret_cast<const float4*>(a.bpk);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 bq = bp[2 * g + h];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                accA[k][4 * g + 0] = bq.x; accA[k][4 * g + 1] = bq.y; accA[k][4 * g + 2] = bq.z; accA[k][4 * g + 3] = bq.w;
-            }
-        }
-    }
+    acc_from_bias<3>(accA, a.bpk, 0, h);
     const int nchunks = a.kq >> 2;
     const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(a.wsplit16);
-    cu32x2 rq0[P2_NIN], rq1[P2_NIN], rq2[P2_NIN], rq3[P2_NIN];
+    cu32x2 rq[4][P2_NIN];
     bf16x8 rws[P2_NWS];
-    const float* qb0; const float* qb1; const float* qb2; const float* qb3;
-    int qrs0, qrs1, qrs2, qrs3, qcs0, qcs1, qcs2, qcs3, qm0 = 0, qm1 = 0, qm2 = 0, qm3 = 0;
-#define CRFP_QDESC(QB_, QRS, QCS, QM, QI, CH)                                                             \
-    {                                                                                                     \
-        const QuadDesc d_ = a.qd[4 * (CH) + (QI)];                                                        \
-        QB_ = d_.base + (long long)n * d_.bstride; QRS = d_.rs; QCS = d_.cs; QM = d_.mask;                \
-    }
+    ChunkQuads cq;
 #define CRFP_P2_ISSUE(CH)                                                                                 \
     {                                                                                                     \
-        CRFP_QDESC(qb0, qrs0, qcs0, qm0, 0, CH) CRFP_QDESC(qb1, qrs1, qcs1, qm1, 1, CH)                   \
-        CRFP_QDESC(qb2, qrs2, qcs2, qm2, 2, CH) CRFP_QDESC(qb3, qrs3, qcs3, qm3, 3, CH)                   \
-        _Pragma("unroll") for (int t = 0; t < P2_NIN; ++t) {                                              \
-            rq0[t] = CRFP_LDACT(cu32x2, qb0 + cgy[t] * qrs0 + cgx[t] * qcs0);               \
-            rq1[t] = CRFP_LDACT(cu32x2, qb1 + cgy[t] * qrs1 + cgx[t] * qcs1);               \
-            rq2[t] = CRFP_LDACT(cu32x2, qb2 + cgy[t] * qrs2 + cgx[t] * qcs2);               \
-            rq3[t] = CRFP_LDACT(cu32x2, qb3 + cgy[t] * qrs3 + cgx[t] * qcs3);               \
-        }                                                                                                 \
-        _Pragma("unroll") for (int k = 0; k < P2_NWS; ++k) {                                              \
-            const int idx = min(tid + P2_NT * k, P2_WPC - 1);                                             \
-            rws[k] = wp[(long long)(CH) * P2_WPC + idx];                                                  \
-        }                                                                                                 \
+        cq.fetch(a, n, CH);                                                                               \
+        _Pragma("unroll") for (int t = 0; t < P2_NIN; ++t)                                                \
+            _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                 \
+                rq[q][t] = CRFP_LDACT(cu32x2, cq.base[q] + cgy[t] * cq.rs[q] + cgx[t] * cq.cs[q]);        \
+        issue_weights<P2_NT, P2_WPC>(rws, wp + (long long)(CH) * P2_WPC, tid);                            \
     }
     CRFP_P2_ISSUE(0)
     bf16x8 rwb[P2_NWB];   // conv B's weights (both chunks), fetched under conv A's last chunk
     for (int ch = 0; ch < nchunks; ++ch) {
-        const int m0 = qm0, m1 = qm1, m2 = qm2, m3 = qm3;
         __syncthreads();  // every wave finished reading the previous chunk
+        // stage_bf16's two forms, written out: through the helper this kernel takes 136 instead of 134 VGPRs (profiles/r13_conv_mfma_resources.md)
+        const int m0 = cq.mask[0], m1 = cq.mask[1], m2 = cq.mask[2], m3 = cq.mask[3];
         if ((m0 & m1 & m2 & m3) == 15 && !((m0 | m1 | m2 | m3) & 32)) {   // wave-uniform: 16 real bf16 channels -> plain copy
 #pragma unroll
             for (int t = 0; t < P2_NIN; ++t) {
                 const int idx = tid + P2_NT * t;
                 if (idx < P2_NEL) {
                     const unsigned km = sval[t] ? 0xffffffffu : 0u;
-                    tileA[0][idx] = u32x4_t{rq0[t].x & km, rq0[t].y & km, rq1[t].x & km, rq1[t].y & km};
-                    tileA[1][idx] = u32x4_t{rq2[t].x & km, rq2[t].y & km, rq3[t].x & km, rq3[t].y & km};
+                    tileA[0][idx] = u32x4_t{rq[0][t].x & km, rq[0][t].y & km, rq[1][t].x & km, rq[1][t].y & km};
+                    tileA[1][idx] = u32x4_t{rq[2][t].x & km, rq[2][t].y & km, rq[3][t].x & km, rq[3][t].y & km};
                 }
             }
         } else {
@@ -1707,25 +1563,20 @@ __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvA
             for (int t = 0; t < P2_NIN; ++t) {
                 const int idx = tid + P2_NT * t;
                 if (idx < P2_NEL) {
-                    const cu32x2 w0 = quad_words(rq0[t], m0, sval[t]), w1 = quad_words(rq1[t], m1, sval[t]);
-                    const cu32x2 w2 = quad_words(rq2[t], m2, sval[t]), w3 = quad_words(rq3[t], m3, sval[t]);
+                    const cu32x2 w0 = quad_words(rq[0][t], m0, sval[t]), w1 = quad_words(rq[1][t], m1, sval[t]);
+                    const cu32x2 w2 = quad_words(rq[2][t], m2, sval[t]), w3 = quad_words(rq[3][t], m3, sval[t]);
                     tileA[0][idx] = u32x4_t{w0.x, w0.y, w1.x, w1.y};
                     tileA[1][idx] = u32x4_t{w2.x, w2.y, w3.x, w3.y};
                 }
             }
         }
-#pragma unroll
-        for (int k = 0; k < P2_NWS; ++k) {
-            const int idx = tid + P2_NT * k;
-            if (idx < P2_WPC) wlds[idx] = rws[k];
-        }
+        stage_weights<P2_NT, P2_WPC>(wlds, rws, tid);
         __syncthreads();
         if (ch + 1 < nchunks) {
             CRFP_P2_ISSUE(ch + 1)
         } else {
             const bf16x8* __restrict__ wb = reinterpret_cast<const bf16x8*>(b.wsplit16);
-#pragma unroll
-            for (int k = 0; k < P2_NWB; ++k) rwb[k] = wb[min(tid + P2_NT * k, 2 * P2_WPC - 1)];
+            issue_weights<P2_NT, 2 * P2_WPC>(rwb, wb, tid);
         }
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -1742,7 +1593,6 @@ __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvA
         }
     }
 #undef CRFP_P2_ISSUE
-#undef CRFP_QDESC
     // conv A's epilogue into LDS: activation, zero outside the image, round to bf16 (what the two-kernel path stores), 8 bytes per
     // (cout quad, pixel): channel 8 g + 4 h + r is position 4 h + r of the 8-channel element (chunk g >> 1, quad pair g & 1)
     {
@@ -1769,23 +1619,9 @@ __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvA
     }
     __syncthreads();   // conv A's last reads of tileA / wlds are done (and `mid` is on its way)
     bf16x8* const wb_lds = reinterpret_cast<bf16x8*>(&tileA[0][0]);
-#pragma unroll
-    for (int k = 0; k < P2_NWB; ++k) {
-        const int idx = tid + P2_NT * k;
-        if (idx < 2 * P2_WPC) wb_lds[idx] = rwb[k];
-    }
+    stage_weights<P2_NT, 2 * P2_WPC>(wb_lds, rwb, tid);
     f32x16 acc[1][2];
-    {
-        const float4* __restrict__ bp = reinterpret_cast<const float4*>(b.bpk);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 bq = bp[2 * g + h];
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt) {
-                acc[0][pt][4 * g + 0] = bq.x; acc[0][pt][4 * g + 1] = bq.y; acc[0][pt][4 * g + 2] = bq.z; acc[0][pt][4 * g + 3] = bq.w;
-            }
-        }
-    }
+    acc_from_bias<2>(acc[0], b.bpk, 0, h);
     __syncthreads();
 #pragma unroll
     for (int c2 = 0; c2 < 2; ++c2)
@@ -1813,547 +1649,9 @@ __global__ __launch_bounds__(P2_NT, 2) void conv3x3_bf16_pair_kernel(const ConvA
 
 #endif  // CRFP_ACT_BF16
 
-#ifdef CRFP_LAB   // experiments that lose to conv3x3_split_kernel<1,1,2>: built only into the lab library (make lab)
-// ---------------------------------------------------------------- software-pipelined persistent variant (f16x3)
-// One 512-thread workgroup per CU (two waves per SIMD) walks a strided list of 8x64 output tiles; wave = one output
-// row (two 32-pixel MFMA column tiles).  The work is a stream of items (tile, K-chunk).  LDS holds TWO items (halo tile
-// images 2 x 42 KB + weight fragments 2 x 18 KB); the registers hold two more in raw fp32 form.  While the MFMAs of
-// item s run out of LDS buffer s&1 the same waves
-//   * issue the global loads of item s+2 (a full item of latency budget; measured wait at use: 16 cycles),
-//   * split item s+1 (loaded during item s-1) into its two fp16 images and write them + its weights to buffer (s+1)&1,
-// slice by slice between the taps: the MFMA is asynchronous (32 cycles per 32x32x16), so VALU/LDS instructions
-// issued between two of them ride in its shadow.  The code between two barriers is branch-free (every thread
-// writes both of its halo slots; surplus threads hit a dummy slot), otherwise the scheduler cannot interleave.
-// One barrier per item; accumulators start at the bias; the epilogue runs when a tile's last chunk is done.
-// History: the first version (bf16x6, 4 waves) needed 6.9 k cycles per item against 3.5 k of MFMA -- LDS operand traffic
-// (0.75 ds_read_b128 per MFMA = 93 % of the LDS pipe) and in-order issue behind a full LDS queue with one wave per
-// SIMD; 8 waves fixed the issue stalls but bf16x6 stayed LDS-bound (7.9 k per item).  f16x3 moves 2/3 of the bytes.
-// Barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope release fence + s_barrier, and the release
-// makes hipcc wait for vmcnt(0): every wave then sits out the write-acknowledge latency of its epilogue stores (2.5-3.3 k
-// cycles per item measured) although nobody in the workgroup reads them.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr int PIPE_NW = 8, PIPE_NT = 64 * PIPE_NW;
-constexpr int PIPE_NEL = (PIPE_NW + 2) * LW;                   // 660 halo pixels
-constexpr int PIPE_WPC = 9 * 2 * 64;                           // weight vectors per (cout tile, chunk), f16x3
-constexpr int PIPE_NWS = (PIPE_WPC + PIPE_NT - 1) / PIPE_NT;   // 3 weight vectors per thread
-
-struct PipeRegs {
-    f32x4 q[4][2];        // [K-quad of the chunk][halo element of this thread]
-    bf16x8 w[PIPE_NWS];   // this thread's share of the chunk's 18 KB weight fragment image
-    int m[4];             // component masks of the 4 quads (wave-uniform)
-    bool ok[2];           // halo element inside the image
-};
-
-__device__ __forceinline__ void pipe_issue(PipeRegs& R, const ConvArgs& a, const bf16x8* __restrict__ wp, int n, int T0,
-                                           int nchunks, int ch, int tx0, int ty0, int tid) {
-    const int H = a.H, W = a.W;
-    const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
-    int cgy[2], cgx[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int idx = min(tid + PIPE_NT * t, PIPE_NEL - 1);
-        const int r = idx / LW, c = idx - r * LW;
-        const int gy = ty0 + r - 1, gx = tx0 + c - 1;
-        R.ok[t] = tid + PIPE_NT * t < PIPE_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        cgy[t] = min(max(gy, 0), H - 1);
-        cgx[t] = min(max(gx, 0), W - 1);
-    }
-#pragma unroll
-    for (int qi = 0; qi < 4; ++qi) {
-        const QuadDesc d = a.qd[4 * ch + qi];
-        const float* qb = d.base + (long long)ns * d.bstride;
-        R.m[qi] = d.mask;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) R.q[qi][t] = *reinterpret_cast<const f32x4*>(qb + cgy[t] * d.rs + cgx[t] * d.cs);
-    }
-#pragma unroll
-    for (int k = 0; k < PIPE_NWS; ++k)
-        R.w[k] = wp[(long long)(T0 * nchunks + ch) * PIPE_WPC + min(tid + PIPE_NT * k, PIPE_WPC - 1)];
-}
-
-// unit U in 0..3: halo element U>>1, quad pair U&1 -> two fp16x8 images.  Slot PIPE_NEL is a dummy.
-template <int U>
-__device__ __forceinline__ void pipe_split_unit(const PipeRegs& R, bf16x8 (*tl)[2][PIPE_NEL + 1], int tid) {
-    constexpr int t = U >> 1, pr = U & 1;
-    const int idx = min(tid + PIPE_NT * t, PIPE_NEL);
-    bf16x8 p0, p1;
-    split_f16x8(mask_quad(R.q[2 * pr][t], R.ok[t] ? R.m[2 * pr] : 0), mask_quad(R.q[2 * pr + 1][t], R.ok[t] ? R.m[2 * pr + 1] : 0),
-                p0, p1);
-    tl[0][pr][idx] = p0; tl[1][pr][idx] = p1;
-}
-
-template <int K>
-__device__ __forceinline__ void pipe_put_weight(const PipeRegs& R, bf16x8* wl, int tid) {
-    wl[min(tid + PIPE_NT * K, PIPE_WPC)] = R.w[K];   // slot PIPE_WPC is a dummy
-}
-
-__device__ __forceinline__ void pipe_tap(f32x16 (&acc)[1][2], f32x16 (&acl)[1][2], const bf16x8* wl,
-                                         const bf16x8 (*tl)[2][PIPE_NEL + 1], int tap, int wave, int lane) {
-    const int j = lane & 31, h = lane >> 5;
-    const int ky = tap / 3, kx = tap - 3 * ky;
-    bf16x8 wa[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) wa[p] = wl[(tap * 2 + p) * 64 + lane];
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt) {
-        const int pix = (wave + ky) * LW + pt * 32 + j + kx;
-        bf16x8 bq[2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) bq[p] = tl[p][h][pix];
-        split_mfma<2>(acc[0][pt], acl[0][pt], wa, bq);
-    }
-}
-
-__global__ __launch_bounds__(PIPE_NT, 1) void conv3x3_split_pipe_kernel(const ConvArgs a) {
-    __shared__ bf16x8 tile[2][2][2][PIPE_NEL + 1];   // [buffer][split part][quad pair][halo pixel (+1 dummy)]  84.6 KB
-    __shared__ bf16x8 wlds[2][PIPE_WPC + 1];         // [buffer][(tap, part)][lane] (+1 dummy)                   36.9 KB
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int tiles_x = (a.W + TW - 1) / TW, ntiles = tiles_x * ((a.H + PIPE_NW - 1) / PIPE_NW);
-    const int T0 = blockIdx.y, n = blockIdx.z;
-    const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
-    const int nchunks = a.kq >> 2;
-    const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int nitems = my_tiles * nchunks;
-    const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(a.wsplit16);
-    const EpiCtx ec = epi_ctx(a, n);
-    float4 bq4[4];   // this lane's bias quads: the accumulators of every tile start there
-#pragma unroll
-    for (int g = 0; g < 4; ++g) bq4[g] = reinterpret_cast<const float4*>(a.bpk)[T0 * 8 + 2 * g + h];
-
-    // issue cursor (items are issued two ahead of the one being multiplied)
-    int ik = 0, ich = 0;
-    PipeRegs RA, RB;
-#define CRFP_PIPE_ISSUE(R)                                                                                \
-    {                                                                                                     \
-        if (ik < my_tiles) {                                                                              \
-            const int t_ = blockIdx.x + ik * gridDim.x, ty_ = t_ / tiles_x, tx_ = t_ - ty_ * tiles_x;     \
-            pipe_issue(R, a, wp, n, T0, nchunks, ich, tx_ * TW, ty_ * PIPE_NW, tid);                      \
-        }                                                                                                 \
-        if (++ich == nchunks) { ich = 0; ++ik; }                                                          \
-    }
-#define CRFP_PIPE_ACC_INIT                                                                                \
-    _Pragma("unroll") for (int pt = 0; pt < 2; ++pt)                                                      \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                   \
-            acc[0][pt][4 * g + 0] = bq4[g].x; acc[0][pt][4 * g + 1] = bq4[g].y;                           \
-            acc[0][pt][4 * g + 2] = bq4[g].z; acc[0][pt][4 * g + 3] = bq4[g].w;                           \
-            acl[0][pt][4 * g + 0] = 0.0f; acl[0][pt][4 * g + 1] = 0.0f;                                   \
-            acl[0][pt][4 * g + 2] = 0.0f; acl[0][pt][4 * g + 3] = 0.0f;                                   \
-        }
-    CRFP_PIPE_ISSUE(RA)
-    CRFP_PIPE_ISSUE(RB)
-    // item 0 -> buffer 0
-    pipe_split_unit<0>(RA, tile[0], tid); pipe_split_unit<1>(RA, tile[0], tid);
-    pipe_split_unit<2>(RA, tile[0], tid); pipe_split_unit<3>(RA, tile[0], tid);
-    pipe_put_weight<0>(RA, wlds[0], tid); pipe_put_weight<1>(RA, wlds[0], tid); pipe_put_weight<2>(RA, wlds[0], tid);
-    __syncthreads();
-
-    f32x16 acc[1][2], acl[1][2];
-    CRFP_PIPE_ACC_INIT
-    int mk = 0, mch = 0;   // item being multiplied
-
-#ifdef CRFP_PIPE_STAMPS
-    long long st_wait = 0, st_taps = 0, st_epi = 0, st_bar = 0, st_t = __builtin_amdgcn_s_memtime();
-#define CRFP_PST(ACC) { const long long t_ = __builtin_amdgcn_s_memtime(); ACC += t_ - st_t; st_t = t_; }
-#else
-#define CRFP_PST(ACC)
+#ifdef CRFP_LAB   // main loops that lost their A/B, their knobs and their dispatch (launch_conv_lab): lab library only (make lab)
+#include "conv_mfma_lab.inc"
 #endif
-    // one item: MFMAs out of LDS buffer BUF; RNEXT (item s+1, landed) is split / copied into buffer BUF^1 between the
-    // taps; RFREE (consumed by the previous item) receives the loads of item s+2 first of all
-#define CRFP_PIPE_ITEM(BUF, RNEXT, RFREE)                                                                 \
-    {                                                                                                     \
-        CRFP_PST(st_bar)                                                                                  \
-        CRFP_PIPE_ISSUE(RFREE)                                                                            \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 0, wave, lane);                                          \
-        pipe_split_unit<0>(RNEXT, tile[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 1, wave, lane);                                          \
-        pipe_put_weight<0>(RNEXT, wlds[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 2, wave, lane);                                          \
-        pipe_split_unit<1>(RNEXT, tile[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 3, wave, lane);                                          \
-        pipe_put_weight<1>(RNEXT, wlds[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 4, wave, lane);                                          \
-        pipe_split_unit<2>(RNEXT, tile[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 5, wave, lane);                                          \
-        pipe_put_weight<2>(RNEXT, wlds[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 6, wave, lane);                                          \
-        pipe_split_unit<3>(RNEXT, tile[(BUF) ^ 1], tid);                                                  \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 7, wave, lane);                                          \
-        pipe_tap(acc, acl, wlds[BUF], tile[BUF], 8, wave, lane);                                          \
-        CRFP_PST(st_taps)                                                                                 \
-        if (++mch == nchunks) {                                                                           \
-            const int t_ = blockIdx.x + mk * gridDim.x, ty_ = t_ / tiles_x, tx_ = t_ - ty_ * tiles_x;     \
-            _Pragma("unroll") for (int pt = 0; pt < 2; ++pt)                                              \
-                _Pragma("unroll") for (int e = 0; e < 16; ++e) acc[0][pt][e] += acl[0][pt][e] * (1.0f / F16_RES_SCALE); \
-            conv_epilogue<1, 2, 1, 2>(ec, acc, T0, tx_ * TW, ty_ * PIPE_NW, wave, j, h);                  \
-            CRFP_PIPE_ACC_INIT                                                                            \
-            mch = 0; ++mk;                                                                                \
-        }                                                                                                 \
-        CRFP_PST(st_epi)                                                                                  \
-        lds_barrier();     /* buffer BUF^1 complete, every wave done with buffer BUF */                  \
-    }
-
-    for (int s = 0; s < nitems; s += 2) {
-        CRFP_PIPE_ITEM(0, RB, RA)
-        if (s + 1 < nitems) CRFP_PIPE_ITEM(1, RA, RB)
-    }
-#undef CRFP_PIPE_ITEM
-#undef CRFP_PIPE_ISSUE
-#undef CRFP_PIPE_ACC_INIT
-#ifdef CRFP_PIPE_STAMPS
-    if (a.stamps && tid == 0) {
-        long long* o = a.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 8;
-        o[0] = st_wait; o[1] = st_taps; o[2] = st_epi; o[3] = st_bar; o[4] = nitems;
-    }
-    if (a.stamps && lane == 0 && blockIdx.x == 3) {   // per-wave view of one workgroup
-        long long* o = a.stamps + (8192 + wave) * 8;
-        o[0] = st_wait; o[1] = st_taps; o[2] = st_epi; o[3] = st_bar; o[4] = nitems;
-    }
-#endif
-}
-
-// ---------------------------------------------------------------- input-stationary variant (short K, many couts)
-// For convolutions whose whole K fits in LDS (Cin <= 32: the 32->216 offset/mask conv, the pixel-shuffle
-// expanders 32->96 / 24->64 / 32->64) the halo tile is staged and split ONCE per workgroup and the
-// workgroup then walks all cout tiles, streaming only the packed weights (27 KB per (cout tile, chunk),
-// prefetched into registers during the previous step's MFMAs).  The regular kernel re-stages the same
-// input once per cout tile and pays its prologue/epilogue bubble 7x for the 216-channel conv.
-template <int NCH, int NWAVES, int NP>
-__global__ __launch_bounds__(64 * NWAVES, NWAVES == 4 ? 2 : 1) void conv3x3_split_is_kernel(const ConvArgs a) {
-    constexpr int RPW = 1, TH = NWAVES, LH = TH + 2, PT = 2, NT = 64 * NWAVES;
-    constexpr int NEL = LH * LW;
-    constexpr int NIN = (NEL + NT - 1) / NT;
-    constexpr int WPC = 9 * NP * 64;
-    constexpr int NWS = (WPC + NT - 1) / NT;
-    __shared__ bf16x8 tile[NCH][NP][2][NEL];
-    __shared__ bf16x8 wlds[WPC];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int tiles_x = (a.W + TW - 1) / TW;
-    const int btile = xcd_band_tile(blockIdx.x, gridDim.x);   // XCD x works on a contiguous band of tiles
-    const int tx0 = (btile % tiles_x) * TW, ty0 = (btile / tiles_x) * TH;
-    const int n = blockIdx.z;
-    const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
-    const int H = a.H, W = a.W;
-    const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(NP == 3 ? a.wsplit : a.wsplit16);
-    const int nsteps = a.ctiles * NCH;
-
-    bf16x8 rws[NWS];
-#define CRFP_IS_WLOAD(STEP)                                                                               \
-    _Pragma("unroll") for (int k = 0; k < NWS; ++k)                                                       \
-        rws[k] = wp[(long long)(STEP) * WPC + min(tid + NT * k, WPC - 1)];
-    CRFP_IS_WLOAD(0)   // (cout tile 0, chunk 0): packed index (T*nchunks + ch)*WPC == step*WPC
-
-    // ---- stage + split the whole input tile once
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-        f32x4 rq[4][NIN];
-        int msk[4];
-        bool ok[NIN];
-#pragma unroll
-        for (int qi = 0; qi < 4; ++qi) {
-            const QuadDesc d = a.qd[4 * ch + qi];
-            const float* qb = d.base + (long long)ns * d.bstride;
-            msk[qi] = d.mask;
-#pragma unroll
-            for (int t = 0; t < NIN; ++t) {
-                const int idx = min(tid + NT * t, NEL - 1);
-                const int r = idx / LW, c = idx - r * LW;
-                const int gy = ty0 + r - 1, gx = tx0 + c - 1;
-                ok[t] = tid + NT * t < NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-                rq[qi][t] = *reinterpret_cast<const f32x4*>(qb + min(max(gy, 0), H - 1) * d.rs + min(max(gx, 0), W - 1) * d.cs);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NIN; ++t) {
-            const int idx = tid + NT * t;
-            if (idx < NEL) {
-                bf16x8 pp[NP];
-                split_parts<NP>(mask_quad(rq[0][t], ok[t] ? msk[0] : 0), mask_quad(rq[1][t], ok[t] ? msk[1] : 0), pp);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) tile[ch][p][0][idx] = pp[p];
-                split_parts<NP>(mask_quad(rq[2][t], ok[t] ? msk[2] : 0), mask_quad(rq[3][t], ok[t] ? msk[3] : 0), pp);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) tile[ch][p][1][idx] = pp[p];
-            }
-        }
-    }
-
-    long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
-    if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tA += t - t0; t0 = t; }
-    f32x16 acc[1][PT], acl[1][PT];
-    const EpiCtx ec = epi_ctx(a, n);
-    float2 flpre[PT];   // flow of this lane's pixels (ST_OFFMASK): loaded here, not between two epilogues' stores
-#pragma unroll
-    for (int pt = 0; pt < PT; ++pt) {
-        const int y = min(ty0 + wave * RPW + (pt >> 1), H - 1), x = min(tx0 + (pt & 1) * 32 + j, W - 1);
-        flpre[pt] = a.store == ST_OFFMASK ? *reinterpret_cast<const float2*>(ec.flp + ((long long)y * W + x) * 2)
-                                          : make_float2(0.0f, 0.0f);
-    }
-    for (int step = 0; step < nsteps; ++step) {
-        const int ch = step % NCH, ct = step / NCH;
-        if (ch == 0) {
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { acc[0][pt][e] = 0.0f; acl[0][pt][e] = 0.0f; }
-        }
-        __syncthreads();  // all waves done with the previous step's weights (and, first time, tile staged)
-#pragma unroll
-        for (int k = 0; k < NWS; ++k) {
-            const int idx = tid + NT * k;
-            if (idx < WPC) wlds[idx] = rws[k];
-        }
-        __syncthreads();
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tB += t - t0; t0 = t; }
-        if (step + 1 < nsteps) { CRFP_IS_WLOAD(step + 1) }
-#pragma unroll CRFP_TAP_UNROLL
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap - 3 * ky;
-            bf16x8 wa[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) wa[p] = wlds[(tap * NP + p) * 64 + lane];
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt) {
-                const int pix = (wave * RPW + (pt >> 1) + ky) * LW + (pt & 1) * 32 + j + kx;
-                bf16x8 bq[NP];
-#pragma unroll
-                for (int p = 0; p < NP; ++p) bq[p] = tile[ch][p][h][pix];
-                split_mfma<NP>(acc[0][pt], acl[0][pt], wa, bq);
-            }
-        }
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tD += t - t0; t0 = t; }
-        if (ch == NCH - 1) {
-            if (NP == 2) {
-#pragma unroll
-                for (int pt = 0; pt < PT; ++pt)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[0][pt][e] += acl[0][pt][e] * (1.0f / F16_RES_SCALE);
-            }
-            conv_epilogue<1, PT, RPW, 0>(ec, acc, ct, tx0, ty0, wave, j, h, flpre);
-        }
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tC += t - t0; t0 = t; }
-    }
-    if (a.stamps && tid == 0) {
-        long long* o = a.stamps + (long long)blockIdx.x * 4;
-        o[0] = tA; o[1] = tB; o[2] = tC; o[3] = tD;
-    }
-#undef CRFP_IS_WLOAD
-}
-
-// ================================================================ warp-specialised split-bf16 convolution
-// Measured on the single-role kernels above (s_memtime stamps): the MFMA phase is only 40-50 % of a
-// block's life; the rest is (a) the fp32->3xbf16 split + LDS write of the next chunk, which cannot
-// overlap the MFMAs of the same waves, and (b) vmcnt being in-order on CDNA: a wave that has epilogue
-// stores in flight must drain them before it can consume a prefetched load (12k cycles per cout tile
-// in the 216-channel conv).  Here the roles are split:
-//   * 8 compute waves (one output row of 64 px each, 2 per SIMD) only ever read LDS, issue MFMAs and
-//     fire their epilogue stores -- they never wait on vmcnt inside the main loop;
-//   * 4 loader waves (one per SIMD) own every global load: they fetch the next chunk's halo tile (fp32)
-//     and packed weights, split the activations into 3 bf16 images and write them into the OTHER half
-//     of a double-buffered LDS tile while the compute waves run the current chunk.
-// Two workgroup barriers per chunk: X = compute done with the weight image / loaders done with the next
-// tile, Y = weight image of this chunk visible.  Weights (27 KB per chunk) are single-buffered: the
-// loaders hold them in registers and copy them in between X and Y (~400 idle compute cycles).
-// IS = input-stationary form for Cin <= 32 and many couts: both LDS tile halves hold the (at most two)
-// K-chunks for the whole block and the loop runs over (cout tile, chunk) steps streaming only weights.
-constexpr int WS_NC = 8, WS_NL = 8, WS_NT = 64 * (WS_NC + WS_NL), WS_TH = 8, WS_LH = WS_TH + 2, WS_NEL = WS_LH * LW;
-
-template <bool IS>
-__global__ __launch_bounds__(WS_NT, 1) void conv3x3_split_ws_kernel(const ConvArgs a) {
-    constexpr int NLT = 64 * WS_NL;                       // loader threads
-    constexpr int NIN = (WS_NEL + NLT - 1) / NLT;         // halo pixels per loader thread (3)
-    constexpr int NWS = (27 * 64 + NLT - 1) / NLT;        // weight vectors per loader thread (7)
-    __shared__ bf16x8 tile[2][3][2][WS_NEL];
-    __shared__ bf16x8 wlds[27 * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles_x = (a.W + TW - 1) / TW;
-    const int tx0 = (blockIdx.x % tiles_x) * TW, ty0 = (blockIdx.x / tiles_x) * WS_TH;
-    const int n = blockIdx.z;
-    const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
-    const int H = a.H, W = a.W;
-    const int nchunks = a.kq >> 2;
-    const int T0 = IS ? 0 : blockIdx.y;
-    const int nsteps = IS ? a.ctiles * nchunks : nchunks;   // IS: step = ct*nchunks + ch
-
-    if (wave >= WS_NC) {
-        // ------------------------------------------------------------ loader role
-        const int lt = tid - 64 * WS_NC;
-        const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(a.wsplit);
-        int cgy[NIN], cgx[NIN];
-        bool sval[NIN];
-#pragma unroll
-        for (int t = 0; t < NIN; ++t) {
-            const int idx = min(lt + NLT * t, WS_NEL - 1);
-            const int r = idx / LW, c = idx - r * LW;
-            const int gy = ty0 + r - 1, gx = tx0 + c - 1;
-            sval[t] = lt + NLT * t < WS_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            cgy[t] = min(max(gy, 0), H - 1);
-            cgx[t] = min(max(gx, 0), W - 1);
-        }
-        // Loader schedule, two register sets (A, B): right after barrier Y(s) the loads of chunk s+2 are
-        // issued into the set that was just consumed, THEN the other set (chunk s+1, issued a whole step
-        // earlier) is split and written to the idle tile half.  Every load is unconditional (chunk index
-        // clamped) so that the in-order vmcnt counts are compile-time constants and the compiler can wait
-        // for "all but the loads just issued" instead of vmcnt(0).
-        f32x4 qa0[NIN], qa1[NIN], qa2[NIN], qa3[NIN], qb0[NIN], qb1[NIN], qb2[NIN], qb3[NIN];
-        bf16x8 wa_[NWS], wb_[NWS];
-        int ma0 = 0, ma1 = 0, ma2 = 0, ma3 = 0, mb0 = 0, mb1 = 0, mb2 = 0, mb3 = 0;
-#define CRFP_WS_LOAD_IN(R0, R1, R2, R3, M0, M1, M2, M3, CH)                                               \
-        {                                                                                                 \
-            const QuadDesc d0 = a.qd[4 * (CH)], d1 = a.qd[4 * (CH) + 1], d2 = a.qd[4 * (CH) + 2],         \
-                           d3 = a.qd[4 * (CH) + 3];                                                       \
-            const float* b0 = d0.base + (long long)ns * d0.bstride;                                        \
-            const float* b1 = d1.base + (long long)ns * d1.bstride;                                        \
-            const float* b2 = d2.base + (long long)ns * d2.bstride;                                        \
-            const float* b3 = d3.base + (long long)ns * d3.bstride;                                        \
-            M0 = d0.mask; M1 = d1.mask; M2 = d2.mask; M3 = d3.mask;                                       \
-            _Pragma("unroll") for (int t = 0; t < NIN; ++t) {                                             \
-                R0[t] = *reinterpret_cast<const f32x4*>(b0 + cgy[t] * d0.rs + cgx[t] * d0.cs);            \
-                R1[t] = *reinterpret_cast<const f32x4*>(b1 + cgy[t] * d1.rs + cgx[t] * d1.cs);            \
-                R2[t] = *reinterpret_cast<const f32x4*>(b2 + cgy[t] * d2.rs + cgx[t] * d2.cs);            \
-                R3[t] = *reinterpret_cast<const f32x4*>(b3 + cgy[t] * d3.rs + cgx[t] * d3.cs);            \
-            }                                                                                             \
-        }
-#define CRFP_WS_LOAD_W(RW, WSTEP)                                                                         \
-        _Pragma("unroll") for (int k = 0; k < NWS; ++k)                                                   \
-            RW[k] = wp[(long long)(WSTEP) * 1728 + min(lt + NLT * k, 1727)];
-#define CRFP_WS_WRITE_IN(R0, R1, R2, R3, M0, M1, M2, M3, BUF)                                             \
-        _Pragma("unroll") for (int t = 0; t < NIN; ++t) {                                                 \
-            const int idx = lt + NLT * t;                                                                 \
-            if (idx < WS_NEL) {                                                                           \
-                bf16x8 p0, p1, p2;                                                                        \
-                split_bf16x8(mask_quad(R0[t], sval[t] ? M0 : 0), mask_quad(R1[t], sval[t] ? M1 : 0), p0, p1, p2); \
-                tile[BUF][0][0][idx] = p0; tile[BUF][1][0][idx] = p1; tile[BUF][2][0][idx] = p2;          \
-                split_bf16x8(mask_quad(R2[t], sval[t] ? M2 : 0), mask_quad(R3[t], sval[t] ? M3 : 0), p0, p1, p2); \
-                tile[BUF][0][1][idx] = p0; tile[BUF][1][1][idx] = p1; tile[BUF][2][1][idx] = p2;          \
-            }                                                                                             \
-        }
-#define CRFP_WS_WRITE_W(RW)                                                                               \
-        _Pragma("unroll") for (int k = 0; k < NWS; ++k) {                                                 \
-            const int idx = lt + NLT * k;                                                                 \
-            if (idx < 1728) wlds[idx] = RW[k];                                                            \
-        }
-        // packed weight image of (cout tile T, chunk ch) starts at ((T*nchunks + ch)*27)*64 vectors
-        const long long wbase = (long long)T0 * nchunks;
-        const int last = nsteps - 1, lastc = nchunks - 1;
-        if (IS) {
-            CRFP_WS_LOAD_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, 0)
-            CRFP_WS_LOAD_W(wa_, wbase)
-            CRFP_WS_WRITE_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, 0)
-            if (nchunks > 1) {
-                CRFP_WS_LOAD_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, 1)
-                CRFP_WS_WRITE_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, 1)
-            }
-            for (int step = 0; step < nsteps; ++step) {
-                __syncthreads();  // X
-                CRFP_WS_WRITE_W(wa_)
-                __syncthreads();  // Y
-                CRFP_WS_LOAD_W(wa_, wbase + min(step + 1, last))
-            }
-        } else {
-            CRFP_WS_LOAD_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, 0)
-            CRFP_WS_LOAD_W(wa_, wbase)
-            CRFP_WS_LOAD_IN(qb0, qb1, qb2, qb3, mb0, mb1, mb2, mb3, min(1, lastc))
-            CRFP_WS_LOAD_W(wb_, wbase + min(1, last))
-            CRFP_WS_WRITE_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, 0)
-            // top of an even step s: tile[s&1] = chunk s, wa_ = weights(s), set B = chunk s+1 (in flight)
-            long long sA = 0, sB = 0, sC = 0, sD = 0, t0 = __builtin_amdgcn_s_memtime();
-#define CRFP_ST(ACC) if (a.stamps) { const long long t_ = __builtin_amdgcn_s_memtime(); ACC += t_ - t0; t0 = t_; }
-            for (int step = 0; step < nsteps; step += 2) {
-                __syncthreads();  // X: compute done with wlds and with tile[(step+1)&1]
-                CRFP_ST(sD)
-                CRFP_WS_WRITE_W(wa_)
-                __syncthreads();  // Y
-                CRFP_ST(sC)
-                CRFP_WS_LOAD_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, min(step + 2, lastc))
-                CRFP_WS_LOAD_W(wa_, wbase + min(step + 2, last))
-                CRFP_ST(sA)
-                if (step + 1 >= nsteps) break;
-                CRFP_WS_WRITE_IN(qb0, qb1, qb2, qb3, mb0, mb1, mb2, mb3, (step + 1) & 1)
-                CRFP_ST(sB)
-                __syncthreads();  // X
-                CRFP_ST(sD)
-                CRFP_WS_WRITE_W(wb_)
-                __syncthreads();  // Y
-                CRFP_ST(sC)
-                CRFP_WS_LOAD_IN(qb0, qb1, qb2, qb3, mb0, mb1, mb2, mb3, min(step + 3, lastc))
-                CRFP_WS_LOAD_W(wb_, wbase + min(step + 3, last))
-                CRFP_ST(sA)
-                if (step + 2 < nsteps) CRFP_WS_WRITE_IN(qa0, qa1, qa2, qa3, ma0, ma1, ma2, ma3, step & 1)
-                CRFP_ST(sB)
-            }
-            if (a.stamps && lt == 0) {
-                long long* o = a.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 4 + 4 * 8192;
-                o[0] = sA; o[1] = sB; o[2] = sC; o[3] = sD;
-            }
-#undef CRFP_ST
-        }
-#undef CRFP_WS_LOAD_IN
-#undef CRFP_WS_LOAD_W
-#undef CRFP_WS_WRITE_IN
-#undef CRFP_WS_WRITE_W
-        return;
-    }
-
-    // ---------------------------------------------------------------- compute role: wave = output row
-    const int j = lane & 31, h = lane >> 5;
-    f32x16 acc[1][2];
-    const EpiCtx ec = epi_ctx(a, n);
-    float2 flpre[2] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)};
-    if (a.store == ST_OFFMASK) {
-        const int y = min(ty0 + wave, H - 1);
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt)
-            flpre[pt] = *reinterpret_cast<const float2*>(a.flow + (long long)n * a.flow_bstride +
-                                                         ((long long)y * W + min(tx0 + pt * 32 + j, W - 1)) * 2);
-    }
-    long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
-    for (int step = 0; step < nsteps; ++step) {
-        const int ch = IS ? step % nchunks : step;
-        const int buf = IS ? ch : (step & 1);
-        if (!IS ? step == 0 : ch == 0) {
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[0][pt][e] = 0.0f;
-        }
-        __syncthreads();  // X
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tA += t - t0; t0 = t; }
-        __syncthreads();  // Y
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tB += t - t0; t0 = t; }
-#pragma unroll CRFP_TAP_UNROLL
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap - 3 * ky;
-            const bf16x8 w0 = wlds[(tap * 3 + 0) * 64 + lane], w1 = wlds[(tap * 3 + 1) * 64 + lane],
-                         w2 = wlds[(tap * 3 + 2) * 64 + lane];
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt) {
-                const int pix = (wave + ky) * LW + pt * 32 + j + kx;
-                const bf16x8 b0 = tile[buf][0][h][pix], b1 = tile[buf][1][h][pix], b2 = tile[buf][2][h][pix];
-                f32x16 c = acc[0][pt];
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b1, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b2, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b0, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b1, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b0, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b0, c, 0, 0, 0);
-                acc[0][pt] = c;
-            }
-        }
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tD += t - t0; t0 = t; }
-        if (IS && ch == nchunks - 1) conv_epilogue<1, 2, 1, 0>(ec, acc, step / nchunks, tx0, ty0, wave, j, h, flpre);
-        if (a.stamps) { const long long t = __builtin_amdgcn_s_memtime(); tC += t - t0; t0 = t; }
-    }
-    if (a.stamps && tid == 0) {
-        long long* o = a.stamps + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-        o[0] = tA; o[1] = tB; o[2] = tC; o[3] = tD;
-    }
-    if (!IS) conv_epilogue<1, 2, 1, 0>(ec, acc, T0, tx0, ty0, wave, j, h, flpre);
-}
-
-#endif  // CRFP_LAB
 
 // split weight pack: wsplit bf16 index =
 //   (((((T*nchunks + ch)*9 + tap)*3 + part)*64 + lane)*8 + jj),  lane = half*32 + row,
@@ -2521,26 +1819,17 @@ bool precision_env_strict(int family) {
 namespace CRFP_NS {
 #endif
 
-#ifdef CRFP_LAB
-static const char* lab_conv_mode() { static const char* m = getenv("CRFP_CONV_MODE"); return m ? m : "f16x3"; }
-static int lab_knob(const char* k, int dflt) { const char* v = getenv(k); return v ? atoi(v) : dflt; }
-#endif
-
 // SRC_S3 sources / s3_dst are understood by conv3x3_split_kernel<1,1,2> (the default) only
 bool conv_s3_supported() {
     static const bool ok = [] {
         if (kActBf16 || precision_env_strict(0)) return false;
 #ifdef CRFP_LAB
-        if (strcmp(lab_conv_mode(), "f16x3")) return false;
-        if (lab_knob("CRFP_SPLIT_WS", 0) || lab_knob("CRFP_SPLIT_IS", 0) || lab_knob("CRFP_SPLIT_PIPE", 0)) return false;
-        if (lab_knob("CRFP_SPLIT_RPW", 1) != 1 || lab_knob("CRFP_SPLIT_CT", 1) != 1 || !lab_knob("CRFP_CONV_S3", 1)) return false;
+        if (!lab_conv_s3_supported()) return false;
 #endif
         return true;
     }();
     return ok;
 }
-
-static bool uses_s3_dst_only_4wave(const ConvArgs&) { return false; }   // the shared epilogue writes S3 images from either kernel
 
 // per-quad load descriptors (wave-uniform in the kernels: one s_load per quad); filled into the caller's private plan copy
 static int build_quad_descs(ConvArgs& am, const char* name) {
@@ -2582,6 +1871,29 @@ static int build_quad_descs(ConvArgs& am, const char* name) {
     return 0;
 }
 
+// algorithmic work of one conv for ProfScope: activations in and out in the storage type plus the fp32 weights; 2 flops per multiply-add
+struct ConvWork { double px, in_ch, bytes, flops; };
+static ConvWork conv_work(const ConvArgs& a) {
+    ConvWork w;
+    w.px = (double)a.N * a.H * a.W;
+    w.in_ch = 0;
+    for (int i = 0; i < a.nsrc; ++i) w.in_ch += a.src[i].kind == SRC_ZERO ? 0 : a.src[i].nch;
+    w.bytes = w.px * (w.in_ch + a.cout) * (double)sizeof(act_t) + (double)a.cout * w.in_ch * 9 * 4.0;
+    w.flops = 2.0 * w.px * a.cout * w.in_ch * 9.0;
+    return w;
+}
+
+// what a launcher derives in its private, mutable plan copy before the kernel reads it: no stamps, the weight images behind a.wsplit, the
+// per-quad load descriptors
+static int prepare_plan(ConvArgs& am, const char* name) {
+    am.stamps = nullptr;
+    am.wsplit16 = am.wsplit ? (const char*)am.wsplit + conv_split16_offset_bytes(am) : nullptr;
+#ifndef CRFP_ACT_BF16
+    am.wsplit_sa = am.wsplit ? (const char*)am.wsplit + conv_split_sa_offset_bytes(am) : nullptr;
+#endif
+    return am.kq <= CRFP_MAX_KQ ? build_quad_descs(am, name) : 0;
+}
+
 int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
     if (a.kq & 1 || a.kq < 2 || a.ctiles < 1 || a.nsrc < 1 || a.nsrc > CRFP_MAX_SRC) {
         set_error("conv_mfma %s: bad plan (kq=%d ctiles=%d nsrc=%d)", name, a.kq, a.ctiles, a.nsrc);
@@ -2613,102 +1925,24 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         set_error("conv_mfma %s: SRC_S3 / s3_dst need the default f16x3 kernel, ST_Q4 and cout %% 8 == 0", name);
         return CRFP_E_UNSUPPORTED;
     }
-    int split_rpw = 1;
-#ifdef CRFP_LAB
-    split_rpw = lab_knob("CRFP_SPLIT_RPW", 1);
-    const int split_ct = lab_knob("CRFP_SPLIT_CT", 1);
-    if (lab_knob("CRFP_CONV_CT", 2) < 2) ct2 = false;
-    if (split && split_ct < 2) ct2 = false;
-#else
-    if (split) ct2 = false;  // <2,1> needs 93 KB of LDS (1 workgroup per CU): slower than 2 x <1,1>
-#endif
-    const int TH = (ct2 || (split && split_rpw == 1)) ? 4 : 8;
-    const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
-    const double px = (double)a.N * a.H * a.W;
-    double in_ch = 0;
-    for (int i = 0; i < a.nsrc; ++i) in_ch += a.src[i].kind == SRC_ZERO ? 0 : a.src[i].nch;
-    ProfScope prof(name, s, px * (in_ch + a.cout) * (double)sizeof(act_t) + (double)a.cout * in_ch * 9 * 4.0,
-                   2.0 * px * a.cout * in_ch * 9.0);
+    const ConvWork work = conv_work(a);
+    ProfScope prof(name, s, work.bytes, work.flops);
     ConvArgs& am = const_cast<ConvArgs&>(a);  // callers pass a private, mutable plan copy
-    am.stamps = nullptr;
-#ifdef CRFP_LAB
-    // diagnostic: CRFP_STAMP_PTR=<device address> CRFP_STAMP_NAME=<launch site> records phase cycles per block
-    static const char* stamp_name = getenv("CRFP_STAMP_NAME");
-    static long long* stamp_ptr = getenv("CRFP_STAMP_PTR") ? (long long*)strtoull(getenv("CRFP_STAMP_PTR"), nullptr, 0) : nullptr;
-    am.stamps = (stamp_ptr && stamp_name && !strcmp(stamp_name, name)) ? stamp_ptr : nullptr;
-#endif
-    am.wsplit16 = a.wsplit ? (const char*)a.wsplit + conv_split16_offset_bytes(a) : nullptr;
-#ifndef CRFP_ACT_BF16
-    am.wsplit_sa = a.wsplit ? (const char*)a.wsplit + conv_split_sa_offset_bytes(a) : nullptr;
-#endif
     if (env_strict || a.strict) am.ovf = nullptr;   // nothing downstream turns this output into an fp16 operand
-    if (a.kq <= CRFP_MAX_KQ) {
-        const int rc = build_quad_descs(am, name);
+    {
+        const int rc = prepare_plan(am, name);
         if (rc) return rc;
     }
 #ifdef CRFP_LAB
-    const bool use_f16 = strcmp(lab_conv_mode(), "bf16x6") != 0;
-    // warp-specialised variant: measured 346 vs 351.5 frames/s for the single-role kernels (loader issue is
-    // throttled by the ~12 B/clk/CU the memory system delivers) -> kept as an opt-in experiment
-    const bool use_ws = lab_knob("CRFP_SPLIT_WS", 0) == 1;
-    // input-stationary variant: wins for bf16x6 (65 KB workgroups, 2 per CU); with f16x3 the plain kernel runs 3 workgroups
-    // per CU and is faster even for the 216-channel conv (139.8 vs 147.6 us), so it is opt-in there
-    const bool use_is = lab_knob("CRFP_SPLIT_IS", use_f16 ? 0 : 1) != 0;
-    const bool use_pipe = lab_knob("CRFP_SPLIT_PIPE", 0) == 1;
-    const int pipe_wgs = lab_knob("CRFP_PIPE_WGS", 256);
-    if (split && use_ws) {
-        const int wtiles = ((a.W + TW - 1) / TW) * ((a.H + WS_TH - 1) / WS_TH);
-        if (use_is && a.kq <= 8 && a.ctiles >= 2) {
-            conv3x3_split_ws_kernel<true><<<dim3(wtiles, 1, a.N), WS_NT, 0, s>>>(a);
-        } else {
-            conv3x3_split_ws_kernel<false><<<dim3(wtiles, a.ctiles, a.N), WS_NT, 0, s>>>(a);
-        }
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-    if (split && use_is && a.kq <= 8 && a.ctiles >= 2) {
-        // input-stationary: whole K in LDS, one workgroup per 4x64 tile walks every cout tile
-        dim3 grid(((a.W + TW - 1) / TW) * ((a.H + 7) / 8), 1, a.N);
-        const int is_waves = lab_knob("CRFP_IS_WAVES", 8);
-        if (use_f16 && is_waves == 4) {
-            dim3 grid4(((a.W + TW - 1) / TW) * ((a.H + 3) / 4), 1, a.N);
-            if (a.kq == 4) conv3x3_split_is_kernel<1, 4, 2><<<grid4, 256, 0, s>>>(am);
-            else conv3x3_split_is_kernel<2, 4, 2><<<grid4, 256, 0, s>>>(am);
-        } else if (use_f16) {
-            if (a.kq == 4) conv3x3_split_is_kernel<1, 8, 2><<<grid, 512, 0, s>>>(am);
-            else conv3x3_split_is_kernel<2, 8, 2><<<grid, 512, 0, s>>>(am);
-        } else {
-            if (a.kq == 4) conv3x3_split_is_kernel<1, 8, 3><<<grid, 512, 0, s>>>(am);
-            else conv3x3_split_is_kernel<2, 8, 3><<<grid, 512, 0, s>>>(am);
-        }
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-    if (split && use_pipe) {
-        // persistent: one workgroup per CU walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...
-        const int ntl = ((a.W + TW - 1) / TW) * ((a.H + PIPE_NW - 1) / PIPE_NW);
-        const int per = (ntl + pipe_wgs - 1) / pipe_wgs;           // tiles per workgroup
-        dim3 grid((ntl + per - 1) / per, a.ctiles, a.N);           // balanced shares
-        conv3x3_split_pipe_kernel<<<grid, PIPE_NT, 0, s>>>(a);
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-    if (split && (ct2 || split_rpw != 1 || !use_f16)) {
-        if (ct2) {
-            dim3 grid(tiles * (a.ctiles / 2), 1, a.N);
-            if (use_f16) conv3x3_split_kernel<2, 1, 2><<<grid, 256, 0, s>>>(am);
-            else conv3x3_split_kernel<2, 1, 3><<<grid, 256, 0, s>>>(am);
-        } else if (split_rpw == 1) {
-            conv3x3_split_kernel<1, 1, 3><<<dim3(tiles * a.ctiles, 1, a.N), 256, 0, s>>>(am);
-        } else {
-            dim3 grid(tiles * a.ctiles, 1, a.N);
-            if (use_f16) conv3x3_split_kernel<1, 2, 2><<<grid, 256, 0, s>>>(am);
-            else conv3x3_split_kernel<1, 2, 3><<<grid, 256, 0, s>>>(am);
-        }
-        CRFP_CHECK_LAUNCH();
-        return 0;
+    {
+        bool done = false;
+        const int rc = launch_conv_lab(am, name, split, ct2, s, &done);
+        if (rc || done) return rc;
     }
 #endif
+    if (split) ct2 = false;  // <2,1> needs 93 KB of LDS (1 workgroup per CU): slower than 2 x <1,1>
+    const int TH = (ct2 || split) ? 4 : 8;
+    const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
     if (split) {
 #ifdef CRFP_ACT_BF16
         // (8-row tiles, conv3x3_bf16_kernel<2>: 1.25 instead of 1.5 ds_read_b128 per MFMA and half the weight staging, but 450
@@ -2721,12 +1955,8 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         // ... and only while its 8-row tiles fill no more than one round of the chip's 512 slots (two 60 KB workgroups per CU): a lock-step
         // batch of clips is several rounds, where tile granularity no longer matters and the 4-wave kernel's four workgroups per CU overlap
         // more of each other's load / MFMA / store phases (round 4, same box, 4 clips: res.main0 15.1 -> 14.1 us per clip, conv_fuse 14.7 -> 14.0,
-        // conv1 9.9 -> 9.2; CRFP_BF16_X8_MAX_WGS overrides the threshold for A/B runs)
-#ifdef CRFP_LAB
-        static const int x8_max_wgs = getenv("CRFP_BF16_X8_MAX_WGS") ? atoi(getenv("CRFP_BF16_X8_MAX_WGS")) : 512;   // A/B knob, lab library only
-#else
+        // conv1 9.9 -> 9.2)
         constexpr int x8_max_wgs = 512;   // fixed in the product: the x8 / 4-wave choice is part of the per-clip bit-identity contract
-#endif
         if (a.ctiles == 1 && ((a.kq >> 2) & 1) == 0 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + B8_TH - 1) / B8_TH) <= x8_max_wgs) {
             const int tiles8 = ((a.W + TW - 1) / TW) * ((a.H + B8_TH - 1) / B8_TH);
             conv3x3_bf16x8_kernel<<<dim3(tiles8 * a.ctiles, 1, a.N), B8_NT, 0, s>>>(am);
@@ -2736,24 +1966,14 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         // 8-wave single-accumulator kernel for the convs with one cout tile (the 32-cout layers: one round of 450 workgroups
         // instead of 1.17 rounds of 900; same-box: conv1 26.4 -> 24.6 us, conv2 28.7 -> 26.1, block0 46.0 -> 43.2, main0 40.0 ->
         // 38.0, clip -1.5 %); with several cout tiles the 4-wave kernel stays (offset/mask head 114.0 vs 117.7 us)
-#ifdef CRFP_LAB
-        static const int s8_max_wgs = getenv("CRFP_F32_S8_MAX_WGS") ? atoi(getenv("CRFP_F32_S8_MAX_WGS")) : (1 << 30);   // A/B knob (round 4), lab library only
-#else
-        constexpr int s8_max_wgs = 1 << 30;
-#endif
-        if (a.ctiles == 1 && !uses_s3_dst_only_4wave(a) && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + S8_TH - 1) / S8_TH) <= s8_max_wgs) {
+        constexpr int s8_max_wgs = 1 << 30;   // (the lab library's CRFP_F32_S8_MAX_WGS lowers it: launch_conv_lab)
+        if (a.ctiles == 1 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + S8_TH - 1) / S8_TH) <= s8_max_wgs) {
 #ifdef CRFP_S8_NW
             constexpr int s8nw = CRFP_S8_NW;
 #else
             constexpr int s8nw = S8_TH;
 #endif
             const int tiles8 = ((a.W + TW - 1) / TW) * ((a.H + s8nw - 1) / s8nw);
-#ifdef CRFP_LAB
-            static const int s8p = getenv("CRFP_S8P") ? atoi(getenv("CRFP_S8P")) : 0;   // the persistent 4-row form (lost: see the kernel)
-            const int items4 = tiles * a.ctiles;
-            if (s8p && items4 > 512) conv3x3_split8p_kernel<<<dim3(512, 1, a.N), S8P_NT, 0, s>>>(am, items4);
-            else
-#endif
             conv3x3_split8_kernel<s8nw><<<dim3(tiles8 * a.ctiles, 1, a.N), 64 * s8nw, 0, s>>>(am);
         } else
             conv3x3_split_kernel<1, 1, 2><<<dim3(tiles * a.ctiles, 1, a.N), 256, 0, s>>>(am);
@@ -2798,22 +2018,12 @@ int launch_conv_mfma_dual(const ConvArgs& a0, const char* name0, const ConvArgs&
         conv_s3_supported()) {
         const int tiles = ((a0.W + TW - 1) / TW) * ((a0.H + 3) / 4), w0 = tiles * a0.ctiles;
         if ((w0 & 7) == 0) {
-            double bytes = 0, flops = 0;
-            for (const ConvArgs* a : {&a0, &a1}) {
-                double in_ch = 0;
-                for (int i = 0; i < a->nsrc; ++i) in_ch += a->src[i].kind == SRC_ZERO ? 0 : a->src[i].nch;
-                const double px = (double)a->N * a->H * a->W;
-                bytes += px * (in_ch + a->cout) * (double)sizeof(act_t) + (double)a->cout * in_ch * 9 * 4.0;
-                flops += 2.0 * px * a->cout * in_ch * 9.0;
-            }
-            ProfScope prof(name_both, s, bytes, flops);
+            const ConvWork w0k = conv_work(a0), w1k = conv_work(a1);
+            ProfScope prof(name_both, s, w0k.bytes + w1k.bytes, w0k.flops + w1k.flops);
             ConvArgs* am[2] = {&const_cast<ConvArgs&>(a0), &const_cast<ConvArgs&>(a1)};   // callers pass private, mutable plan copies
             const char* nm[2] = {name0, name1};
             for (int k = 0; k < 2; ++k) {
-                am[k]->stamps = nullptr;
-                am[k]->wsplit16 = (const char*)am[k]->wsplit + conv_split16_offset_bytes(*am[k]);
-                am[k]->wsplit_sa = (const char*)am[k]->wsplit + conv_split_sa_offset_bytes(*am[k]);
-                const int rc = build_quad_descs(*am[k], nm[k]);
+                const int rc = prepare_plan(*am[k], nm[k]);
                 if (rc) return rc;
             }
             conv3x3_split_dual_kernel<1, 1, 2><<<dim3(2 * w0, 1, a0.N), 256, 0, s>>>(*am[0], *am[1], w0);
@@ -2864,20 +2074,13 @@ int launch_conv_ksplit(const ConvArgs& a, const char* name, hipStream_t s) {
         return CRFP_E_UNSUPPORTED;
     }
     const int tiles = ((a.W + TW - 1) / TW) * ((a.H + 3) / 4);
-    double in_ch = 0;
-    for (int i = 0; i < a.nsrc; ++i) in_ch += a.src[i].kind == SRC_ZERO ? 0 : a.src[i].nch;
-    const double px = (double)a.N * a.H * a.W;
-    ProfScope prof(name, s, px * (in_ch * (double)sizeof(act_t) + a.cout * 4.0 * a.ksplit) + (double)a.cout * in_ch * 9 * 4.0, 2.0 * px * a.cout * in_ch * 9.0);
+    const ConvWork w = conv_work(a);   // ... but the output leaves as ksplit float partial tensors
+    ProfScope prof(name, s, w.px * (w.in_ch * (double)sizeof(act_t) + a.cout * 4.0 * a.ksplit) + (double)a.cout * w.in_ch * 9 * 4.0, w.flops);
     ConvArgs& am = const_cast<ConvArgs&>(a);   // callers pass a private, mutable plan copy
-    am.stamps = nullptr;
     am.act = CRFP_ACT_NONE;
     am.dst_f32 = 1;
     am.ovf = nullptr;
-    am.wsplit16 = (const char*)a.wsplit + conv_split16_offset_bytes(a);
-#ifndef CRFP_ACT_BF16
-    am.wsplit_sa = (const char*)a.wsplit + conv_split_sa_offset_bytes(a);
-#endif
-    const int rc = build_quad_descs(am, name);
+    const int rc = prepare_plan(am, name);
     if (rc) return rc;
     const dim3 grid(tiles * a.ctiles, 1, a.N * a.ksplit);
 #ifdef CRFP_ACT_BF16
@@ -2921,16 +2124,12 @@ int launch_conv_pair(const ConvArgs& a, const ConvArgs& b, const char* name, hip
     }
     for (int i = 0; i < a.nsrc; ++i)
         if (a.src[i].kind == SRC_NCHW || a.src[i].kind == SRC_S3) { set_error("conv_pair %s: NCHW / S3 sources are not supported", name); return CRFP_E_UNSUPPORTED; }
-    const double px = (double)a.N * a.H * a.W;
-    double in_ch = 0;
-    for (int i = 0; i < a.nsrc; ++i) in_ch += a.src[i].kind == SRC_ZERO ? 0 : a.src[i].nch;
+    const ConvWork w = conv_work(a);
     // algorithmic work of the PAIR: A's inputs + B's outputs (+ residual) cross HBM, the 32-channel tensor between them does not
-    ProfScope prof(name, s, px * (in_ch + 32 + (b.resid ? 32 : 0)) * (double)sizeof(act_t) + (32.0 * in_ch + 32.0 * 32.0) * 9 * 4.0,
-                   2.0 * px * 32 * (in_ch + 32) * 9.0);
+    ProfScope prof(name, s, w.px * (w.in_ch + 32 + (b.resid ? 32 : 0)) * (double)sizeof(act_t) + (32.0 * w.in_ch + 32.0 * 32.0) * 9 * 4.0,
+                   2.0 * w.px * 32 * (w.in_ch + 32) * 9.0);
     ConvArgs am = a;
-    am.stamps = nullptr;
-    am.wsplit16 = (const char*)a.wsplit + conv_split16_offset_bytes(a);
-    const int rc = build_quad_descs(am, name);
+    const int rc = prepare_plan(am, name);
     if (rc) return rc;
     PairB pb;
     memset(&pb, 0, sizeof(pb));
