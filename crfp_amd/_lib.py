@@ -20,6 +20,24 @@ GAZE_ROW_INTS, GAZE_EXISTS, GAZE_COUNTS = 24, 1, 2   # row length and entry flag
 c_float_p = C.POINTER(C.c_float)
 
 
+class ProbeConv(C.Structure):
+    """crfp_probe_conv of include/crfp_hip.h: one conv of a crfp_conv_probe call (test hook)."""
+    _fields_ = [("src", C.c_void_p * 4), ("weight", C.c_void_p), ("bias", C.c_void_p), ("weight2", C.c_void_p), ("bias2", C.c_void_p),
+                ("residual", C.c_void_p), ("flow", C.c_void_p), ("dst", C.c_void_p * 3), ("dst_raw", C.c_void_p * 3),
+                ("nsrc", C.c_int), ("src_kind", C.c_int * 4), ("src_nch", C.c_int * 4), ("src_pad", C.c_int * 4),
+                ("cout", C.c_int), ("cout_split", C.c_int), ("store", C.c_int), ("ps_r", C.c_int), ("act", C.c_int), ("n_off_quads", C.c_int),
+                ("ndst", C.c_int), ("dst_q0", C.c_int * 3), ("dst_q1", C.c_int * 3), ("dst_pad", C.c_int * 3),
+                ("strict", C.c_int), ("dst_f32", C.c_int), ("post_scale", C.c_float)]
+
+
+# kernel variants crfp_conv_probe reports (CRFP_CONVK_*)
+CONV_KERNELS = ("none", "mfma_shift_ct2", "mfma_shift", "mfma_ct2", "mfma_rows4", "mfma_rows8", "split8", "split4", "split_dual", "bf16_x8",
+                "bf16_4w", "bf16_pair")
+PROBE_MODES = {"single": 0, "dual": 1, "pair": 2, "s3_chain": 3}
+PROBE_SRC = {"q4": 0, "unshuf4": 2, "flow2": 3}
+PROBE_STORE = {"q4": 0, "ps": 1, "offmask": 3}
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int), ("total_ms", C.c_double),
                 ("bytes", C.c_double), ("flops", C.c_double)]
@@ -85,6 +103,10 @@ SIGNATURES = {
     "crfp_prof_reset": (C.c_int, []),
     "crfp_debug_side_tables": (C.c_int, []),
     "crfp_prof_report": (C.c_int, [C.POINTER(ProfRecord), C.c_int]),
+    "crfp_conv_probe_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(ProbeConv), C.POINTER(ProbeConv)] + [C.c_int] * 3),
+    "crfp_conv_probe_kernel": (C.c_int, [C.c_int, C.POINTER(ProbeConv), C.POINTER(ProbeConv)] + [C.c_int] * 3 + [C.POINTER(C.c_int)]),
+    "crfp_conv_probe": (C.c_int, [C.c_int, C.POINTER(ProbeConv), C.POINTER(ProbeConv)] + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_int)] +
+                        [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_dsv_debug_fetch": (C.c_int, [C.c_char_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p] +
                              [C.POINTER(C.c_int)] * 3 + [C.c_void_p]),
 }
@@ -138,6 +160,10 @@ for _k, _row in FAMILIES.items():
 # bf16-storage twins of the C-ABI's n = 1 conveniences (crfp_dsv_forward_clip = crfp_dsv_forward_batch with n = 1, and so on)
 for _n in ("workspace_bytes", "status_offset", "forward_clip", "stream_frame"):
     SIGNATURES[f"crfp_dsv_{_n}_bf16"] = SIGNATURES[f"crfp_dsv_{_n}"]
+
+for _n in ("workspace_bytes", "kernel", ""):
+    _n = "crfp_conv_probe" + ("_" + _n if _n else "")
+    SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 
 _lib = None
 

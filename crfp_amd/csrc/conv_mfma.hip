@@ -1894,6 +1894,54 @@ static int prepare_plan(ConvArgs& am, const char* name) {
     return am.kq <= CRFP_MAX_KQ ? build_quad_descs(am, name) : 0;
 }
 
+// whether launch_conv_mfma runs plan a on a split-operand kernel (fp32 build: f16x3, bf16 build: bf16 operands) instead of the fp32 MFMA
+static bool conv_plan_splits(const ConvArgs& a) {
+    static const bool env_strict = precision_env_strict(0);
+    bool nchw_src = false;
+    for (int i = 0; i < a.nsrc; ++i) nchw_src |= a.src[i].kind == SRC_NCHW || a.src[i].kind == SRC_NCHW_SHIFT;
+    return a.wsplit && !(env_strict || a.strict) && (a.kq & 3) == 0 && !nchw_src && a.kq <= CRFP_MAX_KQ;
+}
+
+// The kernel launch_conv_mfma runs for a plan that passed its checks (the lab library's experiments branch off before this is asked, and its
+// cout-tile knob may forbid the two-tile fp32-MFMA kernels: pair_ctiles)
+static ConvKernel select_kernel(const ConvArgs& a, bool pair_ctiles) {
+    const bool split = conv_plan_splits(a);
+    const bool ct2 = !split && pair_ctiles && a.ctiles % 2 == 0;  // split: <2,1> needs 93 KB of LDS (1 workgroup per CU): slower than 2 x <1,1>
+    if (split) {
+#ifdef CRFP_ACT_BF16
+        // (8-row tiles, conv3x3_bf16_kernel<2>: 1.25 instead of 1.5 ds_read_b128 per MFMA and half the weight staging, but 450
+        // workgroups on 256 CUs -- measured neutral to -8 % per conv, so 4-row tiles stay.  A register prefetch two chunks deep
+        // (126 VGPRs, still 4 workgroups per CU) was also slower: 32->32 conv 15.2 -> 16.3 us, offset / mask head 70.8 -> 74.0.)
+        // 8-wave kernel, two chunks per staging phase, for the 32-cout layers with an even chunk count: same-box 32 -> 32 convs 16.0 ->
+        // 15.1 us, conv2(+x) 17.7 -> 17.0, conv_fuse 22.2 -> 21.6, identical values; block0 (5 chunks: a half-empty last stage) 25.4 -> 26.0,
+        // so odd chunk counts keep the 4-wave kernel
+        // (for layers with several cout tiles it loses: FNet dec2a 36 -> 43 us, enc3b 22 -> 26, the pixel-shuffle heads +0..1 us)
+        // ... and only while its 8-row tiles fill no more than one round of the chip's 512 slots (two 60 KB workgroups per CU): a lock-step
+        // batch of clips is several rounds, where tile granularity no longer matters and the 4-wave kernel's four workgroups per CU overlap
+        // more of each other's load / MFMA / store phases (round 4, same box, 4 clips: res.main0 15.1 -> 14.1 us per clip, conv_fuse 14.7 -> 14.0,
+        // conv1 9.9 -> 9.2)
+        constexpr int x8_max_wgs = 512;   // fixed in the product: the x8 / 4-wave choice is part of the per-clip bit-identity contract
+        if (a.ctiles == 1 && ((a.kq >> 2) & 1) == 0 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + B8_TH - 1) / B8_TH) <= x8_max_wgs)
+            return CK_BF16_X8;
+        return CK_BF16_4W;
+#else
+        // 8-wave single-accumulator kernel for the convs with one cout tile (the 32-cout layers: one round of 450 workgroups
+        // instead of 1.17 rounds of 900; same-box: conv1 26.4 -> 24.6 us, conv2 28.7 -> 26.1, block0 46.0 -> 43.2, main0 40.0 ->
+        // 38.0, clip -1.5 %); with several cout tiles the 4-wave kernel stays (offset/mask head 114.0 vs 117.7 us)
+        constexpr int s8_max_wgs = 1 << 30;   // (the lab library's CRFP_F32_S8_MAX_WGS lowers it: launch_conv_lab)
+        if (a.ctiles == 1 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + S8_TH - 1) / S8_TH) <= s8_max_wgs) return CK_SPLIT8;
+        return CK_SPLIT4;
+#endif
+    }
+    if (a.src[0].kind == SRC_NCHW_SHIFT) return ct2 ? CK_MFMA_SHIFT_CT2 : CK_MFMA_SHIFT;   // SPyNet's 7x7-as-3x3 convolutions: 18 ... 144 K-quads, two chunks per staging phase
+    if (ct2) return CK_MFMA_CT2;
+    // few 8-row tiles (the LR-resolution convs of a single streamed frame: 115 workgroups for 180 x 320): 4-row tiles spread the
+    // same latency-bound work over twice as many CUs
+    const int tiles = ((a.W + TW - 1) / TW) * ((a.H + 7) / 8);
+    return (long long)tiles * a.ctiles * a.N < 512 ? CK_MFMA_ROWS4 : CK_MFMA_ROWS8;
+}
+ConvKernel conv_select_kernel(const ConvArgs& a) { return select_kernel(a, true); }
+
 int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
     if (a.kq & 1 || a.kq < 2 || a.ctiles < 1 || a.nsrc < 1 || a.nsrc > CRFP_MAX_SRC) {
         set_error("conv_mfma %s: bad plan (kq=%d ctiles=%d nsrc=%d)", name, a.kq, a.ctiles, a.nsrc);
@@ -1915,11 +1963,10 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         }
     }
     static const bool env_strict = precision_env_strict(0);
-    const bool use_split = !(env_strict || a.strict);
-    bool ct2 = a.ctiles % 2 == 0;
-    bool nchw_src = false, s3_src = false;
-    for (int i = 0; i < a.nsrc; ++i) { nchw_src |= a.src[i].kind == SRC_NCHW || a.src[i].kind == SRC_NCHW_SHIFT; s3_src |= a.src[i].kind == SRC_S3; }
-    const bool split = a.wsplit && use_split && (a.kq & 3) == 0 && !nchw_src && a.kq <= CRFP_MAX_KQ;
+    bool ct2 = a.ctiles % 2 == 0;   // the lab library's cout-tile knobs may clear it
+    bool s3_src = false;
+    for (int i = 0; i < a.nsrc; ++i) s3_src |= a.src[i].kind == SRC_S3;
+    const bool split = conv_plan_splits(a);
     const bool uses_s3 = a.s3_dst != nullptr || s3_src;
     if (uses_s3 && (!split || !conv_s3_supported() || (a.s3_dst && (a.store != ST_Q4 || (a.cout & 7))))) {
         set_error("conv_mfma %s: SRC_S3 / s3_dst need the default f16x3 kernel, ST_Q4 and cout %% 8 == 0", name);
@@ -1940,58 +1987,36 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         if (rc || done) return rc;
     }
 #endif
-    if (split) ct2 = false;  // <2,1> needs 93 KB of LDS (1 workgroup per CU): slower than 2 x <1,1>
-    const int TH = (ct2 || split) ? 4 : 8;
-    const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
-    if (split) {
+    const int tw = (a.W + TW - 1) / TW;
+    const int tiles4 = tw * ((a.H + 3) / 4), tiles8 = tw * ((a.H + 7) / 8);   // 4-row / 8-row tiles of 64 columns
+    const int nz = a.N * (a.ksplit > 0 ? a.ksplit : 1);
+    switch (select_kernel(a, ct2)) {
 #ifdef CRFP_ACT_BF16
-        // (8-row tiles, conv3x3_bf16_kernel<2>: 1.25 instead of 1.5 ds_read_b128 per MFMA and half the weight staging, but 450
-        // workgroups on 256 CUs -- measured neutral to -8 % per conv, so 4-row tiles stay.  A register prefetch two chunks deep
-        // (126 VGPRs, still 4 workgroups per CU) was also slower: 32->32 conv 15.2 -> 16.3 us, offset / mask head 70.8 -> 74.0.)
-        // 8-wave kernel, two chunks per staging phase, for the 32-cout layers with an even chunk count: same-box 32 -> 32 convs 16.0 ->
-        // 15.1 us, conv2(+x) 17.7 -> 17.0, conv_fuse 22.2 -> 21.6, identical values; block0 (5 chunks: a half-empty last stage) 25.4 -> 26.0,
-        // so odd chunk counts keep the 4-wave kernel
-        // (for layers with several cout tiles it loses: FNet dec2a 36 -> 43 us, enc3b 22 -> 26, the pixel-shuffle heads +0..1 us)
-        // ... and only while its 8-row tiles fill no more than one round of the chip's 512 slots (two 60 KB workgroups per CU): a lock-step
-        // batch of clips is several rounds, where tile granularity no longer matters and the 4-wave kernel's four workgroups per CU overlap
-        // more of each other's load / MFMA / store phases (round 4, same box, 4 clips: res.main0 15.1 -> 14.1 us per clip, conv_fuse 14.7 -> 14.0,
-        // conv1 9.9 -> 9.2)
-        constexpr int x8_max_wgs = 512;   // fixed in the product: the x8 / 4-wave choice is part of the per-clip bit-identity contract
-        if (a.ctiles == 1 && ((a.kq >> 2) & 1) == 0 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + B8_TH - 1) / B8_TH) <= x8_max_wgs) {
-            const int tiles8 = ((a.W + TW - 1) / TW) * ((a.H + B8_TH - 1) / B8_TH);
+        case CK_BF16_X8: {
+            static_assert(B8_TH == 8, "conv3x3_bf16x8_kernel walks 8-row tiles");
             conv3x3_bf16x8_kernel<<<dim3(tiles8 * a.ctiles, 1, a.N), B8_NT, 0, s>>>(am);
-        } else
-            conv3x3_bf16_kernel<1><<<dim3(tiles * a.ctiles, 1, a.N), 256, 0, s>>>(am);
+            break;
+        }
+        case CK_BF16_4W: conv3x3_bf16_kernel<1><<<dim3(tiles4 * a.ctiles, 1, a.N), 256, 0, s>>>(am); break;
 #else
-        // 8-wave single-accumulator kernel for the convs with one cout tile (the 32-cout layers: one round of 450 workgroups
-        // instead of 1.17 rounds of 900; same-box: conv1 26.4 -> 24.6 us, conv2 28.7 -> 26.1, block0 46.0 -> 43.2, main0 40.0 ->
-        // 38.0, clip -1.5 %); with several cout tiles the 4-wave kernel stays (offset/mask head 114.0 vs 117.7 us)
-        constexpr int s8_max_wgs = 1 << 30;   // (the lab library's CRFP_F32_S8_MAX_WGS lowers it: launch_conv_lab)
-        if (a.ctiles == 1 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + S8_TH - 1) / S8_TH) <= s8_max_wgs) {
+        case CK_SPLIT8: {
 #ifdef CRFP_S8_NW
             constexpr int s8nw = CRFP_S8_NW;
 #else
             constexpr int s8nw = S8_TH;
 #endif
-            const int tiles8 = ((a.W + TW - 1) / TW) * ((a.H + s8nw - 1) / s8nw);
-            conv3x3_split8_kernel<s8nw><<<dim3(tiles8 * a.ctiles, 1, a.N), 64 * s8nw, 0, s>>>(am);
-        } else
-            conv3x3_split_kernel<1, 1, 2><<<dim3(tiles * a.ctiles, 1, a.N), 256, 0, s>>>(am);
+            const int tiles_s8 = tw * ((a.H + s8nw - 1) / s8nw);
+            conv3x3_split8_kernel<s8nw><<<dim3(tiles_s8 * a.ctiles, 1, a.N), 64 * s8nw, 0, s>>>(am);
+            break;
+        }
+        case CK_SPLIT4: conv3x3_split_kernel<1, 1, 2><<<dim3(tiles4 * a.ctiles, 1, a.N), 256, 0, s>>>(am); break;
 #endif
-    } else if (a.src[0].kind == SRC_NCHW_SHIFT) {   // SPyNet's 7x7-as-3x3 convolutions: 18 ... 144 K-quads, two chunks per staging phase
-        const int tiles4 = ((a.W + TW - 1) / TW) * ((a.H + 3) / 4);
-        const int nz = a.N * (a.ksplit > 0 ? a.ksplit : 1);
-        if (ct2) conv3x3_mfma_kernel<2, 1, 2><<<dim3(tiles4 * (a.ctiles / 2), 1, nz), 256, 0, s>>>(a);
-        else conv3x3_mfma_kernel<1, 1, 2><<<dim3(tiles4 * a.ctiles, 1, nz), 256, 0, s>>>(a);
-    } else if (ct2) {
-        conv3x3_mfma_kernel<2, 1><<<dim3(tiles * (a.ctiles / 2), 1, a.N), 256, 0, s>>>(a);
-    } else if ((long long)tiles * a.ctiles * a.N < 512) {
-        // few 8-row tiles (the LR-resolution convs of a single streamed frame: 115 workgroups for 180 x 320): 4-row tiles spread the
-        // same latency-bound work over twice as many CUs
-        const int tiles4 = ((a.W + TW - 1) / TW) * ((a.H + 3) / 4);
-        conv3x3_mfma_kernel<1, 1><<<dim3(tiles4 * a.ctiles, 1, a.N), 256, 0, s>>>(a);
-    } else {
-        conv3x3_mfma_kernel<1, 2><<<dim3(tiles * a.ctiles, 1, a.N), 256, 0, s>>>(a);
+        case CK_MFMA_SHIFT_CT2: conv3x3_mfma_kernel<2, 1, 2><<<dim3(tiles4 * (a.ctiles / 2), 1, nz), 256, 0, s>>>(a); break;
+        case CK_MFMA_SHIFT: conv3x3_mfma_kernel<1, 1, 2><<<dim3(tiles4 * a.ctiles, 1, nz), 256, 0, s>>>(a); break;
+        case CK_MFMA_CT2: conv3x3_mfma_kernel<2, 1><<<dim3(tiles4 * (a.ctiles / 2), 1, a.N), 256, 0, s>>>(a); break;
+        case CK_MFMA_ROWS4: conv3x3_mfma_kernel<1, 1><<<dim3(tiles4 * a.ctiles, 1, a.N), 256, 0, s>>>(a); break;
+        case CK_MFMA_ROWS8: conv3x3_mfma_kernel<1, 2><<<dim3(tiles8 * a.ctiles, 1, a.N), 256, 0, s>>>(a); break;
+        default: set_error("conv_mfma %s: no kernel for this plan in this build", name); return CRFP_E_UNSUPPORTED;
     }
     CRFP_CHECK_LAUNCH();
     return 0;
@@ -1999,7 +2024,8 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
 
 
 // Two convs of the same shape in one launch (fp32 build: conv3x3_split_dual_kernel); anything it does not cover runs as two launches.
-int launch_conv_mfma_dual(const ConvArgs& a0, const char* name0, const ConvArgs& a1, const char* name1, const char* name_both, hipStream_t s) {
+// The decision: CK_SPLIT_DUAL, or CK_NONE for two launches.
+ConvKernel conv_select_dual(const ConvArgs& a0, const ConvArgs& a1) {
 #ifndef CRFP_ACT_BF16
 #ifndef CRFP_CONV_DUAL
 #define CRFP_CONV_DUAL 1   // A/B builds: 0 = always two launches
@@ -2017,7 +2043,19 @@ int launch_conv_mfma_dual(const ConvArgs& a0, const char* name0, const ConvArgs&
     if (CRFP_CONV_DUAL && !lab && plain_split(a0) && plain_split(a1) && a0.N == a1.N && a0.H == a1.H && a0.W == a1.W && a0.ctiles == a1.ctiles &&
         conv_s3_supported()) {
         const int tiles = ((a0.W + TW - 1) / TW) * ((a0.H + 3) / 4), w0 = tiles * a0.ctiles;
-        if ((w0 & 7) == 0) {
+        if ((w0 & 7) == 0) return CK_SPLIT_DUAL;
+    }
+#else
+    (void)a0; (void)a1;
+#endif
+    return CK_NONE;
+}
+
+int launch_conv_mfma_dual(const ConvArgs& a0, const char* name0, const ConvArgs& a1, const char* name1, const char* name_both, hipStream_t s) {
+    switch (conv_select_dual(a0, a1)) {
+#ifndef CRFP_ACT_BF16
+        case CK_SPLIT_DUAL: {
+            const int tiles = ((a0.W + TW - 1) / TW) * ((a0.H + 3) / 4), w0 = tiles * a0.ctiles;
             const ConvWork w0k = conv_work(a0), w1k = conv_work(a1);
             ProfScope prof(name_both, s, w0k.bytes + w1k.bytes, w0k.flops + w1k.flops);
             ConvArgs* am[2] = {&const_cast<ConvArgs&>(a0), &const_cast<ConvArgs&>(a1)};   // callers pass private, mutable plan copies
@@ -2030,10 +2068,12 @@ int launch_conv_mfma_dual(const ConvArgs& a0, const char* name0, const ConvArgs&
             CRFP_CHECK_LAUNCH();
             return 0;
         }
-    }
 #endif
-    const int rc = launch_conv_mfma(a0, name0, s);
-    return rc ? rc : launch_conv_mfma(a1, name1, s);
+        default: {
+            const int rc = launch_conv_mfma(a0, name0, s);
+            return rc ? rc : launch_conv_mfma(a1, name1, s);
+        }
+    }
 }
 
 // ---------------------------------------------------------------- K slices for small maps (round 6: FNet's deep layers) -- measured, NOT shipped

@@ -190,6 +190,26 @@ struct ConvArgs {
 
 bool conv_s3_supported();   // the selected conv kernels consume SRC_S3 sources (default f16x3 path of the fp32 build only)
 
+// The conv kernel variant a launcher runs (values: CRFP_CONVK_* of the C-ABI's test hook crfp_conv_probe).  conv_select_kernel is the
+// whole selection rule of launch_conv_mfma for a plan that passed its checks -- host code, geometry and plan only; conv_select_dual is
+// launch_conv_mfma_dual's: CK_SPLIT_DUAL for one launch, CK_NONE for two launches through launch_conv_mfma.
+enum ConvKernel : int {
+    CK_NONE = CRFP_CONVK_NONE,
+    CK_MFMA_SHIFT_CT2 = CRFP_CONVK_MFMA_SHIFT_CT2,   // conv3x3_mfma_kernel<2, 1, 2> (SRC_NCHW_SHIFT views, even cout tiles)
+    CK_MFMA_SHIFT = CRFP_CONVK_MFMA_SHIFT,           // conv3x3_mfma_kernel<1, 1, 2>
+    CK_MFMA_CT2 = CRFP_CONVK_MFMA_CT2,               // conv3x3_mfma_kernel<2, 1>
+    CK_MFMA_ROWS4 = CRFP_CONVK_MFMA_ROWS4,           // conv3x3_mfma_kernel<1, 1>
+    CK_MFMA_ROWS8 = CRFP_CONVK_MFMA_ROWS8,           // conv3x3_mfma_kernel<1, 2>
+    CK_SPLIT8 = CRFP_CONVK_SPLIT8,                   // conv3x3_split8_kernel (fp32 build)
+    CK_SPLIT4 = CRFP_CONVK_SPLIT4,                   // conv3x3_split_kernel<1, 1, 2> (fp32 build)
+    CK_SPLIT_DUAL = CRFP_CONVK_SPLIT_DUAL,           // conv3x3_split_dual_kernel<1, 1, 2> (fp32 build)
+    CK_BF16_X8 = CRFP_CONVK_BF16_X8,                 // conv3x3_bf16x8_kernel (bf16 build)
+    CK_BF16_4W = CRFP_CONVK_BF16_4W,                 // conv3x3_bf16_kernel<1> (bf16 build)
+    CK_BF16_PAIR = CRFP_CONVK_BF16_PAIR              // conv3x3_bf16_pair_kernel (bf16 build, launch_conv_pair)
+};
+ConvKernel conv_select_kernel(const ConvArgs& a);
+ConvKernel conv_select_dual(const ConvArgs& a0, const ConvArgs& a1);
+
 // packed row (0..ctiles*32) -> reference output channel, or -1 (padding)
 __host__ __device__ inline int conv_row_to_cout(int row, int cout, int store, int ps_r) {
     if (store == ST_PS) {

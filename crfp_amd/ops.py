@@ -349,3 +349,96 @@ def spynet_forward(params, ref, supp):
         _lib.check(L.crfp_spynet_forward(ptrs, ref.data_ptr(), supp.data_ptr(), flow.data_ptr(), n, h, w, ws.data_ptr(), ws.numel(),
                                          _stream()), "crfp_spynet_forward")
     return flow
+
+
+def _probe_desc(spec, n, h, w, dev, keep, own_sources, want_raw, elem_bytes):
+    """crfp_probe_conv for one conv of a conv_probe call -> (struct, destination tensors, raw tensors)."""
+    d = _lib.ProbeConv()
+    srcs = spec.get("srcs", []) if own_sources else []
+    d.nsrc = len(srcs)
+    cin = 0
+    for i, s in enumerate(srcs):
+        kind, t = s[0], _dev(s[1], f"srcs[{i}]")
+        keep.append(t)
+        nch = {"q4": t.shape[1], "unshuf4": 16 * t.shape[1], "flow2": 2}[kind]
+        want = {"q4": (n, nch, h, w), "unshuf4": (n, nch // 16, 4 * h, 4 * w), "flow2": (n, h, w, 2)}[kind]
+        assert tuple(t.shape) == want, f"conv_probe: source {i} ({kind}) is {tuple(t.shape)}, expected {want}"
+        d.src[i], d.src_kind[i], d.src_nch[i], d.src_pad[i] = t.data_ptr(), _lib.PROBE_SRC[kind], nch, int(s[2]) if len(s) > 2 else 0
+        cin += nch
+    for name in ("weight", "bias", "weight2", "bias2", "residual", "flow"):
+        t = spec.get(name)
+        if t is not None:
+            t = _dev(t, name)
+            keep.append(t)
+            setattr(d, name, t.data_ptr())
+    cout = spec["weight"].shape[0] + (spec["weight2"].shape[0] if spec.get("weight2") is not None else 0)
+    d.cout, d.cout_split = cout, spec["weight"].shape[0] if spec.get("weight2") is not None else 0
+    store = spec.get("store", "q4")
+    d.store, d.ps_r, d.act, d.post_scale = _lib.PROBE_STORE[store], int(spec.get("ps_r", 0)), ACT[spec.get("act", "none")], float(spec.get("post_scale", 1.0))
+    d.n_off_quads, d.strict, d.dst_f32 = int(spec.get("n_off_quads", 0)), int(bool(spec.get("strict"))), int(bool(spec.get("dst_f32")))
+    outs, raws = [], []
+    if store == "ps":
+        r = d.ps_r
+        dsts = [(0, 0, 0)]
+        shapes = [(n, cout // (r * r), h * r, w * r)]
+    else:
+        ncq = (cout + 3) // 4
+        dsts = spec.get("dsts")
+        dsts = [(0, ncq, 0)] if dsts is None else [tuple(x) + (0,) * (3 - len(x)) for x in dsts]
+        shapes = [(n, min(4 * q1, cout) - 4 * q0, h, w) for q0, q1, _ in dsts]
+    d.ndst = len(dsts)
+    for i, ((q0, q1, pad), shp) in enumerate(zip(dsts, shapes)):
+        o = torch.empty(shp, dtype=torch.float32, device=dev)
+        outs.append(o)
+        d.dst[i], d.dst_q0[i], d.dst_q1[i], d.dst_pad[i] = o.data_ptr(), q0, q1, pad
+        if want_raw and store == "q4":
+            eb = 4 if d.dst_f32 else elem_bytes
+            rw = torch.empty(n * (q1 - q0) * (h + pad) * (w + pad) * 4 * eb, dtype=torch.uint8, device=dev)
+            raws.append(rw)
+            d.dst_raw[i] = rw.data_ptr()
+    return d, outs, raws
+
+
+def conv_probe(a, b=None, mode="single", storage="f32", raw=False):
+    """Test hook (crfp_conv_probe / crfp_conv_probe_bf16): one launch of the engines' own MFMA conv kernels on the caller's tensors.
+
+    ``a`` / ``b`` describe a conv each: ``srcs`` = [(kind, tensor[, pad])] with kind "q4" ([n, c, h, w]), "unshuf4" ([n, c, 4h, 4w]) or
+    "flow2" ([n, h, w, 2]); ``weight`` / ``bias`` (and ``weight2`` / ``bias2`` for the rows behind them); ``residual``; ``flow``;
+    ``store`` "q4" (``dsts`` = [(q0, q1[, pad])] quad ranges, default one destination with everything), "ps" (``ps_r``) or "offmask"
+    (``n_off_quads``); ``act``, ``post_scale``, ``strict``, ``dst_f32``.  mode: "single", "dual" (a and b side by side), "pair" (bf16: a
+    feeds b in one launch) or "s3_chain" (fp32: a's output reaches b as the pre-split fp16 image; give a ``dsts=[]``).
+    Returns a dict: ``out`` (per conv, the list of its destination tensors, NCHW fp32; elements no lane wrote are NaN), ``status``
+    (int32 [2, n]: the range-guard word of every batch item, per conv), ``kernel`` (the variant names the launcher chose, per conv),
+    ``raw`` (with raw=True: per conv the raw bytes of each "q4" destination, pads included)."""
+    import ctypes as C
+    L = _lib.lib()
+    sfx = "_bf16" if storage == "bf16" else ""
+    first = a["srcs"][0]
+    t0 = first[1]
+    if first[0] == "flow2":
+        n, h, w = t0.shape[0], t0.shape[1], t0.shape[2]
+    else:
+        n, h, w = t0.shape[0], t0.shape[2] // (4 if first[0] == "unshuf4" else 1), t0.shape[3] // (4 if first[0] == "unshuf4" else 1)
+    dev = t0.device
+    keep = []
+    eb = 2 if storage == "bf16" else 4
+    da, outs_a, raws_a = _probe_desc(a, n, h, w, dev, keep, True, raw, eb)
+    if b is not None:
+        db, outs_b, raws_b = _probe_desc(b, n, h, w, dev, keep, mode == "dual", raw, eb)
+    m = _lib.PROBE_MODES[mode]
+    pa, pb = C.byref(da), (C.byref(db) if b is not None else None)
+    with _on(*keep):
+        nb = getattr(L, "crfp_conv_probe_workspace_bytes" + sfx)(m, pa, pb, n, h, w)
+        if nb == 0:
+            _lib.check(-1, "crfp_conv_probe_workspace_bytes" + sfx)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        status = torch.zeros((2, n), dtype=torch.int32, device=dev)
+        kern = (C.c_int * 2)()
+        _lib.check(getattr(L, "crfp_conv_probe" + sfx)(m, pa, pb, n, h, w, status.data_ptr(), kern, ws.data_ptr(), nb, _stream()),
+                   "crfp_conv_probe" + sfx)
+        torch.cuda.current_stream().synchronize()   # the workspace goes away with this call
+    res = {"out": [outs_a] + ([outs_b] if b is not None else []), "status": status,
+           "kernel": tuple(_lib.CONV_KERNELS[k] for k in kern)}
+    if raw:
+        res["raw"] = [raws_a] + ([raws_b] if b is not None else [])
+    return res

@@ -438,6 +438,80 @@ int crfp_debug_side_tables(void);
 int crfp_dsv_debug_fetch(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
                          int* c_out, int* h_out, int* w_out, void* stream);
 
+/* ---- Test hook: ONE launch of the engines' own 3x3 conv kernels on caller-supplied tensors (tests/test_gpu_conv_probe.py).  Not a product
+ * entry: every call builds the plan as the engines do (same source table, same packers, same launchers), converts the API tensors to the
+ * build's storage type (fp32, or bf16 for crfp_conv_probe_bf16), launches, converts back, and reports which kernel variant the launcher
+ * chose.  All tensors are contiguous fp32 device memory.
+ *   src[i]:   CRFP_PROBE_SRC_Q4 [n, nch, h, w] (src_pad = 1: held in padded planes with a zero pad row / column);
+ *             CRFP_PROBE_SRC_FLOW2 [n, h, w, 2] (dx, dy), nch = 2;  CRFP_PROBE_SRC_UNSHUF4 [n, nch / 16, 4h, 4w], read as pixel_unshuffle(., 4)
+ *   weight [cout, cin, 3, 3], bias [cout] (cin = sum of nch); with weight2 / bias2: rows >= cout_split come from weight2 [cout - cout_split, cin, 3, 3]
+ *   out = act(conv + bias) * post_scale (+ residual [n, cout, h, w])
+ *   store CRFP_PROBE_ST_Q4: ndst destinations, destination d receives output quads (4 channels each) [dst_q0[d], dst_q1[d]) as
+ *             dst[d] [n, min(4 q1, cout) - 4 q0, h, w]; dst_pad[d] = 1: held in padded planes on the device.  Every destination is filled
+ *             with 0xFF bytes before the launch, so an element no lane wrote comes back NaN.  dst_raw[d] (optional) receives the raw
+ *             destination buffer, n * (q1 - q0) * (h + pad) * (w + pad) * 4 elements of the storage type (dst_f32: float).
+ *   store CRFP_PROBE_ST_PS (ps_r in {2, 4}): dst[0] [n, cout / r^2, h r, w r] = pixel_shuffle(out, r)
+ *   store CRFP_PROBE_ST_OFFMASK: dst[0] [n, cout, h, w] float; quads < n_off_quads hold 10 tanh(conv) + flow [n, h, w, 2] flipped to (y, x),
+ *             the rest sigmoid(conv)
+ *   strict: the plain fp32 MFMA (CRFP_DSV_STRICT_F32);  dst_f32: bf16 build, one whole ST_Q4 destination stored as float.
+ * mode CRFP_PROBE_SINGLE: conv a.  CRFP_PROBE_DUAL: a and b through launch_conv_mfma_dual.  CRFP_PROBE_PAIR (bf16 build only, else
+ * CRFP_E_UNSUPPORTED): a (32 couts, no destination) feeding b (32 -> 32) in one launch; b's source table is ignored.  CRFP_PROBE_S3_CHAIN
+ * (fp32 build only): a stores its output only as the pre-split fp16 pair image (a.ndst = 0), b reads it as its single source.
+ * status: n words for conv a followed by n words for conv b (device memory, 2 n unsigned): word k is nonzero when batch item k stored a
+ * value an fp16 operand cannot hold.  kernel (host memory, 2 ints): CRFP_CONVK_* of conv a and conv b; one launch for both (dual kernel,
+ * pair kernel) reports the same value twice; CRFP_CONVK_NONE for an absent conv.  crfp_conv_probe_kernel answers the same question on the
+ * host alone (no launch, tensor pointers ignored): *_bf16 for the bf16 build. */
+#define CRFP_PROBE_MAX_SRC 4
+#define CRFP_PROBE_MAX_DST 3
+#define CRFP_PROBE_SRC_Q4 0
+#define CRFP_PROBE_SRC_UNSHUF4 2
+#define CRFP_PROBE_SRC_FLOW2 3
+#define CRFP_PROBE_ST_Q4 0
+#define CRFP_PROBE_ST_PS 1
+#define CRFP_PROBE_ST_OFFMASK 3
+#define CRFP_PROBE_SINGLE 0
+#define CRFP_PROBE_DUAL 1
+#define CRFP_PROBE_PAIR 2
+#define CRFP_PROBE_S3_CHAIN 3
+#define CRFP_CONVK_NONE 0
+#define CRFP_CONVK_MFMA_SHIFT_CT2 1 /* conv3x3_mfma_kernel<2, 1, 2> */
+#define CRFP_CONVK_MFMA_SHIFT 2     /* conv3x3_mfma_kernel<1, 1, 2> */
+#define CRFP_CONVK_MFMA_CT2 3       /* conv3x3_mfma_kernel<2, 1> */
+#define CRFP_CONVK_MFMA_ROWS4 4     /* conv3x3_mfma_kernel<1, 1> */
+#define CRFP_CONVK_MFMA_ROWS8 5     /* conv3x3_mfma_kernel<1, 2> */
+#define CRFP_CONVK_SPLIT8 6         /* conv3x3_split8_kernel */
+#define CRFP_CONVK_SPLIT4 7         /* conv3x3_split_kernel<1, 1, 2> */
+#define CRFP_CONVK_SPLIT_DUAL 8     /* conv3x3_split_dual_kernel<1, 1, 2> */
+#define CRFP_CONVK_BF16_X8 9        /* conv3x3_bf16x8_kernel */
+#define CRFP_CONVK_BF16_4W 10       /* conv3x3_bf16_kernel<1> */
+#define CRFP_CONVK_BF16_PAIR 11     /* conv3x3_bf16_pair_kernel */
+typedef struct crfp_probe_conv {
+    const float* src[CRFP_PROBE_MAX_SRC];
+    const float* weight;
+    const float* bias;
+    const float* weight2;
+    const float* bias2;
+    const float* residual;
+    const float* flow;
+    float* dst[CRFP_PROBE_MAX_DST];
+    void* dst_raw[CRFP_PROBE_MAX_DST];
+    int nsrc;
+    int src_kind[CRFP_PROBE_MAX_SRC], src_nch[CRFP_PROBE_MAX_SRC], src_pad[CRFP_PROBE_MAX_SRC];
+    int cout, cout_split, store, ps_r, act, n_off_quads;
+    int ndst;
+    int dst_q0[CRFP_PROBE_MAX_DST], dst_q1[CRFP_PROBE_MAX_DST], dst_pad[CRFP_PROBE_MAX_DST];
+    int strict, dst_f32;
+    float post_scale;
+} crfp_probe_conv;
+size_t crfp_conv_probe_workspace_bytes(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w);   /* 0: refused (crfp_last_error) */
+int crfp_conv_probe_kernel(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w, int* kernel);
+int crfp_conv_probe(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w, unsigned* status, int* kernel,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t crfp_conv_probe_workspace_bytes_bf16(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w);
+int crfp_conv_probe_kernel_bf16(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w, int* kernel);
+int crfp_conv_probe_bf16(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w, unsigned* status, int* kernel,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- The benchmark-only regional wiring, model/CRFP_runtime.py::MRCF_simple_v18.forward(lrs, fvs, warp_size) (:8469-8664;
  * built and timed by the reference's test_runtime.py:41,142) as ONE call per clip.  mid_channels = 32, split_ratio = 3, offset_prop.
  * Same conventions as the CRFP_DSV engine above: parameters as CRFP_RT_NUM_PARAMS device pointers in state_dict order

@@ -204,6 +204,122 @@ int main() {
                     }
         EXPECT(crfp_stub_launches() == l0 + accepted);
     }
+    // the conv probe (test hook): sizing, the launcher's kernel-selection rule, every refusal before the first launch, whole calls on the stub
+    {
+        crfp_probe_conv q;
+        std::memset(&q, 0, sizeof(q));
+        q.nsrc = 1; q.src_kind[0] = CRFP_PROBE_SRC_Q4; q.src_nch[0] = 32; q.cout = 32; q.store = CRFP_PROBE_ST_Q4; q.post_scale = 1.0f;
+        q.ndst = 1; q.dst_q1[0] = 8;
+        int k[2] = {-1, -1};
+        const long l0 = crfp_stub_launches();
+        const size_t w32 = crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130);
+        const size_t w16 = crfp_conv_probe_workspace_bytes_bf16(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130);
+        EXPECT(w32 > 2ull * 3 * 8 * 9 * 130 * 16 && w16 > 0 && w16 < w32);
+        // selection: one cout tile -> the 8-wave kernels; the bf16 build's 512-slot rule on both sides; two tiles -> the 4-wave kernels
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &q, nullptr, 19, 72, 192, k) == 0 && k[0] == CRFP_CONVK_SPLIT8 && k[1] == CRFP_CONVK_NONE);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_SINGLE, &q, nullptr, 19, 72, 192, k) == 0 && k[0] == CRFP_CONVK_BF16_4W);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_SINGLE, &q, nullptr, 16, 64, 256, k) == 0 && k[0] == CRFP_CONVK_BF16_X8);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_SINGLE, &q, nullptr, 1, 72, 192, k) == 0 && k[0] == CRFP_CONVK_BF16_X8);
+        crfp_probe_conv s = q;
+        s.strict = 1;
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &s, nullptr, 1, 72, 192, k) == 0 && k[0] == CRFP_CONVK_MFMA_ROWS4);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &s, nullptr, 19, 72, 192, k) == 0 && k[0] == CRFP_CONVK_MFMA_ROWS8);
+        crfp_probe_conv big = q;
+        big.src_nch[0] = 324;   // over the per-quad descriptor table: fp32 MFMA
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &big, nullptr, 1, 4, 64, k) == 0 && k[0] == CRFP_CONVK_MFMA_ROWS4);
+        crfp_probe_conv two = q;
+        two.cout = 64; two.dst_q1[0] = 16;
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &two, nullptr, 2, 8, 65, k) == 0 && k[0] == CRFP_CONVK_SPLIT4);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_SINGLE, &two, nullptr, 2, 8, 65, k) == 0 && k[0] == CRFP_CONVK_BF16_4W);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &s, nullptr, 1, 72, 192, nullptr) == CRFP_E_BADARG);
+        s = two; s.strict = 1;
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_SINGLE, &s, nullptr, 2, 8, 65, k) == 0 && k[0] == CRFP_CONVK_MFMA_CT2);
+        // dual: 4-row tiles * cout tiles a multiple of 8 or not
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_DUAL, &two, &two, 2, 8, 65, k) == 0 && k[0] == CRFP_CONVK_SPLIT_DUAL && k[1] == CRFP_CONVK_SPLIT_DUAL);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_DUAL, &two, &two, 2, 9, 64, k) == 0 && k[0] == CRFP_CONVK_SPLIT4 && k[1] == CRFP_CONVK_SPLIT4);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_DUAL, &two, &q, 2, 8, 65, k) == 0 && k[0] == CRFP_CONVK_SPLIT4 && k[1] == CRFP_CONVK_SPLIT8);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_DUAL, &two, &two, 2, 8, 65, k) == 0 && k[0] == CRFP_CONVK_BF16_4W);
+        // pair / S3 chain: each in its own build only
+        crfp_probe_conv a0 = q;
+        a0.ndst = 0;
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62, k) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62, k) == 0 && k[0] == CRFP_CONVK_BF16_PAIR && k[1] == CRFP_CONVK_BF16_PAIR);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, k) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, k) == 0 && k[0] == CRFP_CONVK_SPLIT8 && k[1] == CRFP_CONVK_SPLIT4);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62) > 0);
+        // refusals of the sizing function
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, &a0, nullptr, 2, 8, 62) == 0);     // no destination
+        EXPECT(std::strstr(crfp_last_error_string(), "destinations") != nullptr);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, nullptr, nullptr, 2, 8, 62) == 0);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_DUAL, &q, nullptr, 2, 8, 62) == 0);
+        EXPECT(crfp_conv_probe_workspace_bytes(4, &q, nullptr, 2, 8, 62) == 0 && crfp_conv_probe_workspace_bytes(-1, &q, nullptr, 2, 8, 62) == 0);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, &q, nullptr, 0, 8, 62) == 0);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, &q, nullptr, 2, 8, 0) == 0);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, &q, nullptr, 70000, 8, 62) == 0);
+        for (int f = 0; f < 10; ++f) {
+            crfp_probe_conv d = q;
+            switch (f) {
+                case 0: d.nsrc = 5; break;
+                case 1: d.src_kind[0] = 1; break;                              // NCHW sources are not the probe's
+                case 2: d.src_kind[0] = CRFP_PROBE_SRC_UNSHUF4; d.src_nch[0] = 24; break;
+                case 3: d.src_kind[0] = CRFP_PROBE_SRC_FLOW2; d.src_nch[0] = 3; break;
+                case 4: d.src_pad[0] = 2; break;
+                case 5: d.cout = 0; break;
+                case 6: d.act = 9; break;
+                case 7: d.dst_q1[0] = 9; break;
+                case 8: d.store = CRFP_PROBE_ST_PS; d.ps_r = 3; break;
+                default: d.store = CRFP_PROBE_ST_OFFMASK; d.n_off_quads = 9; break;
+            }
+            EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, &d, nullptr, 2, 8, 62) == 0);
+            EXPECT(crfp_conv_probe_workspace_bytes_bf16(CRFP_PROBE_SINGLE, &d, nullptr, 2, 8, 62) == 0);
+        }
+        // the call: null tensors, null status / kernel, a short workspace -- all before the first launch
+        unsigned* const st = reinterpret_cast<unsigned*>(16);
+        EXPECT(crfp_conv_probe(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130, st, k, p16, w32, nullptr) == CRFP_E_BADARG);   // null tensors
+        q.src[0] = p16; q.weight = p16; q.bias = p16; q.dst[0] = p16;
+        EXPECT(crfp_conv_probe(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130, nullptr, k, p16, w32, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_conv_probe(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130, st, nullptr, p16, w32, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_conv_probe(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130, st, k, p16, w32 - 1, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_conv_probe(CRFP_PROBE_SINGLE, &q, nullptr, 3, 9, 130, st, k, nullptr, w32, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_stub_launches() == l0);
+        // accepted calls on the stub runtime, device pointers fabricated: every mode, both builds, ragged and padded plans
+        char* const dev = reinterpret_cast<char*>(0x200000000000ull);
+        auto fab = [&](crfp_probe_conv& d, int slot) {
+            float* const base = reinterpret_cast<float*>(dev + ((size_t)slot << 32));
+            for (int i = 0; i < CRFP_PROBE_MAX_SRC; ++i) d.src[i] = base + (i << 24);
+            d.weight = base + (5 << 24); d.bias = base + (6 << 24); d.weight2 = base + (7 << 24); d.bias2 = base + (8 << 24);
+            d.flow = base + (9 << 24);
+            for (int i = 0; i < CRFP_PROBE_MAX_DST; ++i) { d.dst[i] = base + ((10 + i) << 24); d.dst_raw[i] = base + ((13 + i) << 24); }
+        };
+        crfp_probe_conv m = q;
+        m.nsrc = 4; m.src_nch[0] = 24; m.src_pad[0] = 1; m.src_kind[1] = CRFP_PROBE_SRC_Q4; m.src_nch[1] = 8;
+        m.src_kind[2] = CRFP_PROBE_SRC_UNSHUF4; m.src_nch[2] = 64; m.src_kind[3] = CRFP_PROBE_SRC_FLOW2; m.src_nch[3] = 2;
+        m.cout = 38; m.ndst = 3; m.dst_q0[0] = 0; m.dst_q1[0] = 3; m.dst_q0[1] = 3; m.dst_q1[1] = 4; m.dst_pad[1] = 1; m.dst_q0[2] = 4; m.dst_q1[2] = 10;
+        m.residual = p16; m.act = CRFP_ACT_LRELU01;
+        fab(m, 0);
+        crfp_probe_conv om = q;
+        om.cout = 216; om.cout_split = 144; om.store = CRFP_PROBE_ST_OFFMASK; om.n_off_quads = 36; om.dst_q1[0] = 54;
+        fab(om, 1);
+        crfp_probe_conv ps = q;
+        ps.cout = 64; ps.store = CRFP_PROBE_ST_PS; ps.ps_r = 4;
+        fab(ps, 2);
+        fab(two, 3); fab(a0, 4); fab(q, 5);
+        void* const wsp = dev + (100ull << 32);
+        const crfp_probe_conv* singles[] = {&m, &om, &ps, &two, &q};
+        for (const crfp_probe_conv* c : singles)
+            for (const auto& g : {std::initializer_list<int>{1, 1, 1}, {3, 17, 33}, {2, 9, 130}}) {
+                const int n = g.begin()[0], h = g.begin()[1], w = g.begin()[2];
+                EXPECT(crfp_conv_probe(CRFP_PROBE_SINGLE, c, nullptr, n, h, w, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_SINGLE, c, nullptr, n, h, w), nullptr) == 0);
+                EXPECT(crfp_conv_probe_bf16(CRFP_PROBE_SINGLE, c, nullptr, n, h, w, st, k, wsp, crfp_conv_probe_workspace_bytes_bf16(CRFP_PROBE_SINGLE, c, nullptr, n, h, w), nullptr) == 0);
+            }
+        EXPECT(crfp_conv_probe(CRFP_PROBE_DUAL, &two, &m, 2, 8, 65, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_DUAL, &two, &m, 2, 8, 65), nullptr) == 0);
+        EXPECT(crfp_conv_probe(CRFP_PROBE_DUAL, &two, &two, 2, 8, 65, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_DUAL, &two, &two, 2, 8, 65), nullptr) == 0);
+        EXPECT(k[0] == CRFP_CONVK_SPLIT_DUAL);
+        EXPECT(crfp_conv_probe_bf16(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62, st, k, wsp, crfp_conv_probe_workspace_bytes_bf16(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62), nullptr) == 0);
+        EXPECT(crfp_conv_probe_bf16(CRFP_PROBE_PAIR, &a0, &two, 2, 8, 62, st, k, wsp, (size_t)1 << 40, nullptr) == CRFP_E_UNSUPPORTED);   // conv b must be 32 -> 32
+        EXPECT(crfp_conv_probe(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62), nullptr) == 0);
+        EXPECT(crfp_stub_launches() > l0);
+    }
     // ---- whole engine calls on the stub runtime (tools/asan_host/hip_stub.cpp: every HIP call succeeds, no kernel runs): the host side of a
     // call -- argument checks, Layout arenas, the launch-argument tables of ~50 launches per frame, the fork / join of the side stream, the
     // per-thread stream table and crfp_shutdown() -- under the sanitizers.  Device pointers are fabricated and never dereferenced on the host.
