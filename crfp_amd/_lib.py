@@ -32,8 +32,8 @@ class ProbeConv(C.Structure):
 
 # kernel variants crfp_conv_probe reports (CRFP_CONVK_*)
 CONV_KERNELS = ("none", "mfma_shift_ct2", "mfma_shift", "mfma_ct2", "mfma_rows4", "mfma_rows8", "split8", "split4", "split_dual", "bf16_x8",
-                "bf16_4w", "bf16_pair")
-PROBE_MODES = {"single": 0, "dual": 1, "pair": 2, "s3_chain": 3}
+                "bf16_4w", "bf16_pair", "split_pair")
+PROBE_MODES = {"single": 0, "dual": 1, "pair": 2, "s3_chain": 3, "pair_f32": 4}
 PROBE_SRC = {"q4": 0, "unshuf4": 2, "flow2": 3}
 PROBE_STORE = {"q4": 0, "ps": 1, "offmask": 3}
 

@@ -1134,6 +1134,300 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     S8_STAMP_END
 }
 
+// ---------------------------------------------------------------- f16x3s: TWO 3x3 convs in one launch, the tensor between them in LDS
+// The fp32 form of conv3x3_bf16_pair_kernel (further down; same scheme: conv A on the 10 x 64 region conv B's 8-row output tile needs,
+// waves 0-3 three 32-pixel tiles, waves 4-7 two) with the arithmetic of conv3x3_split8_kernel: every accumulator sees the MFMAs of the
+// stand-alone kernel in the same order, conv A's result goes through the stand-alone epilogue's arithmetic (2^-11, activation, post_scale,
+// range guard on conv A's own status word) and then through split_f16x4 -- the values conv B's loader would form from the stored fp32
+// tensor -- so the pair is bit-identical to the two launches.
+// LDS is time-shared, 76 928 B = two workgroups per CU:
+//   conv A, per chunk:  input halo [4 planes][12 x 64 + 2] x 16 B = 49 280  |  weight stage 27 648
+//   conv B, per chunk:  ONE 16-channel half of the intermediate [4 planes][10 x 66] x 16 B = 42 240 in the dead halo  |  conv B's weight stage
+// Conv A's accumulators wait in registers: couts 0-15 (registers 0-7 of each pixel tile) are written before conv B's chunk 0, couts 16-31
+// before its chunk 1, into the same 42 KB.  Conv B's first weight stage rides under conv A's last chunk, its second under its own chunk 0.
+// Registers (128 at 4 waves per SIMD, no scratch): 48 conv A accumulators and split8's even prefetch (32 halo + 16 weight registers per
+// thread) do not fit.  So the output tile is 60 columns wide -- the input halo is then 12 x 64 pixels, one wave-row per prefetch slot, and the
+// 640-wide map still takes 11 column tiles -- and the prefetch is divided by what a wave has left: waves 0-3 (three tiles) hold quads 0-1
+// of every halo pixel and one weight slot (24 + 4 registers), waves 4-7 (two tiles) quads 2-3 and six weight slots (24 + 24).  Conv A's
+// columns 62-63 read two pixels of the next halo row; they and everything outside the image are stored as exact zeros.
+constexpr int PF_NT = 512, PF_OW = 60, PF_IH = 10, PF_IW = 64, PF_LH = 12, PF_LW = 64;
+constexpr int PF_NEL = PF_LH * PF_LW, PF_PL = PF_NEL + 2;   // 768 input halo pixels; a plane ends with the two pixels the last row's taps overrun into
+constexpr int PF_MP = PF_IW + 2, PF_MEL = PF_IH * PF_MP;    // intermediate rows of 64 + 2 zero columns
+constexpr int PF_NWS = (S8_WPC + PF_NT - 1) / PF_NT;        // conv B's second weight stage: even slots
+constexpr int PF_NWL = 1, PF_NWH = (S8_WPC - 256 * PF_NWL + 255) / 256;   // weight slots of a thread of waves 0-3 / waves 4-7
+static_assert(PF_MEL <= PF_PL, "the intermediate half lives in the input halo's LDS");
+static_assert(PF_NEL == 3 * 256, "three wave-rows per thread of either wave group");
+
+struct PairB {          // what conv B adds to conv A's plan: its weights, bias, activation, destinations, residual, status word
+    const void* wsplit_sa;
+    const float* bpk;
+    const float* resid;
+    long long resid_bstride;
+    ConvDst dst[CRFP_MAX_DST];
+    int ndst, cout, act;
+    float post_scale;
+    float* s3_dst;
+    long long s3_bstride;
+    unsigned* ovf;
+    int ovf_div, ovf_add, ovf_skip0;
+};
+
+// conv A's chunk loop for one wave group.  NTA = 3: waves 0-3, quads 0-1 of the halo, weight vectors [0, 256); NTA = 2: waves 4-7, quads 2-3,
+// weight vectors [256, 1728).  Ends with conv B's first weight stage in wlds (fetched under the last chunk, staged behind the barrier
+// that retires conv A's reads).  Thread (wave & 3, lane) holds halo pixels (row (wave & 3) + 4 t, column lane), t = 0..2.
+template <int NTA>
+__device__ __forceinline__ void pair_conv_a(const ConvArgs& a, const bf16x8* __restrict__ wpb, int ns, int ty0, int tx0, int tid, int lane, int wave,
+                                            bf16x8* tile, bf16x8* wlds, f32x16 (&accA)[3]) {
+    constexpr int P = NTA == 3 ? 0 : 1, NW = NTA == 3 ? PF_NWL : PF_NWH;
+    const int j = lane & 31, h = lane >> 5;
+    const int H = a.H, W = a.W;
+    const int gx = tx0 + lane - 2, cgx = min(max(gx, 0), W - 1);
+    const int w3 = wave & 3;
+    const int widx0 = tid;   // weight vector of slot k: tid + 256 k (waves 4-7: tid >= 256)
+    const int nchunks = a.kq >> 2;
+    const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(a.wsplit_sa);
+    {   // accumulators start at 2^11 * bias
+        const float4* __restrict__ bp = reinterpret_cast<const float4*>(a.bpk);
+        int hb = h;   // opaque copy: the two wave groups' loads stay inside their own paths
+        asm volatile("" : "+v"(hb));
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 bq = bp[2 * g + hb];
+#pragma unroll
+            for (int k = 0; k < NTA; ++k) {
+                accA[k][4 * g + 0] = bq.x * F16_RES_SCALE; accA[k][4 * g + 1] = bq.y * F16_RES_SCALE;
+                accA[k][4 * g + 2] = bq.z * F16_RES_SCALE; accA[k][4 * g + 3] = bq.w * F16_RES_SCALE;
+            }
+        }
+    }
+    f32x4 rqa[3], rqb[3];
+    bf16x8 rws[NW];
+    int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+#define CRFP_PA_WEIGHTS(WP, CH)                                                                           \
+    _Pragma("unroll") for (int k = 0; k < NW; ++k)                                                        \
+        rws[k] = (WP)[(long long)(CH) * S8_WPC + min(widx0 + 256 * k, S8_WPC - 1)];
+#define CRFP_PA_ISSUE(CH)                                                                                 \
+    {                                                                                                     \
+        const QuadDesc da_ = a.qd[4 * (CH) + 2 * P], db_ = a.qd[4 * (CH) + 2 * P + 1];                    \
+        const float* qa_ = da_.base + (long long)ns * da_.bstride;                                        \
+        const float* qb_ = db_.base + (long long)ns * db_.bstride;                                        \
+        m0 = a.qd[4 * (CH)].mask; m1 = a.qd[4 * (CH) + 1].mask; m2 = a.qd[4 * (CH) + 2].mask; m3 = a.qd[4 * (CH) + 3].mask; \
+        _Pragma("unroll") for (int t = 0; t < 3; ++t) {                                                   \
+            const int cgy = min(max(ty0 + w3 + 4 * t - 2, 0), H - 1);                                     \
+            rqa[t] = CRFP_LDACT(f32x4, qa_ + cgy * da_.rs + cgx * da_.cs);                                \
+            rqb[t] = CRFP_LDACT(f32x4, qb_ + cgy * db_.rs + cgx * db_.cs);                                \
+        }                                                                                                 \
+        CRFP_PA_WEIGHTS(wp, CH)                                                                           \
+    }
+#define CRFP_PA_STAGE_WEIGHTS                                                                             \
+    _Pragma("unroll") for (int k = 0; k < NW; ++k) {                                                      \
+        const int idx = widx0 + 256 * k;                                                                  \
+        if (idx < S8_WPC) wlds[idx] = rws[k];                                                             \
+    }
+
+    CRFP_PA_ISSUE(0)
+    int ch = 0;
+    do {   // (at least one chunk: no zero-trip path for the compiler to carry registers through)
+        const int c0 = m0, c1 = m1, c2 = m2, c3 = m3;
+        const int ma = P ? c2 : c0, mb = P ? c3 : c1;
+        __syncthreads();
+        int ls = lane;   // opaque copy: the staging addresses are recomputed per chunk instead of living through the MFMA loop
+        asm volatile("" : "+v"(ls));
+        const int gxs = tx0 + ls - 2;
+        const bool xin = gxs >= 0 && gxs < W;
+        if (c0 & 16) {   // SRC_S3 chunk (wave-uniform): already split by its producer -- copy, zero outside the image.  Quads 0-1: the x0 image
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int r = w3 + 4 * t, gy = ty0 + r - 2, idx = r * PF_LW + ls;
+                const bool v = xin && gy >= 0 && gy < H;
+                const f32x4 z = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                tile[(2 * P + 0) * PF_PL + idx] = __builtin_bit_cast(bf16x8, v ? rqa[t] : z);
+                tile[(2 * P + 1) * PF_PL + idx] = __builtin_bit_cast(bf16x8, v ? rqb[t] : z);
+            }
+        } else if ((c0 & c1 & c2 & c3) == 15) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int r = w3 + 4 * t, gy = ty0 + r - 2, idx = r * PF_LW + ls;
+                const bool v = xin && gy >= 0 && gy < H;
+                const float sc = v ? F16_RES_SCALE : 0.0f;
+                const unsigned km = v ? 0xffffffffu : 0u;
+                bf16x8 pa, pb;
+                split_f16x8_fast(rqa[t], rqb[t], sc, km, pa, pb);
+                tile[(0 + P) * PF_PL + idx] = pa; tile[(2 + P) * PF_PL + idx] = pb;
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                const int r = w3 + 4 * t, gy = ty0 + r - 2, idx = r * PF_LW + ls;
+                const bool v = xin && gy >= 0 && gy < H;
+                bf16x8 pp[2];
+                split_parts<2>(mask_quad(rqa[t], v ? ma : 0), mask_quad(rqb[t], v ? mb : 0), pp);
+                tile[(0 + P) * PF_PL + idx] = pp[0]; tile[(2 + P) * PF_PL + idx] = pp[1];
+            }
+        }
+        CRFP_PA_STAGE_WEIGHTS
+        __syncthreads();
+        if (ch + 1 < nchunks) CRFP_PA_ISSUE(ch + 1)
+        else CRFP_PA_WEIGHTS(wpb, 0)   // conv B's first weight stage rides under conv A's last chunk
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+            const f16x8 wA = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 0) * 64 + lane]);
+            const f16x8 wB = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 1) * 64 + lane]);
+            const f16x8 wC = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 2) * 64 + lane]);
+#pragma unroll
+            for (int k = 0; k < NTA; ++k) {
+                const int t = wave + 8 * k;   // tile t of the 10 x 64 region: row t >> 1, half t & 1
+                const int pix = ((t >> 1) + ky) * PF_LW + (t & 1) * 32 + j + kx;
+                const f16x8 b0 = __builtin_bit_cast(f16x8, tile[(0 + h) * PF_PL + pix]);
+                const f16x8 b1 = __builtin_bit_cast(f16x8, tile[(2 + h) * PF_PL + pix]);
+                accA[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wB, b0, accA[k], 0, 0, 0);
+                accA[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wC, b1, accA[k], 0, 0, 0);
+                accA[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wA, b0, accA[k], 0, 0, 0);
+            }
+        }
+    } while (++ch < nchunks);
+    __syncthreads();   // every wave finished conv A's last chunk: the halo and the weight stage are dead
+    CRFP_PA_STAGE_WEIGHTS
+    if (NTA == 2) {   // never read (the caller's loops stop at the wave's tile count): defined, and not live during the chunk loop
+#pragma unroll
+        for (int e = 0; e < 16; ++e) accA[2][e] = 0.0f;
+    }
+#undef CRFP_PA_ISSUE
+#undef CRFP_PA_WEIGHTS
+#undef CRFP_PA_STAGE_WEIGHTS
+}
+
+__global__ __launch_bounds__(PF_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv3x3_pair_kernel(const ConvArgs a, const PairB b) {
+    __shared__ bf16x8 tile[4 * PF_PL];           // conv A: planes [x0 | x1s][quad pair] of the input halo; conv B: the same planes of one intermediate half, PF_MEL each
+    __shared__ bf16x8 wlds[S8_WPC];              // [(tap, image A/B/C)][lane] of the current chunk of conv A, then of conv B
+    const int tid0 = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);   // wave-uniform to the compiler as well
+    const int tiles_x = (a.W + PF_OW - 1) / PF_OW;
+    const int btile = xcd_band_tile(blockIdx.x, gridDim.x);
+    const int tx0 = (btile % tiles_x) * PF_OW, ty0 = (btile / tiles_x) * 8;
+    const int n = blockIdx.z;
+    const int ns = a.src_bgroup > 0 ? n + n / a.src_bgroup : n;   // source batch item (ConvArgs::src_bgroup)
+    const int H = a.H, W = a.W;
+
+    const int ntA = wave < 4 ? 3 : 2;
+    f32x16 accA[3];   // (initialised per wave group: the third tile's registers carry the prefetch of waves 4-7 during conv A)
+    const bf16x8* __restrict__ wpb = reinterpret_cast<const bf16x8*>(b.wsplit_sa);
+    if (tid0 < 8) tile[(tid0 >> 1) * PF_PL + PF_NEL + (tid0 & 1)] = __builtin_bit_cast(bf16x8, f32x4{0.0f, 0.0f, 0.0f, 0.0f});   // the planes' overrun pixels
+    if (wave < 4) pair_conv_a<3>(a, wpb, ns, ty0, tx0, tid0, tid0 & 63, wave, tile, wlds, accA);
+    else pair_conv_a<2>(a, wpb, ns, ty0, tx0, tid0, tid0 & 63, wave, tile, wlds, accA);
+    int tid = tid0;   // opaque copy: what the rest derives from it is computed here, not carried through conv A's loop
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, j = lane & 31, h = lane >> 5;
+
+    // conv A's epilogue into LDS, one 16-channel half (cout quads 4 * half .. + 3 = accumulator registers 8 * half .. + 7) at a time: the
+    // stand-alone epilogue's arithmetic (VBIAS = 2: the bias is in the accumulator, `+ 0` is its bias add), exact zero outside the image
+    // (conv B's zero padding pads A's output) and in the two columns no stored output reads, the range guard over what the stand-alone
+    // launch would store, then the split conv B's loader applies to an fp32 Q4 source.  Channel 8 g + 4 h + r is position 4 h + r of the
+    // 8-channel element (quad pair g & 1) of its half.
+    bf16x8* const mid = tile;   // [x0 | x1s][quad pair][PF_MEL]
+    const float slopeA = a.act == CRFP_ACT_RELU ? 0.0f : (a.act == CRFP_ACT_LRELU01 ? 0.1f : 1.0f);
+    const float postA = a.post_scale;
+    float vmaxA = 0.0f;
+#define CRFP_PF_MID(HALF)                                                                                 \
+    _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                       \
+        if (k == 2 && ntA == 2) break;                                                                    \
+        const int t = wave + 8 * k, r = t >> 1, c = (t & 1) * 32 + j;                                     \
+        const int gy = ty0 + r - 1, gx = tx0 + c - 1;                                                     \
+        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W && c < PF_OW + 2;                          \
+        _Pragma("unroll") for (int gg = 0; gg < 2; ++gg) {                                                \
+            const int g = 2 * (HALF) + gg;                                                                \
+            float v[4];                                                                                   \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                               \
+                const float x = accA[k][4 * g + e] * (1.0f / F16_RES_SCALE) + 0.0f;                       \
+                v[e] = in ? fmaxf(x, slopeA * x) * postA : 0.0f;                                          \
+            }                                                                                             \
+            vmaxA = fmaxf(fmaxf(vmaxA, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3]))); \
+            unsigned hi2[2], lo2[2];                                                                      \
+            split_f16x4(v, hi2, lo2);                                                                     \
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));                                   \
+            *(reinterpret_cast<u32x2*>(&mid[(0 + gg) * PF_MEL + r * PF_MP + c]) + h) = u32x2{hi2[0], hi2[1]}; \
+            *(reinterpret_cast<u32x2*>(&mid[(2 + gg) * PF_MEL + r * PF_MP + c]) + h) = u32x2{lo2[0], lo2[1]}; \
+        }                                                                                                 \
+    }
+#define CRFP_PF_WEIGHTS(WP, CH)                                                                           \
+    _Pragma("unroll") for (int k = 0; k < PF_NWS; ++k)                                                    \
+        rws[k] = (WP)[(long long)(CH) * S8_WPC + min(tid + PF_NT * k, S8_WPC - 1)];
+#define CRFP_PF_STAGE_WEIGHTS                                                                             \
+    _Pragma("unroll") for (int k = 0; k < PF_NWS; ++k) {                                                  \
+        const int idx = tid + PF_NT * k;                                                                  \
+        if (idx < S8_WPC) wlds[idx] = rws[k];                                                             \
+    }
+
+    // (pair_conv_a ended behind the barrier that retires conv A's LDS reads, with conv B's chunk 0 weights staged)
+    CRFP_PF_MID(0)
+    if (tid < 4 * PF_IH * 2) {   // the two zero columns behind each intermediate row (read by conv B's taps of discarded output columns only)
+        const int pl = tid / (PF_IH * 2), rc = tid - pl * (PF_IH * 2);
+        mid[pl * PF_MEL + (rc >> 1) * PF_MP + PF_IW + (rc & 1)] = __builtin_bit_cast(bf16x8, f32x4{0.0f, 0.0f, 0.0f, 0.0f});
+    }
+    f32x16 acc[1][2];
+    {   // conv B's accumulators start at 2^11 * bias
+        const float4* __restrict__ bp = reinterpret_cast<const float4*>(b.bpk);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 bq = bp[2 * g + h];
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt) {
+                acc[0][pt][4 * g + 0] = bq.x * F16_RES_SCALE; acc[0][pt][4 * g + 1] = bq.y * F16_RES_SCALE;
+                acc[0][pt][4 * g + 2] = bq.z * F16_RES_SCALE; acc[0][pt][4 * g + 3] = bq.w * F16_RES_SCALE;
+            }
+        }
+    }
+    __syncthreads();
+    bf16x8 rws[PF_NWS];
+    CRFP_PF_WEIGHTS(wpb, 1)
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+        if (c2 == 1) {
+            __syncthreads();   // every wave finished conv B's chunk 0
+            CRFP_PF_MID(1)
+            CRFP_PF_STAGE_WEIGHTS
+            __syncthreads();
+        }
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+            const f16x8 wA = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 0) * 64 + lane]);
+            const f16x8 wB = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 1) * 64 + lane]);
+            const f16x8 wC = __builtin_bit_cast(f16x8, wlds[(tap * 3 + 2) * 64 + lane]);
+#pragma unroll
+            for (int pt = 0; pt < 2; ++pt) {
+                const int pix = (wave + ky) * PF_MP + pt * 32 + j + kx;
+                const f16x8 b0 = __builtin_bit_cast(f16x8, mid[(0 + h) * PF_MEL + pix]);
+                const f16x8 b1 = __builtin_bit_cast(f16x8, mid[(2 + h) * PF_MEL + pix]);
+                acc[0][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wB, b0, acc[0][pt], 0, 0, 0);
+                acc[0][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wC, b1, acc[0][pt], 0, 0, 0);
+                acc[0][pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wA, b0, acc[0][pt], 0, 0, 0);
+            }
+        }
+    }
+#undef CRFP_PF_MID
+#undef CRFP_PF_STAGE_WEIGHTS
+#undef CRFP_PF_WEIGHTS
+    {   // conv A's range guard, on the word the stand-alone launch raises
+        unsigned* const ovfA = ovf_word(a.ovf, a.ovf_div, a.ovf_add, n, a.ovf_skip0);
+        if (ovfA && !(vmaxA < 65504.0f)) atomicOr(ovfA, 1u);
+    }
+#pragma unroll
+    for (int pt = 0; pt < 2; ++pt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[0][pt][e] *= (1.0f / F16_RES_SCALE);
+    // conv B's epilogue: the shared one, on conv B's destinations / residual / activation / status word, PF_OW columns per tile
+    ConvArgs eb = a;
+    eb.cout = b.cout; eb.act = b.act; eb.post_scale = b.post_scale; eb.store = ST_Q4; eb.ps_r = 0;
+    eb.resid = b.resid; eb.resid_bstride = b.resid_bstride; eb.s3_dst = b.s3_dst; eb.s3_bstride = b.s3_bstride; eb.dst_f32 = 0; eb.ndst = b.ndst;
+    eb.ovf = b.ovf; eb.ovf_div = b.ovf_div; eb.ovf_add = b.ovf_add; eb.ovf_skip0 = b.ovf_skip0;
+#pragma unroll
+    for (int d = 0; d < CRFP_MAX_DST; ++d) eb.dst[d] = b.dst[d];
+    EpiCtx ec = epi_ctx(eb, n);
+    ec.xend = min(W, tx0 + PF_OW);
+    conv_epilogue<1, 2, 1, 2>(ec, acc, 0, tx0, ty0, wave, j, h);
+}
+
 #endif  // !CRFP_ACT_BF16
 
 #ifdef CRFP_ACT_BF16
@@ -1486,8 +1780,8 @@ __global__ __launch_bounds__(B8_NT, 2) void conv3x3_bf16x8_kernel(const ConvArgs
 // Same K order and per-accumulator accumulation order as conv3x3_bf16_kernel / conv3x3_bf16x8_kernel: identical values.
 // LDS 76.7 KB (two workgroups per CU): input chunk tile 25.3 KB (later conv B's 18.4 KB of weights), intermediate 42.2 KB,
 // conv A weight stage 9.2 KB.  45 x 11 = 495 workgroups for a 360 x 640 map = one round of the 512 slots.
-// (The fp32 build has no such kernel: its intermediate is two fp16 images = 84 KB, with the staging tile and the 27.6 KB
-// three-image weight stage 160 KB -- one 8-wave workgroup per CU and 1.9 rounds)
+// (The fp32 build's conv3x3_pair_kernel keeps only ONE 16-channel half of its two-image intermediate in LDS at a time, in the
+// dead input tile: 76.5 KB as well)
 constexpr int P2_NT = 512, P2_OW = 62, P2_IH = 10, P2_IW = 64, P2_LH = 12, P2_LW = 66;
 constexpr int P2_NEL = P2_LH * P2_LW, P2_NIN = (P2_NEL + P2_NT - 1) / P2_NT;   // 792 input halo pixels, 2 per thread
 constexpr int P2_MP = P2_IW + 2, P2_MEL = P2_IH * P2_MP;                       // intermediate rows of 64 + 2 zero columns
@@ -2180,6 +2474,41 @@ int launch_conv_pair(const ConvArgs& a, const ConvArgs& b, const char* name, hip
     am.ovf = b.ovf; am.ovf_div = b.ovf_div; am.ovf_add = b.ovf_add;
     const int tiles = ((a.W + P2_OW - 1) / P2_OW) * ((a.H + 7) / 8);
     conv3x3_bf16_pair_kernel<<<dim3(tiles, 1, a.N), P2_NT, 0, s>>>(am, pb);
+    CRFP_CHECK_LAUNCH();
+    return 0;
+}
+#else
+// conv A -> conv B in one launch (conv3x3_pair_kernel), default split-fp16 mode only; both plans as launch_conv_mfma takes them.  Conv A's
+// output tensor is never written: it must have no other reader.  Conv B may also (or only) write its SRC_S3 image.
+int launch_conv_pair(const ConvArgs& a, const ConvArgs& b, const char* name, hipStream_t s) {
+    if ((a.kq & 3) || a.kq > CRFP_MAX_KQ || a.ctiles != 1 || a.cout != 32 || a.store != ST_Q4 || !a.wsplit || a.act == CRFP_ACT_TANH ||
+        a.act == CRFP_ACT_SIGMOID || a.resid || a.s3_dst || a.ksplit || b.nsrc != 1 || b.src[0].kind != SRC_Q4 || b.kq != 8 || b.ctiles != 1 || b.cout != 32 ||
+        b.store != ST_Q4 || !b.wsplit || b.act == CRFP_ACT_TANH || b.act == CRFP_ACT_SIGMOID || b.dst_f32 || b.ksplit || a.N != b.N || a.H != b.H || a.W != b.W) {
+        set_error("conv_pair %s: unsupported pair (A: kq=%d cout=%d store=%d; B: nsrc=%d kq=%d cout=%d store=%d)", name, a.kq, a.cout, a.store,
+                  b.nsrc, b.kq, b.cout, b.store);
+        return CRFP_E_UNSUPPORTED;
+    }
+    if (a.strict || b.strict || precision_env_strict(0)) { set_error("conv_pair %s: the pair kernel exists in the split-fp16 mode only", name); return CRFP_E_UNSUPPORTED; }
+    if (b.s3_dst && !conv_s3_supported()) { set_error("conv_pair %s: s3_dst needs the default f16x3 kernels", name); return CRFP_E_UNSUPPORTED; }
+    for (int i = 0; i < a.nsrc; ++i)
+        if (a.src[i].kind == SRC_NCHW || a.src[i].kind == SRC_NCHW_SHIFT) { set_error("conv_pair %s: NCHW sources are not supported", name); return CRFP_E_UNSUPPORTED; }
+    const ConvWork w = conv_work(a);
+    // algorithmic work of the PAIR: A's inputs + B's outputs (+ residual) cross HBM, the 32-channel tensor between them does not
+    ProfScope prof(name, s, w.px * (w.in_ch + 32 + (b.resid ? 32 : 0)) * (double)sizeof(act_t) + (32.0 * w.in_ch + 32.0 * 32.0) * 9 * 4.0,
+                   2.0 * w.px * 32 * (w.in_ch + 32) * 9.0);
+    ConvArgs am = a;
+    const int rc = prepare_plan(am, name);
+    if (rc) return rc;
+    PairB pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.wsplit_sa = (const char*)b.wsplit + conv_split_sa_offset_bytes(b);
+    pb.bpk = b.bpk; pb.resid = b.resid; pb.resid_bstride = b.resid_bstride;
+    for (int d = 0; d < CRFP_MAX_DST; ++d) pb.dst[d] = b.dst[d];
+    pb.ndst = b.ndst; pb.cout = b.cout; pb.act = b.act; pb.post_scale = b.post_scale;
+    pb.s3_dst = b.s3_dst; pb.s3_bstride = b.s3_bstride;
+    pb.ovf = b.ovf; pb.ovf_div = b.ovf_div; pb.ovf_add = b.ovf_add; pb.ovf_skip0 = b.ovf_skip0;
+    const int tiles = ((a.W + PF_OW - 1) / PF_OW) * ((a.H + 7) / 8);
+    conv3x3_pair_kernel<<<dim3(tiles, 1, a.N), PF_NT, 0, s>>>(am, pb);
     CRFP_CHECK_LAUNCH();
     return 0;
 }

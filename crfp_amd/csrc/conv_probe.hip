@@ -66,7 +66,7 @@ int check_conv(const crfp_probe_conv& c, const char* who, int mode, int k, bool 
     const bool second = c.cout_split > 0;
     if (second && (c.cout_split >= c.cout || (need_ptrs && (!c.weight2 || !c.bias2)))) { set_error("conv_probe %s: cout_split %d needs 0 < cout_split < cout and weight2 / bias2", who, c.cout_split); return CRFP_E_BADARG; }
     const int ncq = (conv_packed_rows(c.cout, c.store, c.ps_r) + 3) / 4;
-    const int min_dst = (k == 0 && (mode == CRFP_PROBE_PAIR || mode == CRFP_PROBE_S3_CHAIN)) ? 0 : 1;
+    const int min_dst = (k == 0 && (mode == CRFP_PROBE_PAIR || mode == CRFP_PROBE_PAIR_F32 || mode == CRFP_PROBE_S3_CHAIN)) ? 0 : 1;
     switch (c.store) {
         case CRFP_PROBE_ST_Q4:
             if (c.ndst < min_dst || c.ndst > CRFP_PROBE_MAX_DST) { set_error("conv_probe %s: %d destinations", who, c.ndst); return CRFP_E_BADARG; }
@@ -98,10 +98,11 @@ int check_conv(const crfp_probe_conv& c, const char* who, int mode, int k, bool 
 
 // validates the call, builds both plan items and lays the workspace out behind `base` (null: sizes only, plans unbound)
 int prepare(Probe& P, int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w, char* base, bool need_ptrs) {
-    if (mode < CRFP_PROBE_SINGLE || mode > CRFP_PROBE_S3_CHAIN) { set_error("conv_probe: unknown mode %d", mode); return CRFP_E_BADARG; }
+    if (mode < CRFP_PROBE_SINGLE || mode > CRFP_PROBE_PAIR_F32) { set_error("conv_probe: unknown mode %d", mode); return CRFP_E_BADARG; }
     if (!a || (mode != CRFP_PROBE_SINGLE && !b)) { set_error("conv_probe: null conv descriptor"); return CRFP_E_BADARG; }
     if (n < 1 || n > kMaxN || h < 1 || w < 1 || (long long)h * w > (1LL << 24)) { set_error("conv_probe: bad geometry (n=%d h=%d w=%d)", n, h, w); return CRFP_E_BADARG; }
     if (mode == CRFP_PROBE_PAIR && !kActBf16) { set_error("conv_probe: the pair kernel exists in the bf16 build only"); return CRFP_E_UNSUPPORTED; }
+    if (mode == CRFP_PROBE_PAIR_F32 && kActBf16) { set_error("conv_probe: the fp32 pair kernel exists in the fp32 build only"); return CRFP_E_UNSUPPORTED; }
     if (mode == CRFP_PROBE_S3_CHAIN && kActBf16) { set_error("conv_probe: SRC_S3 images exist in the fp32 build only"); return CRFP_E_UNSUPPORTED; }
     P.mode = mode; P.n = n; P.h = h; P.w = w;
     P.count = mode == CRFP_PROBE_SINGLE ? 1 : 2;
@@ -121,7 +122,7 @@ int prepare(Probe& P, int mode, const crfp_probe_conv* a, const crfp_probe_conv*
         const crfp_probe_conv& c = *v.c;
         std::vector<SrcSpec> specs;
         if (own_sources(mode, k)) for (int i = 0; i < c.nsrc; ++i) specs.push_back({c.src_kind[i], c.src_nch[i]});
-        else specs.push_back({mode == CRFP_PROBE_PAIR ? (int)SRC_Q4 : (int)SRC_S3, a->cout});
+        else specs.push_back({mode == CRFP_PROBE_S3_CHAIN ? (int)SRC_S3 : (int)SRC_Q4, a->cout});
         for (auto& s : specs) v.cin += s.nch;
         if (v.cin > kMaxCh) { set_error("conv_probe: %d input channels", v.cin); return CRFP_E_BADARG; }
         add_mfma(items[k], k ? "conv_probe:b" : "conv_probe:a", 2 * k, c.cout_split > 0 ? 2 * k + 1 : -1, v.cin, c.cout, specs, c.store, c.ps_r, c.act, c.post_scale);
@@ -207,6 +208,7 @@ void bind(Probe& P, const float* packed) {
 void choose(const Probe& P, int* kernel) {
     kernel[0] = kernel[1] = CK_NONE;
     if (P.mode == CRFP_PROBE_PAIR) { kernel[0] = kernel[1] = CK_BF16_PAIR; return; }
+    if (P.mode == CRFP_PROBE_PAIR_F32) { kernel[0] = kernel[1] = CK_SPLIT_PAIR; return; }
     if (P.mode == CRFP_PROBE_DUAL && conv_select_dual(P.cv[0].plan, P.cv[1].plan) == CK_SPLIT_DUAL) { kernel[0] = kernel[1] = CK_SPLIT_DUAL; return; }
     for (int k = 0; k < P.count; ++k) kernel[k] = conv_select_kernel(P.cv[k].plan);
 }
@@ -281,6 +283,11 @@ int CRFP_API(crfp_conv_probe)(int mode, const crfp_probe_conv* a, const crfp_pro
         case CRFP_PROBE_DUAL: rc = launch_conv_mfma_dual(P.cv[0].plan, "conv_probe:a", P.cv[1].plan, "conv_probe:b", "conv_probe:dual", s); break;
         case CRFP_PROBE_PAIR:
 #ifdef CRFP_ACT_BF16
+            rc = launch_conv_pair(P.cv[0].plan, P.cv[1].plan, "conv_probe:pair", s);
+#endif
+            break;
+        case CRFP_PROBE_PAIR_F32:
+#ifndef CRFP_ACT_BF16
             rc = launch_conv_pair(P.cv[0].plan, P.cv[1].plan, "conv_probe:pair", s);
 #endif
             break;

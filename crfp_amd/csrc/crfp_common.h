@@ -205,7 +205,8 @@ enum ConvKernel : int {
     CK_SPLIT_DUAL = CRFP_CONVK_SPLIT_DUAL,           // conv3x3_split_dual_kernel<1, 1, 2> (fp32 build)
     CK_BF16_X8 = CRFP_CONVK_BF16_X8,                 // conv3x3_bf16x8_kernel (bf16 build)
     CK_BF16_4W = CRFP_CONVK_BF16_4W,                 // conv3x3_bf16_kernel<1> (bf16 build)
-    CK_BF16_PAIR = CRFP_CONVK_BF16_PAIR              // conv3x3_bf16_pair_kernel (bf16 build, launch_conv_pair)
+    CK_BF16_PAIR = CRFP_CONVK_BF16_PAIR,             // conv3x3_bf16_pair_kernel (bf16 build, launch_conv_pair)
+    CK_SPLIT_PAIR = CRFP_CONVK_SPLIT_PAIR            // conv3x3_pair_kernel (fp32 build, launch_conv_pair)
 };
 ConvKernel conv_select_kernel(const ConvArgs& a);
 ConvKernel conv_select_dual(const ConvArgs& a0, const ConvArgs& a1);
@@ -385,10 +386,9 @@ int launch_conv_pack(const ConvArgs& a, const float* w_oihw, const float* bias, 
 int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s);
 // two convs of the same shape (N, H, W, cout tiles) in one launch where the build has the kernel for it (fp32: conv3x3_split_dual_kernel), else two launches
 int launch_conv_mfma_dual(const ConvArgs& a0, const char* name0, const ConvArgs& a1, const char* name1, const char* name_both, hipStream_t s);
-#ifdef CRFP_ACT_BF16
-// bf16 build: conv a (32 couts, no other reader of its output) feeding conv b (32 -> 32) in ONE launch, the tensor between them in LDS
+// conv a (32 couts, no other reader of its output) feeding conv b (32 -> 32) in ONE launch, the tensor between them in LDS (bf16 build:
+// conv3x3_bf16_pair_kernel; fp32 build: conv3x3_pair_kernel, split-fp16 mode only, conv b may write its SRC_S3 image)
 int launch_conv_pair(const ConvArgs& a, const ConvArgs& b, const char* name, hipStream_t s);
-#endif
 size_t conv_split_weight_bytes(const ConvArgs& a);
 size_t conv_split16_offset_bytes(const ConvArgs& a);   // offset of the fp16 pair (bf16 build: the bf16) image inside the split weight block
 int launch_conv_pack_split(const ConvArgs& a, const float* w_oihw, const float* w2, int cout_split, void* wsplit,

@@ -522,27 +522,39 @@ struct Runner {
         ConvArgs a = plan(idA, N, H, W, srcsA, dstsA, dstH, dstW), b = plan(idB, N, H, W, srcsB, dstsB, dstH, dstW);
         rc = launch_conv_mfma_dual(a, M.items[idA].name, b, M.items[idB].name, name_both, s);
     }
-#ifdef CRFP_ACT_BF16
-    // conv idA -> conv idB in one launch (conv3x3_bf16_pair_kernel): idA's output has no other reader and is never written
+    // conv idA -> conv idB in one launch (conv3x3_bf16_pair_kernel / conv3x3_pair_kernel): idA's output has no other reader and is never written.
+    // s3B (fp32 build): conv idB's output goes (only, when dstsB is empty) to an SRC_S3 image
     void mfma_pair(int idA, int idB, const char* name, int N, int H, int W, std::vector<SrcBind> srcsA, std::vector<DstBind> dstsB,
-                   const float* residB = nullptr, long long residB_bs = 0) {
+                   const float* residB = nullptr, long long residB_bs = 0, float* s3B = nullptr, long long s3B_bs = 0) {
         if (rc) return;
         const ConvArgs a = plan(idA, N, H, W, srcsA, {});
         ConvArgs b = plan(idB, N, H, W, {{nullptr, 0}}, dstsB);
         b.resid = residB; b.resid_bstride = residB_bs;
+        b.s3_dst = s3B; b.s3_bstride = s3B_bs;
         rc = launch_conv_pair(a, b, name, s);
     }
-#endif
-    // which 2x-resolution conv pairs run as one launch: bf16 storage only (the fp32 build's intermediate does not fit LDS, conv_mfma.hip),
-    // and one clip per call only: the pair kernel (two 77 KB workgroups per CU, 1.25x the MFMAs for conv A's halo) wins where a launch is a
-    // single round of workgroups (39.5 -> 34.5 and 31.9 -> 25.3 us per clip, round 3); in a lock-step batch the two single convs on the
-    // 4-wave kernel take 26.0 and 19.9 us per clip against the pairs' 29.0 and 19.9 (round 4, 4 clips, same box), and so do the 540 x 960 maps of
-    // one 4K clip (1 088 pair tiles: 572 vs 562 frames/s).  So: pairs while the launch is at most one round of the 512 slots.
-    // CRFP_CONV_PAIR=0 / 2: never / always
-    bool pair_convs() const {
-        static const int mode = !kActBf16 ? 0 : (getenv("CRFP_CONV_PAIR") ? atoi(getenv("CRFP_CONV_PAIR")) : 1);   // read once
-        const long long pair_tiles = (long long)L.B * ((2 * L.w + 61) / 62) * ((2 * L.h + 7) / 8);   // 8 x 62 output tiles of the pair kernel
-        return mode == 2 || (mode == 1 && pair_tiles <= 512);
+    // Which 2x-resolution conv pairs run as one launch.  CRFP_CONV_PAIR=0 / 2: never / always; the results are bit-identical either way, so the
+    // rule may look at geometry and batch.
+    // bf16 build, one clip per call only: the pair kernel (two 77 KB workgroups per CU, 1.25x the MFMAs for conv A's halo) wins where a launch
+    // is a single round of workgroups (39.5 -> 34.5 and 31.9 -> 25.3 us per clip, round 3); in a lock-step batch the two single convs on the
+    // 4-wave kernel take 26.0 and 19.9 us per clip against the pairs' 29.0 and 19.9 (round 4, 4 clips, same box), and so do the 540 x 960 maps
+    // of one 4K clip (1 088 pair tiles: 572 vs 562 frames/s).  So: pairs while the launch is at most one round of the 512 slots.
+    // fp32 build (conv3x3_pair_kernel, 60-column tiles, split-fp16 mode only; round 14, profiles/r14_conv_pair_f32_ab.txt, us per clip, two
+    // launches -> pair): its single convs are 8-wave one-round kernels already, and what the pair removes (a kernel floor, conv A's store
+    // burst, conv B's prologue) does not depend on rounds.  res pair: 52.0 -> 41.8 (one clip), 42.4 -> 33.4 (lock-step n = 4), 95.1 -> 84.1
+    // (4K, 1 088 tiles): always.  dcn_block pair: 69.1 -> 62.0 (one clip), 58.2 -> 54.6 (n = 4), but 132.7 -> 135.4 at 4K: while ONE clip's
+    // map is at most one round.  Strict fp32 (CRFP_DSV_STRICT_F32, CRFP_PRECISION=f32) keeps two launches.
+    enum PairSite { PAIR_RES = 0, PAIR_DCN_BLOCK = 1 };
+    bool pair_convs(PairSite site) const {
+        static const int mode = getenv("CRFP_CONV_PAIR") ? atoi(getenv("CRFP_CONV_PAIR")) : 1;   // read once
+        constexpr int ow = kActBf16 ? 62 : 60;   // columns of the pair kernel's 8-row output tile
+        const long long clip_tiles = (long long)((2 * L.w + ow - 1) / ow) * ((2 * L.h + 7) / 8);
+        if (!kActBf16) {
+            static const bool env_strict = precision_env_strict(0);
+            if (strict || env_strict) return false;
+            return mode == 2 || (mode == 1 && (site == PAIR_RES || clip_tiles <= 512));
+        }
+        return mode == 2 || (mode == 1 && (long long)L.B * clip_tiles <= 512);
     }
     // plain Q4 -> Q4 conv on whole tensors
     void mfma_q(int id, int N, const Q4& in, const Q4& out) {
@@ -778,7 +790,7 @@ struct Runner {
     }
 
     // ResidualBlockNoBN of level l (model/CRFP.py:449-481): y0 + conv2(relu(conv1(y0))), the 32 output channels going to the
-    // propagated features (24) and the carried ones (8).  bf16 build: one launch, conv1's output stays in LDS.
+    // propagated features (24) and the carried ones (8).  One launch where pair_convs() says so: conv1's output stays in LDS.
     // CRFP_DSV_CRA (M.cra): the block's 32 channels stay together (cra.y); the level's fusion conv and the masked blend then write the
     // same two destinations (model/CRFP.py:2533-2535): [prop | carry] = mk2 * conv_tttf_l(cat(y, fovea level l)) + (1 - mk2) * y
     void res_block(int l, float* prop_next, float* carry_l, int H2, int W2, int par = 0, const uint8_t* mk = nullptr, long long mk_b = 0) {
@@ -787,12 +799,9 @@ struct Runner {
         std::vector<DstBind> dsts = {{prop_next, 6 * P2q, 0, 6}, {carry_l, 6 * P2qp, 6, 8, 1}};
         if (M.cra) dsts = {{F(L.c_y), L.c_y.bs, 0, 8}};
         if (M.abl()) dsts = {{prop_next, 8 * P2q, 0, 8}};   // CRFP_simple / CRFP: all 32 channels are the next level's features
-#ifdef CRFP_ACT_BF16
-        if (pair_convs())
+        if (pair_convs(PAIR_RES))
             mfma_pair(it_lvl(l, L_RB1), it_lvl(l, L_RB2), "conv_mfma_pair:res.conv1_conv2_add", B, H2, W2, {{F(L.y0), L.y0.bs}}, dsts, F(L.y0), L.y0.bs);
-        else
-#endif
-        {
+        else {
             mfma(it_lvl(l, L_RB1), B, H2, W2, {{F(L.y0), L.y0.bs}}, {{F(L.y1), L.y1.bs, 0, 8}});
             mfma(it_lvl(l, L_RB2), B, H2, W2, {{F(L.y1), L.y1.bs}}, dsts, 0, 0, F(L.y0), L.y0.bs);
         }
@@ -917,12 +926,10 @@ struct Runner {
                 // dcn_block.0's inputs: [features | carried] | warped previous state | flow; CRFP_simple / CRFP: features (32) | warped | flow
                 const std::vector<SrcBind> db0 = abl ? std::vector<SrcBind>{{prop, bs6}, {F(L.prev2w), bs8}, {flow2, f2b}, {nullptr, 0}}
                                                      : std::vector<SrcBind>{{prop, bs6}, {cw, bs6}, {F(L.prev2w), bs8}, {flow2, f2b}, {nullptr, 0}};
-#ifdef CRFP_ACT_BF16
-                if (pair_convs())   // dcn_block.0 -> .2 in one launch, the 32-channel tensor between them stays in LDS
-                    mfma_pair(it_lvl(l, L_DB0), it_lvl(l, L_DB1), "conv_mfma_pair:dcn.block0_block2", B, H2, W2, db0, {{l == 0 ? f : F(L.fb), bs8, 0, 8}});
-                else
-#endif
-                {
+                if (pair_convs(PAIR_DCN_BLOCK)) {   // dcn_block.0 -> .2 in one launch, the 32-channel tensor between them stays in LDS
+                    if (l == 0 && s3) mfma_pair(it_lvl(l, L_DB0), it_lvl(l, L_DB1), "conv_mfma_pair:dcn.block0_block2", B, H2, W2, db0, {}, nullptr, 0, f, bs8);
+                    else mfma_pair(it_lvl(l, L_DB0), it_lvl(l, L_DB1), "conv_mfma_pair:dcn.block0_block2", B, H2, W2, db0, {{l == 0 ? f : F(L.fb), bs8, 0, 8}});
+                } else {
                 mfma(it_lvl(l, L_DB0), B, H2, W2, db0, {{F(L.fa), bs8, 0, 8}});
                 if (l == 0) {
                     if (s3) mfma(it_lvl(l, L_DB1), B, H2, W2, {{F(L.fa), bs8}}, {}, 0, 0, nullptr, 0, nullptr, 0, f, bs8);

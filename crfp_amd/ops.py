@@ -406,7 +406,7 @@ def conv_probe(a, b=None, mode="single", storage="f32", raw=False):
     "flow2" ([n, h, w, 2]); ``weight`` / ``bias`` (and ``weight2`` / ``bias2`` for the rows behind them); ``residual``; ``flow``;
     ``store`` "q4" (``dsts`` = [(q0, q1[, pad])] quad ranges, default one destination with everything), "ps" (``ps_r``) or "offmask"
     (``n_off_quads``); ``act``, ``post_scale``, ``strict``, ``dst_f32``.  mode: "single", "dual" (a and b side by side), "pair" (bf16: a
-    feeds b in one launch) or "s3_chain" (fp32: a's output reaches b as the pre-split fp16 image; give a ``dsts=[]``).
+    feeds b in one launch), "pair_f32" (the same through the fp32 build's pair kernel) or "s3_chain" (fp32: a's output reaches b as the pre-split fp16 image; give a ``dsts=[]``).
     Returns a dict: ``out`` (per conv, the list of its destination tensors, NCHW fp32; elements no lane wrote are NaN), ``status``
     (int32 [2, n]: the range-guard word of every batch item, per conv), ``kernel`` (the variant names the launcher chose, per conv),
     ``raw`` (with raw=True: per conv the raw bytes of each "q4" destination, pads included)."""

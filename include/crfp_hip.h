@@ -455,7 +455,8 @@ int crfp_dsv_debug_fetch(const char* name, int t, int h, int w, const void* work
  *             the rest sigmoid(conv)
  *   strict: the plain fp32 MFMA (CRFP_DSV_STRICT_F32);  dst_f32: bf16 build, one whole ST_Q4 destination stored as float.
  * mode CRFP_PROBE_SINGLE: conv a.  CRFP_PROBE_DUAL: a and b through launch_conv_mfma_dual.  CRFP_PROBE_PAIR (bf16 build only, else
- * CRFP_E_UNSUPPORTED): a (32 couts, no destination) feeding b (32 -> 32) in one launch; b's source table is ignored.  CRFP_PROBE_S3_CHAIN
+ * CRFP_E_UNSUPPORTED): a (32 couts, no destination) feeding b (32 -> 32) in one launch; b's source table is ignored.  CRFP_PROBE_PAIR_F32
+ * (fp32 build only, else CRFP_E_UNSUPPORTED): the same through the fp32 build's pair kernel (split-fp16 mode).  CRFP_PROBE_S3_CHAIN
  * (fp32 build only): a stores its output only as the pre-split fp16 pair image (a.ndst = 0), b reads it as its single source.
  * status: n words for conv a followed by n words for conv b (device memory, 2 n unsigned): word k is nonzero when batch item k stored a
  * value an fp16 operand cannot hold.  kernel (host memory, 2 ints): CRFP_CONVK_* of conv a and conv b; one launch for both (dual kernel,
@@ -473,6 +474,7 @@ int crfp_dsv_debug_fetch(const char* name, int t, int h, int w, const void* work
 #define CRFP_PROBE_DUAL 1
 #define CRFP_PROBE_PAIR 2
 #define CRFP_PROBE_S3_CHAIN 3
+#define CRFP_PROBE_PAIR_F32 4
 #define CRFP_CONVK_NONE 0
 #define CRFP_CONVK_MFMA_SHIFT_CT2 1 /* conv3x3_mfma_kernel<2, 1, 2> */
 #define CRFP_CONVK_MFMA_SHIFT 2     /* conv3x3_mfma_kernel<1, 1, 2> */
@@ -485,6 +487,7 @@ int crfp_dsv_debug_fetch(const char* name, int t, int h, int w, const void* work
 #define CRFP_CONVK_BF16_X8 9        /* conv3x3_bf16x8_kernel */
 #define CRFP_CONVK_BF16_4W 10       /* conv3x3_bf16_kernel<1> */
 #define CRFP_CONVK_BF16_PAIR 11     /* conv3x3_bf16_pair_kernel */
+#define CRFP_CONVK_SPLIT_PAIR 12    /* conv3x3_pair_kernel */
 typedef struct crfp_probe_conv {
     const float* src[CRFP_PROBE_MAX_SRC];
     const float* weight;

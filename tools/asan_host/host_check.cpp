@@ -244,6 +244,10 @@ int main() {
         a0.ndst = 0;
         EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62, k) == CRFP_E_UNSUPPORTED);
         EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62, k) == 0 && k[0] == CRFP_CONVK_BF16_PAIR && k[1] == CRFP_CONVK_BF16_PAIR);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_PAIR_F32, &a0, &q, 2, 8, 62, k) == 0 && k[0] == CRFP_CONVK_SPLIT_PAIR && k[1] == CRFP_CONVK_SPLIT_PAIR);
+        EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_PAIR_F32, &a0, &q, 2, 8, 62, k) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_PAIR_F32 + 1, &a0, &q, 2, 8, 62, k) == CRFP_E_BADARG);
+        EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_PAIR_F32, &a0, &q, 2, 8, 62) > 0 && crfp_conv_probe_workspace_bytes_bf16(CRFP_PROBE_PAIR_F32, &a0, &q, 2, 8, 62) == 0);
         EXPECT(crfp_conv_probe_kernel_bf16(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, k) == CRFP_E_UNSUPPORTED);
         EXPECT(crfp_conv_probe_kernel(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, k) == 0 && k[0] == CRFP_CONVK_SPLIT8 && k[1] == CRFP_CONVK_SPLIT4);
         EXPECT(crfp_conv_probe_workspace_bytes(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62) > 0);
@@ -317,6 +321,15 @@ int main() {
         EXPECT(k[0] == CRFP_CONVK_SPLIT_DUAL);
         EXPECT(crfp_conv_probe_bf16(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62, st, k, wsp, crfp_conv_probe_workspace_bytes_bf16(CRFP_PROBE_PAIR, &a0, &q, 2, 8, 62), nullptr) == 0);
         EXPECT(crfp_conv_probe_bf16(CRFP_PROBE_PAIR, &a0, &two, 2, 8, 62, st, k, wsp, (size_t)1 << 40, nullptr) == CRFP_E_UNSUPPORTED);   // conv b must be 32 -> 32
+        // the fp32 pair path: a whole call, the 32 -> 32 rule for conv b, and no pair under strict fp32
+        EXPECT(crfp_conv_probe(CRFP_PROBE_PAIR_F32, &a0, &q, 2, 19, 130, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_PAIR_F32, &a0, &q, 2, 19, 130), nullptr) == 0);
+        EXPECT(k[0] == CRFP_CONVK_SPLIT_PAIR && k[1] == CRFP_CONVK_SPLIT_PAIR);
+        EXPECT(crfp_conv_probe(CRFP_PROBE_PAIR_F32, &a0, &two, 2, 8, 62, st, k, wsp, (size_t)1 << 40, nullptr) == CRFP_E_UNSUPPORTED);
+        {
+            crfp_probe_conv as = a0;
+            as.strict = 1;
+            EXPECT(crfp_conv_probe(CRFP_PROBE_PAIR_F32, &as, &q, 2, 8, 62, st, k, wsp, (size_t)1 << 40, nullptr) == CRFP_E_UNSUPPORTED);
+        }
         EXPECT(crfp_conv_probe(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62), nullptr) == 0);
         EXPECT(crfp_stub_launches() > l0);
     }
