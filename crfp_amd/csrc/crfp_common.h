@@ -111,7 +111,7 @@ enum StoreMode : int {
     ST_PS = 1,      // pixel_shuffle(r) fused into the store, Q4 destination at (H*r, W*r)
     ST_NCHW = 2,    // NCHW planes
     ST_OFFMASK = 3, // DCN offset/mask epilogue: quads < n_off_quads: 10*tanh + flow(y,x); rest: sigmoid
-    ST_DCNFUSE = 4  // pack-only mode: the 216 offset / mask rows in the register order of dcn_fused_kernel (gather.hip) -- each
+    ST_DCNFUSE = 4  // pack-only mode: the 216 offset / mask rows in the register order of dcn_fused_kernel (dcn_fused.inc) -- each
                     // lane half receives (dy, dx, mask) of its 36 sampling positions as accumulator slot 3*p + c of 7 x 16
 };
 
@@ -402,7 +402,7 @@ int launch_narrow(const NarrowArgs& a, const char* name, hipStream_t s);
 int launch_narrow_pair(const NarrowArgs& a, const NarrowArgs& b, const char* name, hipStream_t s);
 // three stencils in one pass (conv_narrow.hip): a -> b -> c; res: c adds a's output (residual block; the only form of the bf16 build)
 int launch_narrow_chain(const NarrowArgs& a, const NarrowArgs& b, const NarrowArgs& c, bool res, const char* name, hipStream_t s);
-// gather.hip
+// gather.hip (the fused offset head + dcn_g8: dcn_fused.inc, which it includes)
 // src_pad = 1: x is P4 (padded planes, zero pads): validity logic replaced by clamping + hardware range check
 // N > 1: batch strides in elements of each tensor's own type (activations: act_t, flow: float)
 struct WarpDualStrides { long long xa = 0, xb = 0, flow = 0, outa = 0, outb = 0; };

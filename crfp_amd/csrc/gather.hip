@@ -7,11 +7,10 @@
 // flow) hit consecutive 16-B elements: the four corner loads of a wave cover two nearly contiguous
 // 1-KiB row segments that the CU's L1 serves 3 times out of 4; HBM sees each input line once.
 #include "crfp_common.h"
+#include "dcn_sampler.h"
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-
-#include <cstdlib>
 
 namespace CRFP_NS {
 
@@ -79,53 +78,6 @@ __global__ __launch_bounds__(256) void flow_warp_q4_kernel(const float* __restri
     }
 }
 
-#endif
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// ---- P4 sources ("padded Q4"): planes are (H+1) x (W+1) with a zero pad row (y == H) and a zero pad
-// column (x == W).  With the sample position clamped to [-1, size] every one of the 4 bilinear
-// corners either hits real data, a zero pad element (x == -1 is the pad column of the previous row,
-// y == -1 the pad row of the previous plane) or falls outside the buffer, where the hardware range
-// check of a raw buffer load returns 0.  No per-corner validity logic and no 64-bit address math is
-// left on the VALU: one 32-bit byte offset per sample, the other three corners ride on the scalar
-// offset operand (+16, +pitch, +pitch+16).
-#ifndef CRFP_GATHER_AUX
-#define CRFP_GATHER_AUX 0   // cache-policy bits of the gather loads (gfx942+: 1 = sc0, 2 = nt, 16 = sc1)
-#endif
-// one pixel quad (16 bytes of fp32 / 8 bytes of bf16) at byte offset voff + soff; out-of-range reads return 0
-__device__ __forceinline__ f32x4 bload(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-#ifdef CRFP_ACT_BF16
-    return quad_from_bits(__builtin_bit_cast(cu32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, CRFP_GATHER_AUX)));
-#else
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, CRFP_GATHER_AUX));
-#endif
-}
-constexpr int QB = kQuadBytes;   // bytes per pixel quad of a gathered plane
-
-// The two horizontally adjacent corners (x0, x0 + 1) of a bilinear sample are adjacent in memory -- also across the row end,
-// where x0 + 1 is the zero pad column, and at x0 = -1, which is the pad column of the previous row.  In the bf16 build the
-// pair is 16 bytes = ONE buffer_load_dwordx4 (dword alignment is all a buffer load needs): half the gather instructions of
-// the fp32 build, which matters because these kernels are bound by the texture-address / L1 rate of their per-lane gathers,
-// not by bytes (dcn_g8: 66 M lane-loads per launch @A).
-#ifdef CRFP_ACT_BF16
-typedef u32x4 pairraw_t;
-__device__ __forceinline__ pairraw_t bload_pair(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, CRFP_GATHER_AUX);
-}
-__device__ __forceinline__ f32x4 pair_lo(const pairraw_t& p) { return quad_from_bits(cu32x2{p.x, p.y}); }
-__device__ __forceinline__ f32x4 pair_hi(const pairraw_t& p) { return quad_from_bits(cu32x2{p.z, p.w}); }
-#else
-struct pairraw_t { f32x4 lo, hi; };
-__device__ __forceinline__ pairraw_t bload_pair(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    pairraw_t p;
-    p.lo = bload(r, voff, soff);
-    p.hi = bload(r, voff, soff + 16);
-    return p;
-}
-__device__ __forceinline__ f32x4 pair_lo(const pairraw_t& p) { return p.lo; }
-__device__ __forceinline__ f32x4 pair_hi(const pairraw_t& p) { return p.hi; }
 #endif
 
 __global__ __launch_bounds__(256) void flow_warp_p4_kernel(const float* __restrict__ x, long long xb,
@@ -409,8 +361,6 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) { return __builtin_nontemp
 // F16: the 32x32 GEMM runs on the fp16 MFMA with the exact two-term split of conv_mfma.hip (sample = s0 + 2^-11 s1, weights
 // pre-split; hi / lo accumulators): a pair of sampling positions (2 x 4 channels per lane half) is one K = 16 step = 3 MFMAs of
 // 32 cycles instead of 8 fp32 MFMAs of 64.  The C-ABI op keeps the fp32 MFMA (F16 = false).
-typedef _Float16 dcn_f16x8 __attribute__((ext_vector_type(8)));
-
 #ifndef CRFP_ACT_BF16
 template <int NW, int NP, int MINW, bool F16>
 __global__ __launch_bounds__(64 * NW, MINW) void dcn_g8_kernel(const float* __restrict__ x, long long xb,
@@ -537,91 +487,6 @@ __global__ __launch_bounds__(64 * NW, MINW) void dcn_g8_kernel(const float* __re
 // multiplied, and the (dy,dx)/mask quads run two iterations ahead.  In the straight version every pair waited for its own
 // gathers, and its VALU (~33 us of instruction issue), gather (~32 us of L1 bandwidth: 1.06 GB of 16-B corner reads) and
 // offset traffic (199 MB of HBM) added up instead of overlapping (96 us).
-struct DcnPair {
-    pairraw_t tp[2], bt[2];   // [position]: top / bottom corner pairs as loaded
-    float w[2][4];            // modulated bilinear weights
-};
-
-struct DcnOff { f32x4 m4, oa, ob; };   // masks of 4 positions, (dy,dx) of positions (0,1) and (2,3)
-
-// one sampling position (p36 = 9 * group-in-half + tap, compile-time) into slot pi of P: coordinates, modulated bilinear weights,
-// the two 2-corner gathers
-__device__ __forceinline__ void dcn_issue_one(DcnPair& P, int pi, __amdgpu_buffer_rsrc_t rx, float dy, float dx, float mm, int p36,
-                                              float fy0, float fx0, float fH, float fW, int PW, int pitch, int plane_b, int hbase) {
-    const int gi = p36 / 9, tap = p36 - 9 * gi, ky = tap / 3, kx = tap - 3 * ky;
-    // (float)(cy-1) + (float)ky is exact, so this equals the reference's (float)(y - pad + ky) + dy
-    float sy = (fy0 + (float)ky) + dy;
-    float sx = (fx0 + (float)kx) + dx;
-    sy = __builtin_amdgcn_fmed3f(sy, -1.0f, fH);   // = min(max(sy, -1), H) in one instruction (the offsets are finite)
-    sx = __builtin_amdgcn_fmed3f(sx, -1.0f, fW);
-    const float fy = floorf(sy), fx = floorf(sx);
-    const float ly = sy - fy, lx = sx - fx;
-    const float a = (1.0f - ly) * mm, b = ly * mm, hx = 1.0f - lx;
-    P.w[pi][0] = a * hx; P.w[pi][1] = a * lx; P.w[pi][2] = b * hx; P.w[pi][3] = b * lx;
-    // element index fy * PW + fx in float (exact below 2^24: a 2x-resolution plane has < 2^22 elements), one conversion
-    const int vo = (int)__builtin_fmaf(fy, (float)PW, fx) * QB + hbase + gi * plane_b;
-#if defined(CRFP_DF_PROBE_CT) && (CRFP_DF_PROBE_CT & 128)   // A/B builds: coordinates and weights, but no corner gathers (results wrong)
-    P.tp[pi] = pairraw_t{}; P.bt[pi] = pairraw_t{};
-    asm volatile("" ::"v"(vo));
-#else
-    P.tp[pi] = bload_pair(rx, vo, 0);
-    P.bt[pi] = bload_pair(rx, vo, pitch);
-#endif
-}
-
-__device__ __forceinline__ void dcn_issue_pair(DcnPair& P, __amdgpu_buffer_rsrc_t rx, const DcnOff& O, int hb, int v, float fy0,
-                                               float fx0, float fH, float fW, int PW, int pitch, int plane_b, int hbase) {
-    const float dyv[4] = {O.oa.x, O.oa.z, O.ob.x, O.ob.z};
-    const float dxv[4] = {O.oa.y, O.oa.w, O.ob.y, O.ob.w};
-    const float mmv[4] = {O.m4.x, O.m4.y, O.m4.z, O.m4.w};
-#pragma unroll
-    for (int pi = 0; pi < 2; ++pi)
-        dcn_issue_one(P, pi, rx, dyv[hb + pi], dxv[hb + pi], mmv[hb + pi], 4 * v + hb + pi, fy0, fx0, fH, fW, PW, pitch, plane_b, hbase);
-}
-
-// bilinear blend of position pi of a pair into xs[4 pi .. 4 pi + 3] (one multiply + three FMAs per channel)
-__device__ __forceinline__ void dcn_lerp_one(const DcnPair& P, int pi, float (&xs)[8]) {
-    f32x4 val = pair_lo(P.tp[pi]) * P.w[pi][0];
-    val = __builtin_elementwise_fma(pair_hi(P.tp[pi]), f32x4{P.w[pi][1], P.w[pi][1], P.w[pi][1], P.w[pi][1]}, val);
-    val = __builtin_elementwise_fma(pair_lo(P.bt[pi]), f32x4{P.w[pi][2], P.w[pi][2], P.w[pi][2], P.w[pi][2]}, val);
-    val = __builtin_elementwise_fma(pair_hi(P.bt[pi]), f32x4{P.w[pi][3], P.w[pi][3], P.w[pi][3], P.w[pi][3]}, val);
-    xs[4 * pi + 0] = val.x; xs[4 * pi + 1] = val.y; xs[4 * pi + 2] = val.z; xs[4 * pi + 3] = val.w;
-}
-
-// the sampled pair (8 values = one K = 16 step of the lane) split exactly into two fp16 terms and multiplied into the DCN sums
-__device__ __forceinline__ void dcn_split_mfma(const float (&xs)[8], f32x16& acc, f32x16& acl, const f32x4* wl, int u, int lane) {
-    // the exact two-term split in its 3-op-per-value form (conv_mfma.hip split_f16x8_fast): one v_cvt_pk_f16_f32 per pair of
-    // values, x - x0 as one v_fma_mix_f32, the scaled residuals through a second pack -- the same values as the scalar form
-    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-    typedef float f2_t __attribute__((ext_vector_type(2)));
-    typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-    u4_t hi4, lo4;
-    float negone = -1.0f;
-    asm("" : "+v"(negone));   // opaque: keeps fma(x0, -1, x) one v_fma_mix_f32
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const h2_t h2 = __builtin_convertvector(f2_t{xs[2 * i], xs[2 * i + 1]}, h2_t);
-        const float r0 = __builtin_fmaf((float)h2[0], negone, xs[2 * i]);
-        const float r1 = __builtin_fmaf((float)h2[1], negone, xs[2 * i + 1]);
-        const h2_t l2 = __builtin_convertvector(f2_t{r0 * 2048.0f, r1 * 2048.0f}, h2_t);
-        hi4[i] = __builtin_bit_cast(unsigned, h2);
-        lo4[i] = __builtin_bit_cast(unsigned, l2);
-    }
-    const dcn_f16x8 b0 = __builtin_bit_cast(dcn_f16x8, hi4), b1 = __builtin_bit_cast(dcn_f16x8, lo4);
-    const dcn_f16x8 w0 = __builtin_bit_cast(dcn_f16x8, wl[(2 * u) * 64 + lane]);
-    const dcn_f16x8 w1 = __builtin_bit_cast(dcn_f16x8, wl[(2 * u + 1) * 64 + lane]);
-    acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b1, acl, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b0, acc, 0, 0, 0);
-    acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, b0, acl, 0, 0, 0);
-}
-
-__device__ __forceinline__ void dcn_consume_pair(const DcnPair& P, f32x16& acc, f32x16& acl, const f32x4* wl, int u, int lane) {
-    float xs[8];
-    dcn_lerp_one(P, 0, xs);
-    dcn_lerp_one(P, 1, xs);
-    dcn_split_mfma(xs, acc, acl, wl, u, lane);
-}
-
 __global__ __launch_bounds__(256, 3) void dcn_g8_pipe_kernel(const float* __restrict__ x, long long xb,
                                                              const float* __restrict__ offmask, long long omb,
                                                              const float* __restrict__ wpk, const float* __restrict__ bias,
@@ -686,1071 +551,11 @@ __global__ __launch_bounds__(256, 3) void dcn_g8_pipe_kernel(const float* __rest
 #undef CRFP_DCN_ISSUE
 #undef CRFP_DCN_LOAD_OFF
     if (!valid) return;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] += acl[e] * (1.0f / 2048.0f);
-    act_t* o = as_act(out) + (long long)n * ob + ((long long)py * W + px) * 4;
-    float vmax = 0.0f;   // fp16-operand range guard (ConvArgs::ovf): the aligned features feed a split-fp16 conv
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int cq = 2 * g + h;
-        const float4 bb = *reinterpret_cast<const float4*>(bias + 4 * cq);
-        const float4 v = make_float4(acc[4 * g] + bb.x, acc[4 * g + 1] + bb.y, acc[4 * g + 2] + bb.z, acc[4 * g + 3] + bb.w);
-        vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-        stq(o + cq * plane, cf32x4{v.x, v.y, v.z, v.w});
-    }
-    if (ovf && !(vmax < 65504.0f)) atomicOr(ovf_word(ovf, ovf_div, 0, n), 1u);
+    DCN_G8_EPILOGUE(out, ob, bias, ovf, ovf_div)
 }
 
-
-#ifndef CRFP_ACT_BF16
-// ---------------------------------------------------------------- offset / mask conv + dcn_g8 in one kernel (engine, f16x3)
-// The 32 -> 216 offset / mask head (model/CRFP.py:337-340) used to write 199 MB of offsets and masks that dcn_g8 read straight
-// back (28 % of the clip for the pair).  The conv's accumulator layout already is the sampler's: lane = pixel, lane half =
-// 4 deformable groups.  With the cout rows packed in ST_DCNFUSE order (crfp_common.h) every lane half receives the (dy, dx,
-// mask) of its 36 sampling positions as accumulator slot 3 p + c of 7 cout tiles x 16 registers, in the order the sampler
-// consumes them; the values go from the conv's registers through tanh / sigmoid into the coordinate arithmetic and never
-// touch memory.  Workgroup = NW rows x 32 pixels (one wave per row, as dcn_g8_pipe_kernel); the offset feature's SRC_S3 halo tile
-// ((NW + 2) x 34 pixels, both fp16 parts of all 32 channels) and the DCN weight image stay in LDS for the workgroup's life, the conv
-// weights stream through one 18 KB stage per (cout tile, 16-channel chunk) (registers -> LDS, next stage's loads in flight
-// under the MFMAs).  After cout tile T the sampling pairs it completed run (2-3 of the 18); the last pair's gathers stay in
-// flight under tile T+1's MFMAs.  Same arithmetic in the same order as conv3x3_split_kernel<1,1,2> + dcn_g8_pipe_kernel: the
-// results are bit-identical to the two-kernel path.  LDS 81 408 B (NW = 4, two workgroups per CU) / 117 248 B (NW = 8, shipped).
-constexpr int DF_LW = 34;
-constexpr int DF_WCH = 9 * 2 * 64;                   // one (cout tile, chunk) of the fp16 pair image, 16-byte elements
-#ifndef CRFP_DF_BAND_NP
-#define CRFP_DF_BAND_NP 1   // A/B builds: 0 = the natural tile order of the one-tile form (round 5)
-#endif
-#ifndef CRFP_DF_PS_PROBE   // A/B builds, timing only (results wrong): 1 = the persistent form never requests the next tile's halo tile / weights,
-#define CRFP_DF_PS_PROBE 0 // 2 = ... never writes them to LDS
-#endif
-constexpr int DF_PS_PROBE = CRFP_DF_PS_PROBE;
-
-__device__ __forceinline__ void df_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// NW = 4: workgroup of 4 rows x 32 pixels, two per CU, one weight stage (two barriers per stage).  NW = 8: 8 rows, one workgroup
-// per CU, the weight stage double-buffered (one barrier per stage, half the L2 -> LDS weight and DCN-image traffic per pixel).
-// PS (round 6): the PERSISTENT form.  gridDim.x workgroups (one per CU) walk the tile list of the whole launch (all batch items), XCD x
-// taking the contiguous band x of it (xcd_band_tile's split).  The DCN weight image, the bias table and the kernel's registers are set up
-// once per workgroup instead of once per tile; the NEXT tile's halo tile and weight stage 0 are requested in the schedule's tail behind the
-// last gather issue (their registers -- rt, rws -- are dead there; nothing queues behind them in the in-order vmcnt) and go to LDS behind one
-// barrier behind the last DCN MFMA, so only the first tile of a workgroup pays the 116 KB prologue in front of its first MFMA.  Same per-pixel
-// operations in the same order: bit-identical.  Used for launches of >= 6 rounds of the chip (launch_dcn_fused); below that the one-tile form
-// (PS = false, the same XCD-banded tile order) is 1-1.5 % faster (profiles/r06_dcn_fused_persistent_ab.txt).
-template <int NW, bool PS = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(const DcnFuseArgs a) {
-    constexpr int NT = 64 * NW, DF_NEL = (NW + 2) * DF_LW;   // halo tile of an NW x 32-pixel workgroup
-    constexpr int DF_NIN = (8 * DF_NEL + NT - 1) / NT;       // 16-byte tile elements per thread
-    constexpr bool DB = NW == 8;
-    static_assert(!PS || DB, "the persistent form is the 8-wave form");
-    constexpr int CPS = DB ? 2 : 1;                          // chunks per weight stage: NW = 8 stages a whole cout tile (7 barriers per workgroup)
-    constexpr int DF_WST = CPS * DF_WCH, NSTG = 14 / CPS;
-    constexpr int DF_NWS = (DF_WST + NT - 1) / NT;
-    __shared__ f32x4 tile[8][DF_NEL];   // [part * 4 + 8-channel group][halo pixel]: x0 planes, then x1s planes
-    __shared__ f32x4 wst[DB ? 2 : 1][DF_WST];
-    __shared__ f32x4 wl[36 * 64];
-    __shared__ f32x4 bl[DB ? 56 : 1];   // the head's 224 packed biases (NW = 8: LDS has room; NW = 4 keeps them in 4 VGPRs)
-    const int tid0 = threadIdx.x;
-#ifdef CRFP_PRIO47   // A/B builds: static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-    if ((tid0 >> 6) >= 4) __builtin_amdgcn_s_setprio(CRFP_PRIO47);
-#endif
-    const int H = a.H, W = a.W;
-    // the tile list (PS): tile id = (n * tiles_y + ty) * tiles_x + tx; this workgroup takes t_cur, t_cur + t_step, ... below t_end
-    const int tiles_x = (W + 31) >> 5, tiles_y = (H + NW - 1) / NW;
-    int t_cur = 0, t_end = 0, t_step = 1;
-    if (PS) {
-        const int total = tiles_x * tiles_y * a.N, G = (int)gridDim.x;
-#ifdef CRFP_DF_PS_NOBAND   // A/B builds: natural order (tile = workgroup id + k * workgroups)
-        t_cur = (int)blockIdx.x; t_end = total; t_step = G;
-#else
-        const int q = total >> 3, r = total & 7, x = (int)blockIdx.x & 7;
-        const int band0 = x * q + min(x, r);
-        t_cur = band0 + ((int)blockIdx.x >> 3); t_end = band0 + q + (x < r ? 1 : 0); t_step = G >> 3;
-#endif
-        if (t_cur >= t_end) return;
-    }
-    int tx0, ty0, n;
-#define DF_DECODE(T_, TX, TY, NN)                                                                         \
-    {                                                                                                     \
-        const int per_ = tiles_x * tiles_y, n_ = (T_) / per_, r_ = (T_) - n_ * per_, y_ = r_ / tiles_x;   \
-        NN = n_; TY = y_ * NW; TX = (r_ - y_ * tiles_x) * 32;                                             \
-    }
-    if (PS) DF_DECODE(t_cur, tx0, ty0, n)
-#if CRFP_DF_BAND_NP   // the one-tile form walks the tile list in the XCD-banded order too (xcd_band_tile over the launch's linear workgroup id)
-    else if (DB) {
-        const int lin_ = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-        const int tb_ = xcd_band_tile(lin_, (int)(gridDim.x * gridDim.y * gridDim.z));
-        DF_DECODE(tb_, tx0, ty0, n)
-    }
-#endif
-    else { tx0 = blockIdx.x * 32; ty0 = blockIdx.y * NW; n = blockIdx.z; }
-
-    f32x4 rt[DF_NIN];
-    // the offset feature's halo tile of tile (TX, TY, NN) into rt[] (clamped addresses; what lies outside the image is zeroed on the way to LDS)
-#define DF_TLOAD(TX, TY, NN)                                                                              \
-    {                                                                                                     \
-        const f32x4* __restrict__ s3_ = reinterpret_cast<const f32x4*>(a.feat + (long long)(NN) * a.feat_b); \
-        _Pragma("unroll") for (int t = 0; t < DF_NIN; ++t) {                                              \
-            const int idc = min(ltid + NT * t, 8 * DF_NEL - 1);                                           \
-            const int pl = idc / DF_NEL, pix = idc - pl * DF_NEL, r = pix / DF_LW, c = pix - r * DF_LW;   \
-            const int gy = (TY) + r - 1, gx = (TX) + c - 1;                                               \
-            rt[t] = s3_[((long long)pl * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)];       \
-        }                                                                                                 \
-    }
-    int ltid = tid0;  // the thread id as the tile loop sees it: re-defined (opaquely) per tile in the persistent form, so that everything derived
-                      // from it (lane / wave / LDS addresses / the loaders' index math) is recomputed where it is used instead of being hoisted
-                      // out of the tile loop into long-lived registers -- the kernel has none to spare
-    DF_TLOAD(tx0, ty0, n)
-    const f32x4* __restrict__ wc = reinterpret_cast<const f32x4*>(a.wconv);
-    f32x4 rws[DF_NWS];
-#define DF_WLOAD(ST)                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < DF_NWS; ++k) rws[k] = wc[(ST) * DF_WST + min(ltid + NT * k, DF_WST - 1)];
-    DF_WLOAD(0)
-    // Round 5 (CRFP_DF_LATE_PROLOGUE, default on for the 8-wave form): only what the first MFMA needs -- the halo tile and weight stage 0 -- is
-    // fetched in front of the first barrier.  The DCN weight image (36 KB, first used by the sampler's MFMAs behind stage 1's barrier) and weight
-    // stage 1 used to be ingested there too: 153 KB per workgroup before any MFMA, four rounds per launch.  They now land during cout tile 0,
-    // which has no sampler work to hide anyway (DF_BEGIN).  Same values in the same places before their first use: bit-identical.
-    // (PS: the DCN weight image is fetched once per workgroup, in front of the tile loop.)
-#ifndef CRFP_DF_LATE_PROLOGUE
-#define CRFP_DF_LATE_PROLOGUE 1
-#endif
-    constexpr bool LATE = DB && CRFP_DF_LATE_PROLOGUE;
-    static_assert(!PS || LATE, "the persistent form builds on the late prologue");
-    constexpr bool LATE_WL = LATE && !PS;   // the DCN weight image rides in rwl through cout tile 0
-    constexpr int DF_NWL = (36 * 64 + NT - 1) / NT;
-    f32x4 rwl[LATE_WL ? DF_NWL : 1];
-    if (!LATE_WL)
-        for (int i = tid0; i < 36 * 64; i += NT) wl[i] = reinterpret_cast<const f32x4*>(a.wdcn)[i];
-    if (DB && tid0 < 56) bl[tid0] = reinterpret_cast<const f32x4*>(a.bconv)[tid0];
-    float bv[4];   // NW = 4: no LDS left for the bias table
-#pragma unroll
-    for (int k = 0; k < 4; ++k) bv[k] = DB ? 0.0f : a.bconv[min(64 * k + (tid0 & 63), 223)];
-    const long long plane = (long long)H * W * 4;
-    const int PW = W + 1, pitch = PW * QB, plane_b = (H + 1) * pitch;
-    const int guard = pitch + QB;
-    const float fH = (float)H, fW = (float)W;
-    // the halo tile in rt[] (tile at (TX, TY)) and weight stage 0 in rws[] go to LDS
-#define DF_WRITE(B)                                                                                       \
-    _Pragma("unroll") for (int k = 0; k < DF_NWS; ++k) {                                                  \
-        const int idx = ltid + NT * k;                                                                    \
-        if (idx < DF_WST) wst[B][idx] = rws[k];                                                           \
-    }
-#define DF_TWRITE(TX, TY)                                                                                 \
-    _Pragma("unroll") for (int t = 0; t < DF_NIN; ++t) {                                                  \
-        const int idx = ltid + NT * t;                                                                    \
-        const int pl = idx / DF_NEL, pix = idx - pl * DF_NEL, r = pix / DF_LW, c = pix - r * DF_LW;       \
-        const int gy = (TY) + r - 1, gx = (TX) + c - 1;                                                   \
-        const bool tv = gy >= 0 && gy < H && gx >= 0 && gx < W;                                           \
-        if (idx < 8 * DF_NEL) (&tile[0][0])[idx] = tv ? rt[t] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};            \
-    }
-    DF_TWRITE(tx0, ty0)
-    if (DB) { DF_WRITE(0) if (!LATE) { DF_WLOAD(1) } }   // stage 0 in LDS (LATE: stage 1 is requested behind the first barrier)
-
-    for (;;) {   // one tile per trip (not PS: one trip)
-    if (PS) asm volatile("" : "+v"(ltid));
-    const int tid = ltid, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int hbase = 4 * h * plane_b + guard;
-    const int px = tx0 + j, py = ty0 + wave;
-    const bool valid = px < W && py < H;
-    const int cx = min(px, W - 1), cy = min(py, H - 1);
-    const float2 fl = *reinterpret_cast<const float2*>(a.flow + (long long)n * a.flow_b + ((long long)cy * W + cx) * 2);
-    const float cfy = 10.0f + fl.y, cfx = 10.0f + fl.x;
-    int ntx0 = 0, nty0 = 0, nn = 0;   // (PS) the workgroup's next tile
-    const bool has_next = PS && t_cur + t_step < t_end;
-
-    // sampler set-up (dcn_g8_pipe_kernel)
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)const_cast<act_t*>(as_act(a.x) + (long long)n * a.xb) - guard, 0, 8 * plane_b + guard, 0x00020000);
-    const float fy0 = (float)(cy - 1), fx0 = (float)(cx - 1);
-
-    f32x16 acc, acl, ca, cl;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc[e] = 0.0f; acl[e] = 0.0f; }
-#ifdef CRFP_LAB
-    const int DF_PROBE = a.probe;   // timing experiments (results wrong), bits: 1 = no sampling, 2 = no conv MFMAs, 4 = no barriers / weight streaming after stage 0, 8 = barriers but no weight streaming, 32 = conv MFMAs without operand reads, 64 = weight reads only
-#elif defined(CRFP_DF_PROBE_CT)   // A/B builds of the PRODUCT kernel with a compile-time probe (the lab build's run-time probe word costs registers)
-    constexpr int DF_PROBE = CRFP_DF_PROBE_CT;
-#else
-    constexpr int DF_PROBE = 0;
-#endif
-#ifdef CRFP_LAB
-    const float pz = (DF_PROBE & 16) ? 0.0f : 1.0f;   // 16: zero offsets = regular, coalesced sampling positions
-#else
-    constexpr float pz = 1.0f;
-#endif
-    float ov[108];   // activated (dy, dx, mask) of position p at 3 p + c; every index below is a compile-time constant
-    DcnPair Q0, Q1;
-    const f32x4* wcur = &wst[0][0];
-    dcn_f16x8 pw0, pw1, pb0, pb1;   // operands of the next tap (round 5)
-
-    // one (cout tile, chunk) stage = DF_BEGIN (weights registers -> LDS, next stage's loads) + 9 taps x 3 MFMAs (DF_TAPS)
-    // single buffer: barrier (everyone done with the previous stage), registers -> LDS, barrier, next stage's loads.
-    // double buffer: one barrier (stage s complete in buffer s & 1 and everyone done with stage s - 1), then the registers
-    // (stage s + 1) go to the other buffer and stage s + 2's loads leave.  LATE: stage 0 only requests stage 1 and the DCN weight image
-    // behind its barrier; they are written to LDS at the chunk boundary of cout tile 0 (DF_BEGIN(0, 1)), where stage 2's loads leave.
-#define DF_BEGIN(T, CH)                                                                                   \
-    if (CPS == 2 && (CH) == 1) {                                                                          \
-        wcur = &wst[(T) & 1][DF_WCH];                                                                     \
-        if (LATE && (T) == 0) {                                                                           \
-            DF_WRITE(1)                                                                                   \
-            if (LATE_WL) {                                                                                \
-                _Pragma("unroll") for (int k = 0; k < DF_NWL; ++k)                                        \
-                    if (tid + NT * k < 36 * 64) wl[tid + NT * k] = rwl[k];                                \
-            }                                                                                             \
-            DF_WLOAD(2)                                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                            \
-        }                                                                                                 \
-    } else {                                                                                              \
-        constexpr int s_ = (2 * (T) + (CH)) / CPS;                                                        \
-        const bool first_ = s_ == 0;                                                                      \
-        if (first_ || !(DF_PROBE & 4)) df_lds_barrier();                                                  \
-        if (DB && LATE && first_) {                                                                       \
-            DF_WLOAD(1)                                                                                   \
-            if (LATE_WL) {                                                                                \
-                _Pragma("unroll") for (int k = 0; k < DF_NWL; ++k)                                        \
-                    rwl[k] = reinterpret_cast<const f32x4*>(a.wdcn)[min(tid + NT * k, 36 * 64 - 1)];      \
-            }                                                                                             \
-        } else if (DB) {                                                                                  \
-            if (s_ + 1 < NSTG) { DF_WRITE((s_ + 1) & 1) }                                                 \
-            if (s_ + 2 < NSTG) { DF_WLOAD(s_ + 2) }                                                       \
-        } else {                                                                                          \
-            if (first_ || !(DF_PROBE & 12)) { DF_WRITE(0) }                                               \
-            if (first_ || !(DF_PROBE & 4)) df_lds_barrier();                                              \
-            if (s_ + 1 < NSTG && !(DF_PROBE & 12)) { DF_WLOAD(s_ + 1) }                                   \
-        }                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);   /* the next stage's loads leave before this stage's MFMAs */  \
-        wcur = &wst[DB ? (s_ & 1) : 0][0];                                                                \
-    }
-    // Round 5: the operands of the NEXT tap are read from LDS before the current tap's MFMAs (one register set ahead: +16 VGPRs, 234 -> 250).
-    // hipcc had placed every tap's four ds_read_b128 directly in front of its MFMAs behind s_waitcnt lgkmcnt(0 / 1): one exposed LDS round trip
-    // per tap on a kernel with two waves per SIMD (378 conv MFMAs per wave).  The whole-tile weight stage of the 8-wave form holds both chunks,
-    // so the prefetch runs across the chunk boundary; the first tap of a cout tile (behind the stage barrier) loads its own operands.  Same
-    // operations on the same values in the same order: bit-identical.
-    // Round 5: the scheduling region (sampler item + tap) is laid out as 4 DS reads, then 3 x (1 MFMA, CRFP_DF_SGB vector instructions) with
-    // sched_group_barrier, so that the sampler's vector work sits INSIDE each MFMA's shadow instead of in front of a burst of three MFMAs
-    // (gaps of one instruction between MFMAs: 196 -> 60; same-box 131.2 -> 128.4 us, bit-identical; 10 per MFMA: the same; GAP 3 / 7 / 9 / 12
-    // of the generated schedule: 130.0 / 128.8 / 131.8 / 139.4, profiles/r05_dcn_fused_sgb_ab.txt).  -DCRFP_DF_SGB=0: the fenced form.
-#ifndef CRFP_DF_SGB
-#define CRFP_DF_SGB 6
-#endif
-#if defined(CRFP_LAB) && !defined(CRFP_DF_NO_PREFETCH)
-#define CRFP_DF_NO_PREFETCH   // the lab build carries a run-time probe word in this kernel: with the 16 prefetch registers on top it spills (96 B, 255 us)
-#endif
-#if CRFP_DF_SGB > 0
-#define DF_TAP_FENCE
-#define DF_TAP_PIPELINE                                                                                   \
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                                \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, CRFP_DF_SGB, 0); \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, CRFP_DF_SGB, 0); \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, CRFP_DF_SGB, 0);
-#else
-#define DF_TAP_FENCE __builtin_amdgcn_sched_barrier(0);   /* the next tap's reads leave before this tap's MFMAs */
-#define DF_TAP_PIPELINE
-#endif
-#ifndef CRFP_DF_NO_PREFETCH
-#define DF_LDOPS(W0, W1, B0, B1, WB, CH_, TAP_)                                                           \
-    {                                                                                                     \
-        const int ky_ = (TAP_) / 3, kx_ = (TAP_) - 3 * ky_;                                               \
-        const int pix_ = (wave + ky_) * DF_LW + j + kx_;                                                  \
-        W0 = __builtin_bit_cast(dcn_f16x8, (WB)[((TAP_) * 2) * 64 + lane]);                               \
-        W1 = __builtin_bit_cast(dcn_f16x8, (WB)[((TAP_) * 2 + 1) * 64 + lane]);                           \
-        B0 = __builtin_bit_cast(dcn_f16x8, tile[2 * (CH_) + h][pix_]);                                    \
-        B1 = __builtin_bit_cast(dcn_f16x8, tile[4 + 2 * (CH_) + h][pix_]);                                \
-    }
-#define DF_TAPS(CH, TA, TB)                                                                               \
-    if (!(DF_PROBE & 2))                                                                                  \
-    _Pragma("unroll") for (int tap = (TA); tap < (TB); ++tap) {                                           \
-        dcn_f16x8 w0, w1, b0, b1;                                                                         \
-        const bool have_ = CPS == 2 ? !((CH) == 0 && tap == 0) : tap != 0;   /* prefetched by the tap before */ \
-        if (have_) { w0 = pw0; w1 = pw1; b0 = pb0; b1 = pb1; }                                            \
-        else DF_LDOPS(w0, w1, b0, b1, wcur, CH, tap)                                                      \
-        if (DF_PROBE & 32) { /* lab probe: no operand reads after a tile's first tap (results wrong) */ }  \
-        else if ((DF_PROBE & 64) && tap < 8) { /* lab probe: weights only (no activation reads) */         \
-            pw0 = __builtin_bit_cast(dcn_f16x8, wcur[((tap + 1) * 2) * 64 + lane]);                       \
-            pw1 = __builtin_bit_cast(dcn_f16x8, wcur[((tap + 1) * 2 + 1) * 64 + lane]);                   \
-        }                                                                                                 \
-        else if (tap < 8) DF_LDOPS(pw0, pw1, pb0, pb1, wcur, CH, tap + 1)                                 \
-        else if (CPS == 2 && (CH) == 0) DF_LDOPS(pw0, pw1, pb0, pb1, wcur + DF_WCH, 1, 0)                 \
-        DF_TAP_FENCE                                                                                      \
-        cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b1, cl, 0, 0, 0);                                 \
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b0, ca, 0, 0, 0);                                 \
-        cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, b0, cl, 0, 0, 0);                                 \
-        DF_TAP_PIPELINE                                                                                   \
-    }
-#else
-#define DF_TAPS(CH, TA, TB)                                                                               \
-    if (!(DF_PROBE & 2))                                                                                  \
-    _Pragma("unroll") for (int tap = (TA); tap < (TB); ++tap) {                                           \
-        const int ky = tap / 3, kx = tap - 3 * ky;                                                        \
-        const dcn_f16x8 w0 = __builtin_bit_cast(dcn_f16x8, wcur[(tap * 2) * 64 + lane]);                  \
-        const dcn_f16x8 w1 = __builtin_bit_cast(dcn_f16x8, wcur[(tap * 2 + 1) * 64 + lane]);              \
-        const int pix = (wave + ky) * DF_LW + j + kx;                                                     \
-        const dcn_f16x8 b0 = __builtin_bit_cast(dcn_f16x8, tile[2 * (CH) + h][pix]);                      \
-        const dcn_f16x8 b1 = __builtin_bit_cast(dcn_f16x8, tile[4 + 2 * (CH) + h][pix]);                  \
-        cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b1, cl, 0, 0, 0);                                 \
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b0, ca, 0, 0, 0);                                 \
-        cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, b0, cl, 0, 0, 0);                                 \
-    }
-#endif
-    // the accumulators of cout tile T start at its bias, as in the two-kernel path: the 224 packed biases sit in 4 VGPRs
-    // (lane L holds rows L, 64 + L, ...) and each value arrives through v_readlane -- scalar loads here cost a cache-miss
-    // round trip per cout tile and quad (28 per wave, a third of the kernel's fixed cost when measured), per-lane vector
-    // loads would drain the gathers in flight
-#define DF_BIAS(T)                                                                                        \
-    if (DB) {   /* four ds_read_b128 of the lane half's quads (lgkmcnt: the gathers in flight are not waited for) */ \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                   \
-            const f32x4 bq = bl[(T) * 8 + 2 * q + h];                                                     \
-            ca[4 * q] = bq.x; ca[4 * q + 1] = bq.y; ca[4 * q + 2] = bq.z; ca[4 * q + 3] = bq.w;           \
-        }                                                                                                 \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) cl[e] = 0.0f;                                      \
-    } else {                                                                                              \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                  \
-            const int r0 = 32 * (T) + 8 * (e >> 2) + (e & 3), r1 = r0 + 4;                                \
-            const float s0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv[r0 >> 6]), r0 & 63)); \
-            const float s1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv[r1 >> 6]), r1 & 63)); \
-            ca[e] = h ? s1 : s0;                                                                          \
-            cl[e] = 0.0f;                                                                                 \
-        }                                                                                                 \
-    }
-    // end of cout tile T: the raw sums go to ov[] (the accumulators are free for tile T + 1); 10 tanh + flow / sigmoid follow
-    // in place, inside the first taps of tile T + 1
-#define DF_RAW(T)                                                                                         \
-    {                                                                                                     \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                  \
-            const int sl = 16 * (T) + e;                                                                  \
-            if (sl < 108) {                                                                               \
-                /* = ca + cl * 2^-11 as the two-kernel path forms it (the product is exact), in one instruction */ \
-                ov[sl] = __builtin_fmaf(cl[e], 1.0f / 2048.0f, ca[e]);                                    \
-            }                                                                                             \
-        }                                                                                                 \
-    }
-#define DF_TRANS(T)                                                                                       \
-    {                                                                                                     \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                  \
-            const int sl = 16 * (T) + e;                                                                  \
-            if (sl < 108)                                                                                 \
-                ov[sl] = sl % 3 == 0 ? tanh10_plus(ov[sl], cfy) : (sl % 3 == 1 ? tanh10_plus(ov[sl], cfx) : fast_sigmoid(ov[sl])); \
-        }                                                                                                 \
-    }
-#define DF_SB __builtin_amdgcn_sched_barrier(0);
-#define DF_I(U, P)                                                                                        \
-    if (!(DF_PROBE & 1)) {                                                                                \
-        dcn_issue_one(P, 0, rx, ov[6 * (U)] * pz, ov[6 * (U) + 1] * pz, ov[6 * (U) + 2], 2 * (U), fy0, fx0, fH, fW, PW, pitch, plane_b, hbase); \
-        dcn_issue_one(P, 1, rx, ov[6 * (U) + 3] * pz, ov[6 * (U) + 4] * pz, ov[6 * (U) + 5], 2 * (U) + 1, fy0, fx0, fH, fW, PW, pitch, plane_b, hbase); \
-    }
-#define DF_C(U, P)                                                                                        \
-    if (!(DF_PROBE & 1)) { dcn_consume_pair(P, acc, acl, wl, U, lane); }
-    // micro-items of the round-3 schedule (dcn_fused_schedule.inc): a quarter of a tile's activations, one position's coordinates +
-    // gathers, one position's blend, one pair's split + DCN MFMAs
-#define DF_TR(T, Q)                                                                                       \
-    {                                                                                                     \
-        _Pragma("unroll") for (int e = 4 * (Q); e < 4 * (Q) + 4; ++e) {                                   \
-            const int sl = 16 * (T) + e;                                                                  \
-            if (sl < 108)                                                                                 \
-                ov[sl] = sl % 3 == 0 ? tanh10_plus(ov[sl], cfy) : (sl % 3 == 1 ? tanh10_plus(ov[sl], cfx) : fast_sigmoid(ov[sl])); \
-        }                                                                                                 \
-    }
-#define DF_I1(U, PI, P)                                                                                   \
-    if (!(DF_PROBE & 1)) {                                                                                \
-        dcn_issue_one(P, PI, rx, ov[6 * (U) + 3 * (PI)] * pz, ov[6 * (U) + 3 * (PI) + 1] * pz, ov[6 * (U) + 3 * (PI) + 2], 2 * (U) + (PI), \
-                      fy0, fx0, fH, fW, PW, pitch, plane_b, hbase);                                       \
-    }
-#define DF_L(U, PI, P) if (!(DF_PROBE & 1)) { dcn_lerp_one(P, PI, xs); }
-#define DF_S(U) if (!(DF_PROBE & 1)) { dcn_split_mfma(xs, acc, acl, wl, U, lane); }
-    float xs[8];
-    // (PS) hooks in the schedule's tail (behind the last conv MFMA, where rt, rws, the conv accumulators and the operand prefetch registers are
-    // dead).  DF_TAIL_REQUEST, behind the last gather issue: the next tile's halo tile and weight stage 0 are requested (no gather queues behind
-    // them in the in-order vmcnt).  DF_TAIL_COMMIT, behind the last DCN MFMA: one barrier (every wave is past its last conv operand read), then
-    // they go to LDS -- the next tile's first barrier publishes them.  Their registers never live across the loop's back edge.
-#define DF_TAIL_REQUEST                                                                                   \
-    if (PS) {                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        DF_DECODE(has_next ? t_cur + t_step : t_cur, ntx0, nty0, nn)                                      \
-        if (!(DF_PS_PROBE & 1)) { DF_TLOAD(ntx0, nty0, nn) DF_WLOAD(0) }                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-    }
-#define DF_TAIL_COMMIT                                                                                    \
-    if (PS && has_next) {                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        df_lds_barrier();                                                                                 \
-        if (!(DF_PS_PROBE & 2)) { DF_TWRITE(ntx0, nty0) DF_WRITE(0) }                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-    }
-#ifdef CRFP_DF_SCHED_R2
-    // Cout tile T completes the sampling pairs up to (16 T + 10) / 6: 1, 4, 7, 9, 12, 15, 17.  The pairs of tile T are sampled
-    // INSIDE the two stages of tile T + 1, between its taps: the MFMA runs 32 clocks in its own pipe while the wave issues the
-    // sampler's VALU work (coordinates, weights, bilinear FMAs, fp16 split: as many issue clocks per pixel as the MFMAs take),
-    // and a pair's gathers fly under the MFMAs issued before its consumption.  Pair u lives in Q[u & 1]; I(u) follows C(u - 2).
-    DF_BEGIN(0, 0) DF_BIAS(0) DF_TAPS(0, 0, 9)   // (the bias table in LDS is complete behind the first barrier)
-    DF_BEGIN(0, 1) DF_TAPS(1, 0, 9) DF_RAW(0)
-    DF_BIAS(1)
-    DF_BEGIN(1, 0) DF_TAPS(0, 0, 3) DF_TRANS(0) DF_SB DF_TAPS(0, 3, 6) DF_I(0, Q0) DF_SB DF_TAPS(0, 6, 9) DF_I(1, Q1) DF_SB
-    DF_BEGIN(1, 1) DF_TAPS(1, 0, 4) DF_SB DF_C(0, Q0) DF_SB DF_TAPS(1, 4, 9) DF_SB DF_C(1, Q1) DF_SB DF_RAW(1)
-    DF_BIAS(2)
-    DF_BEGIN(2, 0) DF_TAPS(0, 0, 3) DF_TRANS(1) DF_SB DF_TAPS(0, 3, 6) DF_I(2, Q0) DF_SB DF_TAPS(0, 6, 9) DF_I(3, Q1) DF_SB
-    DF_BEGIN(2, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(2, Q0) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(3, Q1) DF_SB DF_TAPS(1, 6, 9) DF_I(4, Q0) DF_SB DF_RAW(2)
-    DF_BIAS(3)
-    DF_BEGIN(3, 0) DF_TAPS(0, 0, 2) DF_TRANS(2) DF_SB DF_TAPS(0, 2, 4) DF_I(5, Q1) DF_SB DF_TAPS(0, 4, 7) DF_SB DF_C(4, Q0) DF_SB DF_TAPS(0, 7, 9) DF_I(6, Q0) DF_SB
-    DF_BEGIN(3, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(5, Q1) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(6, Q0) DF_SB DF_TAPS(1, 6, 9) DF_I(7, Q1) DF_SB DF_RAW(3)
-    DF_BIAS(4)
-    DF_BEGIN(4, 0) DF_TAPS(0, 0, 2) DF_TRANS(3) DF_SB DF_TAPS(0, 2, 4) DF_SB DF_C(7, Q1) DF_SB DF_TAPS(0, 4, 7) DF_I(8, Q0) DF_SB DF_TAPS(0, 7, 9) DF_I(9, Q1) DF_SB
-    DF_BEGIN(4, 1) DF_TAPS(1, 0, 4) DF_SB DF_C(8, Q0) DF_SB DF_TAPS(1, 4, 9) DF_SB DF_C(9, Q1) DF_SB DF_RAW(4)
-    DF_BIAS(5)
-    DF_BEGIN(5, 0) DF_TAPS(0, 0, 3) DF_TRANS(4) DF_SB DF_TAPS(0, 3, 6) DF_I(10, Q0) DF_SB DF_TAPS(0, 6, 9) DF_I(11, Q1) DF_SB
-    DF_BEGIN(5, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(10, Q0) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(11, Q1) DF_SB DF_TAPS(1, 6, 9) DF_I(12, Q0) DF_SB DF_RAW(5)
-    DF_BIAS(6)
-    DF_BEGIN(6, 0) DF_TAPS(0, 0, 2) DF_TRANS(5) DF_SB DF_TAPS(0, 2, 4) DF_I(13, Q1) DF_SB DF_TAPS(0, 4, 7) DF_SB DF_C(12, Q0) DF_SB DF_TAPS(0, 7, 9) DF_I(14, Q0) DF_SB
-    DF_BEGIN(6, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(13, Q1) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(14, Q0) DF_SB DF_TAPS(1, 6, 9) DF_I(15, Q1) DF_SB DF_RAW(6)
-    DF_TRANS(6) DF_I(16, Q0) DF_SB DF_C(15, Q1) DF_SB DF_I(17, Q1) DF_SB DF_TAIL_REQUEST DF_C(16, Q0) DF_SB DF_C(17, Q1) DF_TAIL_COMMIT
-#else
-    // Round 3: ONE micro-item in front of EVERY tap instead of whole pairs between groups of 2-4 taps (tools/gen/dcn_fused_schedule.py
-    // holds the dependency rules and writes the table): <= ~30 vector instructions per 3 MFMAs, the regime in which
-    // tools/micro/mfma_valu_overlap2 shows the vector work disappearing in the MFMA gaps.  Same operations on the same values in
-    // the same per-accumulator order: bit-identical to the round-2 table (-DCRFP_DF_SCHED_R2) and to the two-kernel path.
-#ifdef CRFP_DF_SCHED_INC   // A/B builds: another run of the generator
-#include CRFP_DF_SCHED_INC
-#else
-#include "dcn_fused_schedule.inc"
-#endif
-#endif
-#undef DF_C
-#undef DF_I
-#undef DF_TR
-#undef DF_I1
-#undef DF_L
-#undef DF_S
-#undef DF_TAPS
-#ifdef DF_LDOPS
-#undef DF_LDOPS
-#endif
-#undef DF_BEGIN
-#undef DF_WRITE
-#undef DF_SB
-#undef DF_TRANS
-#undef DF_RAW
-#undef DF_BIAS
-    if (valid) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] += acl[e] * (1.0f / 2048.0f);
-        act_t* o = as_act(a.out) + (long long)n * a.ob + ((long long)py * W + px) * 4;
-        float vmax = 0.0f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int cq = 2 * g + h;
-            const float4 bb = *reinterpret_cast<const float4*>(a.bdcn + 4 * cq);
-            const float4 v = make_float4(acc[4 * g] + bb.x, acc[4 * g + 1] + bb.y, acc[4 * g + 2] + bb.z, acc[4 * g + 3] + bb.w);
-            vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-            stq(o + cq * plane, cf32x4{v.x, v.y, v.z, v.w});
-        }
-        if (a.ovf && !(vmax < 65504.0f)) atomicOr(ovf_word(a.ovf, a.ovf_div, 0, n), 1u);
-    }
-    if (!has_next) break;
-    t_cur += t_step;
-    tx0 = ntx0; ty0 = nty0; n = nn;
-    }   // tiles
-#undef DF_TAIL_REQUEST
-#undef DF_TAIL_COMMIT
-#undef DF_TWRITE
-#undef DF_WLOAD
-#undef DF_TLOAD
-#undef DF_DECODE
-}
-
-#ifdef CRFP_LAB   // lost its A/B (141.2 vs 136.6 us): lab library only (round 5)
-// ---------------------------------------------------------------- round 3: the same fusion with ROLE-SPECIALISED waves
-// dcn_fused_kernel<8> runs conv taps and sampler items in ONE instruction stream per wave: 246 VGPRs = two waves per SIMD, and
-// whatever stalls the stream (an LDS operand read in front of an MFMA, a gather that has not landed, a barrier) stalls both roles'
-// work of that wave.  Per workgroup ~70 k cycles against 13.8 k of MFMA pipe time and 11 k of vector issue per wave; a finer
-// interleave and static wave priorities changed nothing (profiles/r03_mfma_valu_overlap_microtest.txt).
-// Here a workgroup is 16 waves on the same 8 x 32-pixel tile: waves 0-7 ("conv", row = wave) run ONLY the 32 -> 216 head -- the
-// MFMA stream, the weight stages (global -> registers -> LDS, double-buffered per 16-channel chunk) and the tanh / sigmoid of the
-// finished cout tile -- and hand the 16 activated (dy, dx, mask) values per lane of each tile to their partner wave 8 + row
-// ("sampler") through a 32 KB LDS block; waves 8-15 run ONLY coordinates, gathers, bilinear blends, fp16 split and the 54 DCN
-// MFMAs.  Each role fits 128 VGPRs, so four waves share a SIMD (two of each role) and a stalled sampler leaves the SIMD to the
-// MFMA stream and vice versa.  Hand-off: one workgroup barrier per chunk stage (15 in all); the values of tile T are written after
-// barrier 2T+1 and read after barrier 2T+2, those of tile T-1 are read (into registers) right after barrier 2T -- a full
-// barrier earlier -- so the block needs no second slot and no flags.  Same operations on the same values in the same per-accumulator
-// order as dcn_fused_kernel<8> and the two-kernel path: bit-identical results.
-// LDS: halo tile 43.5 KB + weight stages 2 x 18.4 KB + hand-off block 32 KB + DCN weight image 36 KB + biases 0.9 KB = 149 KB.
-constexpr int D2_NT = 1024, D2_NEL = 10 * DF_LW, D2_NIN = (8 * D2_NEL + D2_NT - 1) / D2_NT;
-constexpr int D2_NWS = (DF_WCH + 511) / 512;   // weight elements per conv-wave thread and chunk stage (512 conv threads)
-
-__global__ __launch_bounds__(D2_NT, 1) void dcn_fused2_kernel(const DcnFuseArgs a) {
-    __shared__ f32x4 tile[8][D2_NEL];          // [part * 4 + 8-channel group][halo pixel]
-    __shared__ f32x4 wst[2][DF_WCH];           // one (cout tile, chunk) stage per buffer
-    __shared__ float ovl[16][8][64];           // hand-off block: [slot of the tile][row][lane]
-    __shared__ f32x4 wl[36 * 64];              // DCN weight image (sampler)
-    __shared__ f32x4 bl[56];                   // the head's 224 packed biases
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool conv = wave < 8;
-    const int row = wave & 7, ctid = tid & 511;   // ctid: index among the 512 threads of this role
-    const int j = lane & 31, h = lane >> 5;
-    const int tx0 = blockIdx.x * 32, ty0 = blockIdx.y * 8, n = blockIdx.z;
-    const int H = a.H, W = a.W;
-#ifdef CRFP_LAB
-    const int D2_PROBE = a.probe;   // lab timing experiments (results wrong), bits: 1 = no sampling, 2 = no conv MFMAs, 4 = sampler waves at s_setprio 2, 8 = conv waves at s_setprio 2
-    if (D2_PROBE & 4) { if (!conv) __builtin_amdgcn_s_setprio(2); }
-    if (D2_PROBE & 8) { if (conv) __builtin_amdgcn_s_setprio(2); }
-#else
-    constexpr int D2_PROBE = 0;
-#endif
-
-    // ---- prologue, all 1024 threads: halo tile, DCN weights, biases
-    {
-        const f32x4* __restrict__ s3 = reinterpret_cast<const f32x4*>(a.feat + (long long)n * a.feat_b);
-        f32x4 rt[D2_NIN];
-        bool tv[D2_NIN];
-#pragma unroll
-        for (int t = 0; t < D2_NIN; ++t) {
-            const int idx = tid + D2_NT * t, idc = min(idx, 8 * D2_NEL - 1);
-            const int pl = idc / D2_NEL, pix = idc - pl * D2_NEL, r = pix / DF_LW, c = pix - r * DF_LW;
-            const int gy = ty0 + r - 1, gx = tx0 + c - 1;
-            tv[t] = idx < 8 * D2_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            rt[t] = s3[((long long)pl * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)];
-        }
-        for (int i = tid; i < 36 * 64; i += D2_NT) wl[i] = reinterpret_cast<const f32x4*>(a.wdcn)[i];
-        if (tid < 56) bl[tid] = reinterpret_cast<const f32x4*>(a.bconv)[tid];
-#pragma unroll
-        for (int t = 0; t < D2_NIN; ++t) {
-            const int idx = tid + D2_NT * t;
-            if (idx < 8 * D2_NEL) (&tile[0][0])[idx] = tv[t] ? rt[t] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        }
-    }
-
-    if (conv) {
-        // ================================================================ conv waves
-        const f32x4* __restrict__ wc = reinterpret_cast<const f32x4*>(a.wconv);
-        f32x4 rws[D2_NWS];
-#define D2_WLOAD(ST) _Pragma("unroll") for (int k = 0; k < D2_NWS; ++k) rws[k] = wc[(ST) * DF_WCH + min(ctid + 512 * k, DF_WCH - 1)];
-#define D2_WRITE(B)                                                                                       \
-    _Pragma("unroll") for (int k = 0; k < D2_NWS; ++k) {                                                  \
-        const int idx = ctid + 512 * k;                                                                   \
-        if (idx < DF_WCH) wst[B][idx] = rws[k];                                                           \
-    }
-        D2_WLOAD(0)
-        D2_WRITE(0)
-        D2_WLOAD(1)
-        const int px = tx0 + j, py = ty0 + row;
-        const int cx = min(px, W - 1), cy = min(py, H - 1);
-        const float2 fl = *reinterpret_cast<const float2*>(a.flow + (long long)n * a.flow_b + ((long long)cy * W + cx) * 2);
-        const float cfy = 10.0f + fl.y, cfx = 10.0f + fl.x;
-        f32x16 ca, cl;
-#pragma unroll
-        for (int T = 0; T < 7; ++T) {
-#pragma unroll
-            for (int CH = 0; CH < 2; ++CH) {
-                const int st = 2 * T + CH;
-                __syncthreads();   // barrier `st`: stage st is in wst[st & 1], nobody reads wst[(st + 1) & 1] any more
-                if (CH == 0) {     // accumulators start at the bias (two-kernel path); the table is complete behind barrier 0
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 bq = bl[T * 8 + 2 * q + h];
-                        ca[4 * q] = bq.x; ca[4 * q + 1] = bq.y; ca[4 * q + 2] = bq.z; ca[4 * q + 3] = bq.w;
-                    }
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) cl[e] = 0.0f;
-                }
-                if (st + 1 < 14) { D2_WRITE((st + 1) & 1) }
-                if (st + 2 < 14) { D2_WLOAD(st + 2) }
-                __builtin_amdgcn_sched_barrier(0);   // the next stages' traffic leaves before this stage's MFMAs
-                const f32x4* wcur = &wst[st & 1][0];
-                if (!(D2_PROBE & 2))
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const int ky = tap / 3, kx = tap - 3 * ky;
-                    const dcn_f16x8 w0 = __builtin_bit_cast(dcn_f16x8, wcur[(tap * 2) * 64 + lane]);
-                    const dcn_f16x8 w1 = __builtin_bit_cast(dcn_f16x8, wcur[(tap * 2 + 1) * 64 + lane]);
-                    const int pix = (row + ky) * DF_LW + j + kx;
-                    const dcn_f16x8 b0 = __builtin_bit_cast(dcn_f16x8, tile[2 * CH + h][pix]);
-                    const dcn_f16x8 b1 = __builtin_bit_cast(dcn_f16x8, tile[4 + 2 * CH + h][pix]);
-                    cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b1, cl, 0, 0, 0);
-                    ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b0, ca, 0, 0, 0);
-                    cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, b0, cl, 0, 0, 0);
-                }
-            }
-            // tile T done: raw sum = ca + cl * 2^-11 (one exact-product FMA), 10 tanh + flow / sigmoid, hand the 16 values over
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int sl = 16 * T + e, c3 = sl % 3;   // slot 3 p + c: component c of the half's position p (compile-time)
-                if (sl < 108) {
-                    const float raw = __builtin_fmaf(cl[e], 1.0f / 2048.0f, ca[e]);
-                    ovl[e][row][lane] = c3 == 0 ? tanh10_plus(raw, cfy) : (c3 == 1 ? tanh10_plus(raw, cfx) : fast_sigmoid(raw));
-                }
-            }
-        }
-        __syncthreads();   // barrier 14: tile 6's values are in the block
-#undef D2_WLOAD
-#undef D2_WRITE
-        return;
-    }
-
-    // ================================================================ sampler waves
-    const int px = tx0 + j, py = ty0 + row;
-    const bool valid = px < W && py < H;
-    const int cx = min(px, W - 1), cy = min(py, H - 1);
-    const long long plane = (long long)H * W * 4;
-    const int PW = W + 1, pitch = PW * QB, plane_b = (H + 1) * pitch;
-    const int guard = pitch + QB;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)const_cast<act_t*>(as_act(a.x) + (long long)n * a.xb) - guard, 0, 8 * plane_b + guard, 0x00020000);
-    const float fy0 = (float)(cy - 1), fx0 = (float)(cx - 1), fH = (float)H, fW = (float)W;
-    const int hbase = 4 * h * plane_b + guard;
-    f32x16 acc, acl;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc[e] = 0.0f; acl[e] = 0.0f; }
-    float ov[112];   // activated (dy, dx, mask) of position p at 3 p + c; every index below is a compile-time constant
-    float xs[8];
-    DcnPair Q0;
-#define D2_BAR __syncthreads();
-#define D2_GET(S) ov[S] = ovl[(S) & 15][row][lane];
-#define D2_PAIR(U)                                                                                        \
-    if (!(D2_PROBE & 1)) {                                                                                \
-        __builtin_amdgcn_sched_barrier(0);   /* the hand-off reads of later pairs stay behind this pair (registers) */ \
-        dcn_issue_one(Q0, 0, rx, ov[6 * (U)], ov[6 * (U) + 1], ov[6 * (U) + 2], 2 * (U), fy0, fx0, fH, fW, PW, pitch, plane_b, hbase); \
-        dcn_issue_one(Q0, 1, rx, ov[6 * (U) + 3], ov[6 * (U) + 4], ov[6 * (U) + 5], 2 * (U) + 1, fy0, fx0, fH, fW, PW, pitch, plane_b, hbase); \
-        dcn_lerp_one(Q0, 0, xs);                                                                          \
-        dcn_lerp_one(Q0, 1, xs);                                                                          \
-        dcn_split_mfma(xs, acc, acl, wl, U, lane);                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-    }
-    // window T (T = 1..6) = chunk stages 2T, 2T + 1: the pairs tile T - 1 completed (up to (16 (T - 1) + 10) / 6: 1, 4, 7, 9, 12, 15),
-    // split over the two stages; after barrier 14 the last two.  Barriers 0 and 1 have no sampler work behind them.  The table
-    // (tools/gen/dcn_fused2_sampler.py) reads every hand-off value as late as it is still in LDS.
-#include "dcn_fused2_sampler.inc"
-#undef D2_PAIR
-#undef D2_GET
-#undef D2_BAR
-    if (!valid) return;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] += acl[e] * (1.0f / 2048.0f);
-    act_t* o = as_act(a.out) + (long long)n * a.ob + ((long long)py * W + px) * 4;
-    float vmax = 0.0f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int cq = 2 * g + h;
-        const float4 bb = *reinterpret_cast<const float4*>(a.bdcn + 4 * cq);
-        const float4 v = make_float4(acc[4 * g] + bb.x, acc[4 * g + 1] + bb.y, acc[4 * g + 2] + bb.z, acc[4 * g + 3] + bb.w);
-        vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-        stq(o + cq * plane, cf32x4{v.x, v.y, v.z, v.w});
-    }
-    if (a.ovf && !(vmax < 65504.0f)) atomicOr(ovf_word(a.ovf, a.ovf_div, 0, n), 1u);
-}
-#endif   // CRFP_LAB (dcn_fused2_kernel)
-
-bool dcn_fused_enabled() {
-    static const bool on = !(getenv("CRFP_DCN_FUSED") && atoi(getenv("CRFP_DCN_FUSED")) == 0);
-    return on;
-}
-
-constexpr int kFusedPersistWgs = 256;   // workgroups of the persistent form = CUs of an MI355X (one 8-wave workgroup per CU: 155 KB of LDS, 250 VGPRs)
-// launches with at least this many tiles take the persistent form (six rounds of one workgroup per CU); -DCRFP_LAB: CRFP_DF_PS_MIN_TILES overrides (tests)
-static int fused_persist_min_tiles() {
-#ifdef CRFP_LAB
-    static const int v = getenv("CRFP_DF_PS_MIN_TILES") ? atoi(getenv("CRFP_DF_PS_MIN_TILES")) : 6 * kFusedPersistWgs;
-    return v > kFusedPersistWgs ? v : kFusedPersistWgs + 1;
-#else
-    return 6 * kFusedPersistWgs;
-#endif
-}
-
-int launch_dcn_fused(const DcnFuseArgs& a, hipStream_t s) {
-    if ((long long)(a.H + 1) * (a.W + 1) >= (1ll << 24)) { set_error("dcn_g8: plane of %d x %d exceeds the sampler's 2^24-element index range", a.H, a.W); return CRFP_E_UNSUPPORTED; }
-    const double px = (double)a.N * a.H * a.W;
-    ProfScope prof("offset_mask_conv+dcnv2_g8_fused", s, px * (32 * 4.0 + 8.0 + (32 + 32) * sizeof(act_t)),
-                   2.0 * px * 32 * 216 * 9 + 2.0 * px * 32 * 32 * 9 + px * 288 * 7);
-#ifdef CRFP_LAB
-    static const int probe_env = getenv("CRFP_DCN_FUSE_PROBE") ? atoi(getenv("CRFP_DCN_FUSE_PROBE")) : 0;
-    DcnFuseArgs b = a;
-    b.probe = probe_env;
-    static bool once = false;
-    if (!once && getenv("CRFP_DCN_FUSE_OCC")) {
-        once = true;
-        int nb = -1;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dcn_fused_kernel<4>, 256, 0);
-        fprintf(stderr, "dcn_fused_kernel: %d workgroups per CU (hip error %d)\n", nb, (int)e);
-    }
-    static const int nw_lab = getenv("CRFP_DCN_FUSE_NW") ? atoi(getenv("CRFP_DCN_FUSE_NW")) : 8;
-    static const int fuse_v_lab = getenv("CRFP_DCN_FUSE_V") ? atoi(getenv("CRFP_DCN_FUSE_V")) : 1;
-    if (nw_lab == 8 && fuse_v_lab == 2) dcn_fused2_kernel<<<dim3((a.W + 31) / 32, (a.H + 7) / 8, a.N), D2_NT, 0, s>>>(b);
-    else if (nw_lab == 8 && ((a.W + 31) / 32) * ((a.H + 7) / 8) * a.N >= fused_persist_min_tiles()) dcn_fused_kernel<8, true><<<dim3(kFusedPersistWgs, 1, 1), 512, 0, s>>>(b);
-    else if (nw_lab == 8) dcn_fused_kernel<8><<<dim3((a.W + 31) / 32, (a.H + 7) / 8, a.N), 512, 0, s>>>(b);
-    else dcn_fused_kernel<4><<<dim3((a.W + 31) / 32, (a.H + 3) / 4, a.N), 256, 0, s>>>(b);
-    CRFP_CHECK_LAUNCH();
-    return 0;
-#endif
-    // 8-wave workgroups: 151.6 vs 165.3 us per launch same-box against <4> (lab library: CRFP_DCN_FUSE_NW=4)
-    // (lab library, CRFP_DCN_FUSE_V=2: the role-specialised 16-wave form above -- bit-identical, 141.2 vs 136.6 us per launch same-box @A:
-    // both forms pay the same ~53 us of per-workgroup fixed cost (116 KB of tile / weight prologue and 258 KB of streamed head
-    // weights per 256 pixels, 15 barriers), and the specialised one overlaps only 17 of the 49 us its sampler role adds)
-    // Round 6: both forms walk the tile list in the XCD-banded order (HBM traffic 170 -> 112-116 MB per launch @A).  Launches of six rounds of
-    // the chip and more (a lock-step batch, the 4K map) take the persistent form (-1 % there, +1.5 % at 3.5 rounds: profiles/r06_dcn_fused_persistent_ab.txt)
-#ifndef CRFP_DF_PERSIST
-#define CRFP_DF_PERSIST 1
-#endif
-    const int tiles = ((a.W + 31) / 32) * ((a.H + 7) / 8) * a.N;
-    if (CRFP_DF_PERSIST && tiles >= fused_persist_min_tiles()) dcn_fused_kernel<8, true><<<dim3(kFusedPersistWgs, 1, 1), 512, 0, s>>>(a);
-    else dcn_fused_kernel<8><<<dim3((a.W + 31) / 32, (a.H + 7) / 8, a.N), 512, 0, s>>>(a);
-    CRFP_CHECK_LAUNCH();
-    return 0;
-}
-#else
-// ---------------------------------------------------------------- the same fusion for bf16 storage
-// The offset feature arrives as bf16 Q4 (8-byte quads): its halo tile is copied into LDS as 16-byte elements of 8 channels
-// (13 KB), the head's bf16 weights stream one WHOLE cout tile per stage (both 16-channel chunks, 18 KB, one barrier pair per
-// 18 MFMAs), one v_mfma_f32_32x32x16_bf16 per (tap, chunk) into ONE accumulator that starts at the bias -- the arithmetic of
-// conv3x3_bf16_kernel in the same order, so the clip is bit-identical to the two-kernel path here too.  A corner pair of the
-// sampler is one dwordx4 (24 registers per sampling pair), so three pairs are in flight instead of two.  LDS 68 352 B, two
-// workgroups per CU.
-constexpr int DF_LW = 34;
-constexpr int DF_WST = 2 * 9 * 64;                   // one cout tile of the bf16 image, 16-byte elements
-#ifndef CRFP_DF_BAND_NP
-#define CRFP_DF_BAND_NP 1
-#endif
-#ifndef CRFP_DF_PS_PROBE   // A/B builds, timing only (results wrong): see the fp32 kernel
-#define CRFP_DF_PS_PROBE 0
-#endif
-constexpr int DF_PS_PROBE = CRFP_DF_PS_PROBE;
-typedef __bf16 df_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void df_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// NW = 4: workgroup of 4 rows x 32 pixels, two per CU, one weight stage (two barriers per stage).  NW = 8: 8 rows, one workgroup
-// per CU, the weight stage double-buffered (one barrier per stage, half the L2 -> LDS weight and DCN-image traffic per pixel).
-// PS (round 6): the persistent form -- see the fp32 kernel.
-template <int NW, bool PS = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(const DcnFuseArgs a) {
-    constexpr int NT = 64 * NW, DF_NEL = (NW + 2) * DF_LW;
-    constexpr int DF_NIN = (8 * DF_NEL + NT - 1) / NT;     // 8-byte quads of the tile per thread
-    constexpr int DF_NWS = (DF_WST + NT - 1) / NT;
-    constexpr bool DB = NW == 8;
-    static_assert(!PS || DB, "the persistent form is the 8-wave form");
-    __shared__ cu32x2 tile[4][DF_NEL][2];   // [8-channel group][halo pixel][quad of the pair]
-    __shared__ f32x4 wst[DB ? 2 : 1][DF_WST];
-    __shared__ f32x4 wl[36 * 64];
-    __shared__ f32x4 bl[DB ? 56 : 1];   // the head's 224 packed biases (NW = 8: LDS has room; NW = 4 keeps them in 4 VGPRs)
-    const int tid0 = threadIdx.x;
-    const int H = a.H, W = a.W;
-    const int tiles_x = (W + 31) >> 5, tiles_y = (H + NW - 1) / NW;
-    int t_cur = 0, t_end = 0, t_step = 1;
-    if (PS) {
-        const int total = tiles_x * tiles_y * a.N, G = (int)gridDim.x;
-#ifdef CRFP_DF_PS_NOBAND   // A/B builds: natural order (tile = workgroup id + k * workgroups)
-        t_cur = (int)blockIdx.x; t_end = total; t_step = G;
-#else
-        const int q = total >> 3, r = total & 7, x = (int)blockIdx.x & 7;
-        const int band0 = x * q + min(x, r);
-        t_cur = band0 + ((int)blockIdx.x >> 3); t_end = band0 + q + (x < r ? 1 : 0); t_step = G >> 3;
-#endif
-        if (t_cur >= t_end) return;
-    }
-    int tx0, ty0, n;
-#define DF_DECODE(T_, TX, TY, NN)                                                                         \
-    {                                                                                                     \
-        const int per_ = tiles_x * tiles_y, n_ = (T_) / per_, r_ = (T_) - n_ * per_, y_ = r_ / tiles_x;   \
-        NN = n_; TY = y_ * NW; TX = (r_ - y_ * tiles_x) * 32;                                             \
-    }
-    if (PS) DF_DECODE(t_cur, tx0, ty0, n)
-#if CRFP_DF_BAND_NP   // the one-tile form walks the tile list in the XCD-banded order too (xcd_band_tile over the launch's linear workgroup id)
-    else if (DB) {
-        const int lin_ = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-        const int tb_ = xcd_band_tile(lin_, (int)(gridDim.x * gridDim.y * gridDim.z));
-        DF_DECODE(tb_, tx0, ty0, n)
-    }
-#endif
-    else { tx0 = blockIdx.x * 32; ty0 = blockIdx.y * NW; n = blockIdx.z; }
-
-    int ltid = tid0;   // the thread id as the tile loop sees it (opaquely re-defined per tile: see the fp32 kernel)
-    cu32x2 rt[DF_NIN];
-#define DF_TLOAD(TX, TY, NN)                                                                              \
-    {                                                                                                     \
-        const cu32x2* __restrict__ fq_ = reinterpret_cast<const cu32x2*>(as_act(a.feat) + (long long)(NN) * a.feat_b); \
-        _Pragma("unroll") for (int t = 0; t < DF_NIN; ++t) {                                              \
-            const int idc = min(ltid + NT * t, 8 * DF_NEL - 1);                                           \
-            const int q = idc / DF_NEL, pix = idc - q * DF_NEL, r = pix / DF_LW, c = pix - r * DF_LW;     \
-            const int gy = (TY) + r - 1, gx = (TX) + c - 1;                                               \
-            rt[t] = fq_[((long long)q * H + min(max(gy, 0), H - 1)) * W + min(max(gx, 0), W - 1)];        \
-        }                                                                                                 \
-    }
-#define DF_TWRITE(TX, TY)                                                                                 \
-    _Pragma("unroll") for (int t = 0; t < DF_NIN; ++t) {                                                  \
-        const int idx = ltid + NT * t;                                                                    \
-        const int q = idx / DF_NEL, pix = idx - q * DF_NEL, r = pix / DF_LW, c = pix - r * DF_LW;         \
-        const int gy = (TY) + r - 1, gx = (TX) + c - 1;                                                   \
-        const bool tv = gy >= 0 && gy < H && gx >= 0 && gx < W;                                           \
-        if (idx < 8 * DF_NEL) tile[q >> 1][pix][q & 1] = tv ? rt[t] : cu32x2{0u, 0u};                     \
-    }
-    DF_TLOAD(tx0, ty0, n)
-    const f32x4* __restrict__ wc = reinterpret_cast<const f32x4*>(a.wconv);
-    f32x4 rws[DF_NWS];
-#define DF_WLOAD(ST)                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < DF_NWS; ++k) rws[k] = wc[(ST) * DF_WST + min(ltid + NT * k, DF_WST - 1)];
-    DF_WLOAD(0)
-    // Round 5 (see the fp32 kernel): the DCN weight image and weight stage 1 are requested BEHIND the first barrier and written to LDS in the
-    // middle of cout tile 0 (DF_LATE_FILL), so that only the halo tile and stage 0 are ingested in front of the first MFMA.
-    // (PS: the DCN weight image is fetched once per workgroup, in front of the tile loop.)
-#ifndef CRFP_DF_LATE_PROLOGUE
-#define CRFP_DF_LATE_PROLOGUE 1
-#endif
-    constexpr bool LATE = DB && CRFP_DF_LATE_PROLOGUE;
-    static_assert(!PS || LATE, "the persistent form builds on the late prologue");
-    constexpr bool LATE_WL = LATE && !PS;
-    constexpr int DF_NWL = (36 * 64 + NT - 1) / NT;
-    f32x4 rwl[LATE_WL ? DF_NWL : 1];
-    if (!LATE_WL)
-        for (int i = tid0; i < 36 * 64; i += NT) wl[i] = reinterpret_cast<const f32x4*>(a.wdcn)[i];
-    DF_TWRITE(tx0, ty0)
-
-    const long long plane = (long long)H * W * 4;
-    const int PW = W + 1, pitch = PW * QB, plane_b = (H + 1) * pitch;
-    const int guard = pitch + QB;
-    const float fH = (float)H, fW = (float)W;
-    float bv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) bv[k] = DB ? 0.0f : a.bconv[min(64 * k + (tid0 & 63), 223)];
-    if (DB && tid0 < 56) bl[tid0] = reinterpret_cast<const f32x4*>(a.bconv)[tid0];
-#define DF_WRITE(B)                                                                                       \
-    _Pragma("unroll") for (int k = 0; k < DF_NWS; ++k) {                                                  \
-        const int idx = ltid + NT * k;                                                                    \
-        if (idx < DF_WST) wst[B][idx] = rws[k];                                                           \
-    }
-    if (DB) { DF_WRITE(0) if (!LATE) { DF_WLOAD(1) } }   // stage 0 in LDS (LATE: stage 1 is requested behind the first barrier)
-
-    for (;;) {   // one tile per trip (not PS: one trip)
-    if (PS) asm volatile("" : "+v"(ltid));
-    const int tid = ltid, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int px = tx0 + j, py = ty0 + wave;
-    const bool valid = px < W && py < H;
-    const int cx = min(px, W - 1), cy = min(py, H - 1);
-    const float2 fl = *reinterpret_cast<const float2*>(a.flow + (long long)n * a.flow_b + ((long long)cy * W + cx) * 2);
-    const float cfy = 10.0f + fl.y, cfx = 10.0f + fl.x;
-    int ntx0 = 0, nty0 = 0, nn = 0;   // (PS) the workgroup's next tile
-    const bool has_next = PS && t_cur + t_step < t_end;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)const_cast<act_t*>(as_act(a.x) + (long long)n * a.xb) - guard, 0, 8 * plane_b + guard, 0x00020000);
-    const float fy0 = (float)(cy - 1), fx0 = (float)(cx - 1);
-    const int hbase = 4 * h * plane_b + guard;
-
-    f32x16 acc, acl, ca;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc[e] = 0.0f; acl[e] = 0.0f; }
-    float ov[108];
-    DcnPair Q0, Q1, Q2;
-    const f32x4* wcur = &wst[0][0];
-    df_bf16x8 pw0, pb0;   // operands of the next MFMA (round 5)
-
-    // single buffer: barrier (everyone done with the previous stage), registers -> LDS, barrier, next stage's loads.
-    // double buffer: one barrier (stage T complete in buffer T & 1 and everyone done with stage T - 1), then the registers
-    // (stage T + 1) go to the other buffer and stage T + 2's loads leave
-#define DF_LATE_FILL                                                                                      \
-    if (LATE) {                                                                                           \
-        DF_WRITE(1)                                                                                       \
-        if (LATE_WL) {                                                                                    \
-            _Pragma("unroll") for (int k = 0; k < DF_NWL; ++k)                                            \
-                if (tid + NT * k < 36 * 64) wl[tid + NT * k] = rwl[k];                                    \
-        }                                                                                                 \
-        DF_WLOAD(2)                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-    }
-#define DF_BEGIN(T)                                                                                       \
-    {                                                                                                     \
-        df_lds_barrier();                                                                                 \
-        if (DB && LATE && (T) == 0) {                                                                     \
-            DF_WLOAD(1)                                                                                   \
-            if (LATE_WL) {                                                                                \
-                _Pragma("unroll") for (int k = 0; k < DF_NWL; ++k)                                        \
-                    rwl[k] = reinterpret_cast<const f32x4*>(a.wdcn)[min(tid + NT * k, 36 * 64 - 1)];      \
-            }                                                                                             \
-        } else if (DB) {                                                                                  \
-            if ((T) + 1 < 7) { DF_WRITE(((T) + 1) & 1) }                                                  \
-            if ((T) + 2 < 7) { DF_WLOAD((T) + 2) }                                                        \
-        } else {                                                                                          \
-            DF_WRITE(0)                                                                                   \
-            df_lds_barrier();                                                                             \
-            if ((T) + 1 < 7) { DF_WLOAD((T) + 1) }                                                        \
-        }                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        wcur = &wst[DB ? ((T) & 1) : 0][0];                                                               \
-    }
-    // MFMAs MA .. MB-1 of the cout tile's 18 (chunk-major, then taps: the K order of conv3x3_bf16_kernel)
-    // Round 5: MFMA m + 1's two operands are read from LDS before MFMA m issues (one register set ahead, +8 VGPRs; see the fp32 kernel).  The
-    // first MFMA of a cout tile (behind the stage barrier) loads its own.  Same operations, same order: bit-identical.
-#ifndef CRFP_DF_NO_PREFETCH
-#define DF_LDOPS(W0, B0, M_)                                                                              \
-    {                                                                                                     \
-        const int ch_ = (M_) / 9, tap_ = (M_) - 9 * ch_, ky_ = tap_ / 3, kx_ = tap_ - 3 * ky_;            \
-        const int pix_ = (wave + ky_) * DF_LW + j + kx_;                                                  \
-        W0 = __builtin_bit_cast(df_bf16x8, wcur[(M_) * 64 + lane]);                                       \
-        B0 = __builtin_bit_cast(df_bf16x8, *reinterpret_cast<const f32x4*>(&tile[2 * ch_ + h][pix_][0])); \
-    }
-#define DF_M(MA, MB)                                                                                      \
-    _Pragma("unroll") for (int m = (MA); m < (MB); ++m) {                                                 \
-        df_bf16x8 w0, b0;                                                                                 \
-        if (m != 0) { w0 = pw0; b0 = pb0; }                                                               \
-        else DF_LDOPS(w0, b0, m)                                                                          \
-        if (m + 1 < 18) DF_LDOPS(pw0, pb0, m + 1)                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b0, ca, 0, 0, 0);                                \
-    }
-#else
-#define DF_M(MA, MB)                                                                                      \
-    _Pragma("unroll") for (int m = (MA); m < (MB); ++m) {                                                 \
-        const int ch = m / 9, tap = m - 9 * ch, ky = tap / 3, kx = tap - 3 * ky;                          \
-        const df_bf16x8 w0 = __builtin_bit_cast(df_bf16x8, wcur[m * 64 + lane]);                           \
-        const int pix = (wave + ky) * DF_LW + j + kx;                                                     \
-        const df_bf16x8 b0 = __builtin_bit_cast(df_bf16x8, *reinterpret_cast<const f32x4*>(&tile[2 * ch + h][pix][0])); \
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b0, ca, 0, 0, 0);                                \
-    }
-#endif
-#define DF_BIAS(T)                                                                                        \
-    if (DB) {                                                                                             \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                   \
-            const f32x4 bq = bl[(T) * 8 + 2 * q + h];                                                     \
-            ca[4 * q] = bq.x; ca[4 * q + 1] = bq.y; ca[4 * q + 2] = bq.z; ca[4 * q + 3] = bq.w;           \
-        }                                                                                                 \
-    } else {                                                                                              \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                  \
-            const int r0 = 32 * (T) + 8 * (e >> 2) + (e & 3), r1 = r0 + 4;                                \
-            const float s0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv[r0 >> 6]), r0 & 63)); \
-            const float s1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv[r1 >> 6]), r1 & 63)); \
-            ca[e] = h ? s1 : s0;                                                                          \
-        }                                                                                                 \
-    }
-#define DF_RAW(T)                                                                                         \
-    {                                                                                                     \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                  \
-            const int sl = 16 * (T) + e;                                                                  \
-            if (sl < 108) ov[sl] = ca[e];                                                                 \
-        }                                                                                                 \
-    }
-#define DF_TRANS(T)                                                                                       \
-    {                                                                                                     \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) {                                                  \
-            const int sl = 16 * (T) + e;                                                                  \
-            if (sl < 108)                                                                                 \
-                ov[sl] = sl % 3 == 0 ? tanh10_plus(ov[sl], cfy) : (sl % 3 == 1 ? tanh10_plus(ov[sl], cfx) : fast_sigmoid(ov[sl])); \
-        }                                                                                                 \
-    }
-#define DF_SB __builtin_amdgcn_sched_barrier(0);
-#define DF_I(U, P)                                                                                        \
-    {                                                                                                     \
-        dcn_issue_one(P, 0, rx, ov[6 * (U)], ov[6 * (U) + 1], ov[6 * (U) + 2], 2 * (U), fy0, fx0, fH, fW, PW, pitch, plane_b, hbase); \
-        dcn_issue_one(P, 1, rx, ov[6 * (U) + 3], ov[6 * (U) + 4], ov[6 * (U) + 5], 2 * (U) + 1, fy0, fx0, fH, fW, PW, pitch, plane_b, hbase); \
-    }
-#define DF_C(U, P) { dcn_consume_pair(P, acc, acl, wl, U, lane); }
-    // (PS) the hooks of the schedule's tail: see the fp32 kernel
-#define DF_TAIL_REQUEST                                                                                   \
-    if (PS) {                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        DF_DECODE(has_next ? t_cur + t_step : t_cur, ntx0, nty0, nn)                                      \
-        if (!(DF_PS_PROBE & 1)) { DF_TLOAD(ntx0, nty0, nn) DF_WLOAD(0) }                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-    }
-#define DF_TAIL_COMMIT                                                                                    \
-    if (PS && has_next) {                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-        df_lds_barrier();                                                                                 \
-        if (!(DF_PS_PROBE & 2)) { DF_TWRITE(ntx0, nty0) DF_WRITE(0) }                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                \
-    }
-    // cout tile T completes the sampling pairs up to (16 T + 10) / 6: 1, 4, 7, 9, 12, 15, 17; they are sampled inside tile T + 1.
-    // Pair u lives in Q[u % 3]; I(u) follows C(u - 3).
-    DF_BEGIN(0) DF_BIAS(0) DF_M(0, 9) DF_LATE_FILL DF_M(9, 18) DF_RAW(0)   // (the bias table in LDS is complete behind the first barrier)
-    DF_BIAS(1)
-    DF_BEGIN(1) DF_M(0, 6) DF_TRANS(0) DF_SB DF_M(6, 12) DF_I(0, Q0) DF_SB DF_M(12, 18) DF_I(1, Q1) DF_SB DF_RAW(1)
-    DF_BIAS(2)
-    DF_BEGIN(2) DF_M(0, 4) DF_TRANS(1) DF_SB DF_M(4, 8) DF_I(2, Q2) DF_SB DF_M(8, 12) DF_SB DF_C(0, Q0) DF_SB DF_M(12, 15) DF_I(3, Q0) DF_SB
-                DF_M(15, 18) DF_SB DF_C(1, Q1) DF_SB DF_I(4, Q1) DF_SB DF_RAW(2)
-    DF_BIAS(3)
-    DF_BEGIN(3) DF_M(0, 3) DF_TRANS(2) DF_SB DF_M(3, 6) DF_SB DF_C(2, Q2) DF_SB DF_M(6, 9) DF_I(5, Q2) DF_SB DF_M(9, 12) DF_SB DF_C(3, Q0) DF_SB
-                DF_M(12, 15) DF_I(6, Q0) DF_SB DF_M(15, 18) DF_SB DF_C(4, Q1) DF_SB DF_I(7, Q1) DF_SB DF_RAW(3)
-    DF_BIAS(4)
-    DF_BEGIN(4) DF_M(0, 4) DF_TRANS(3) DF_SB DF_M(4, 8) DF_SB DF_C(5, Q2) DF_SB DF_M(8, 12) DF_I(8, Q2) DF_SB DF_M(12, 15) DF_SB DF_C(6, Q0) DF_SB
-                DF_M(15, 18) DF_I(9, Q0) DF_SB DF_C(7, Q1) DF_SB DF_RAW(4)
-    DF_BIAS(5)
-    DF_BEGIN(5) DF_M(0, 4) DF_TRANS(4) DF_SB DF_M(4, 8) DF_I(10, Q1) DF_SB DF_M(8, 12) DF_SB DF_C(8, Q2) DF_SB DF_M(12, 15) DF_I(11, Q2) DF_SB
-                DF_M(15, 18) DF_SB DF_C(9, Q0) DF_SB DF_I(12, Q0) DF_SB DF_RAW(5)
-    DF_BIAS(6)
-    DF_BEGIN(6) DF_M(0, 3) DF_TRANS(5) DF_SB DF_M(3, 6) DF_SB DF_C(10, Q1) DF_SB DF_M(6, 9) DF_I(13, Q1) DF_SB DF_M(9, 12) DF_SB DF_C(11, Q2) DF_SB
-                DF_M(12, 15) DF_I(14, Q2) DF_SB DF_M(15, 18) DF_SB DF_C(12, Q0) DF_SB DF_I(15, Q0) DF_SB DF_RAW(6)
-    DF_TRANS(6) DF_SB DF_C(13, Q1) DF_SB DF_I(16, Q1) DF_SB DF_C(14, Q2) DF_SB DF_I(17, Q2) DF_SB DF_TAIL_REQUEST DF_C(15, Q0) DF_SB DF_C(16, Q1) DF_SB DF_C(17, Q2) DF_TAIL_COMMIT
-#undef DF_C
-#undef DF_I
-#undef DF_SB
-#undef DF_TRANS
-#undef DF_RAW
-#undef DF_BIAS
-#undef DF_M
-#undef DF_LATE_FILL
-#undef DF_BEGIN
-#undef DF_WRITE
-    if (valid) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] += acl[e] * (1.0f / 2048.0f);
-        act_t* o = as_act(a.out) + (long long)n * a.ob + ((long long)py * W + px) * 4;
-        float vmax = 0.0f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int cq = 2 * g + h;
-            const float4 bb = *reinterpret_cast<const float4*>(a.bdcn + 4 * cq);
-            const float4 v = make_float4(acc[4 * g] + bb.x, acc[4 * g + 1] + bb.y, acc[4 * g + 2] + bb.z, acc[4 * g + 3] + bb.w);
-            vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-            stq(o + cq * plane, cf32x4{v.x, v.y, v.z, v.w});
-        }
-        if (a.ovf && !(vmax < 65504.0f)) atomicOr(ovf_word(a.ovf, a.ovf_div, 0, n), 1u);
-    }
-    if (!has_next) break;
-    t_cur += t_step;
-    tx0 = ntx0; ty0 = nty0; n = nn;
-    }   // tiles
-#undef DF_TAIL_REQUEST
-#undef DF_TAIL_COMMIT
-#undef DF_TWRITE
-#undef DF_WLOAD
-#undef DF_TLOAD
-#undef DF_DECODE
-}
-
-bool dcn_fused_enabled() {
-    static const bool on = !(getenv("CRFP_DCN_FUSED") && atoi(getenv("CRFP_DCN_FUSED")) == 0);
-    return on;
-}
-
-constexpr int kFusedPersistWgs = 256;   // workgroups of the persistent form = CUs of an MI355X (one 8-wave workgroup per CU)
-static int fused_persist_min_tiles() {     // see the fp32 launcher
-#ifdef CRFP_LAB
-    static const int v = getenv("CRFP_DF_PS_MIN_TILES") ? atoi(getenv("CRFP_DF_PS_MIN_TILES")) : 6 * kFusedPersistWgs;
-    return v > kFusedPersistWgs ? v : kFusedPersistWgs + 1;
-#else
-    return 6 * kFusedPersistWgs;
-#endif
-}
-
-int launch_dcn_fused(const DcnFuseArgs& a, hipStream_t s) {
-    if ((long long)(a.H + 1) * (a.W + 1) >= (1ll << 24)) { set_error("dcn_g8: plane of %d x %d exceeds the sampler's 2^24-element index range", a.H, a.W); return CRFP_E_UNSUPPORTED; }
-    const double px = (double)a.N * a.H * a.W;
-    ProfScope prof("offset_mask_conv+dcnv2_g8_fused", s, px * (8.0 + (32 + 32 + 32) * sizeof(act_t)),
-                   2.0 * px * 32 * 216 * 9 + 2.0 * px * 32 * 32 * 9 + px * 288 * 7);
-    // 8-wave workgroups: 91.9 vs 97.0 us per launch same-box against <4> (one clip); -DCRFP_LAB builds: CRFP_DCN_FUSE_NW=4 = A/B knob for
-    // multi-round launches
-#ifdef CRFP_LAB
-    static const int nw4 = getenv("CRFP_DCN_FUSE_NW") && atoi(getenv("CRFP_DCN_FUSE_NW")) == 4;
-    if (nw4) dcn_fused_kernel<4><<<dim3((a.W + 31) / 32, (a.H + 3) / 4, a.N), 256, 0, s>>>(a);
-    else
-#endif
-    {
-        // Round 6: see the fp32 launcher
-#ifndef CRFP_DF_PERSIST
-#define CRFP_DF_PERSIST 1
-#endif
-        const int tiles = ((a.W + 31) / 32) * ((a.H + 7) / 8) * a.N;
-        if (CRFP_DF_PERSIST && tiles >= fused_persist_min_tiles()) dcn_fused_kernel<8, true><<<dim3(kFusedPersistWgs, 1, 1), 512, 0, s>>>(a);
-        else dcn_fused_kernel<8><<<dim3((a.W + 31) / 32, (a.H + 7) / 8, a.N), 512, 0, s>>>(a);
-    }
-    CRFP_CHECK_LAUNCH();
-    return 0;
-}
-#endif
+// the 32 -> 216 offset / mask head + dcn_g8 in one kernel (dcn_fused_kernel, launch_dcn_fused, dcn_fused_enabled)
+#include "dcn_fused.inc"
 
 // wpk[((p36*2 + half)*32 + row)*4 + i] = W[row][4*(4*half + p36/9) + i][p36 % 9]
 #ifndef CRFP_ACT_BF16

@@ -1,4 +1,4 @@
-"""GPU (-m gpu), round 6: the persistent form of the fused offset-head + DCNv2 kernel (gather.hip dcn_fused_kernel<8, true>: launches with more
+"""GPU (-m gpu), round 6: the persistent form of the fused offset-head + DCNv2 kernel (dcn_fused.inc dcn_fused_kernel<8, true>: launches with more
 tiles than CUs) and the other round-6 kernel changes, bit for bit against the paths they replace."""
 import pytest
 

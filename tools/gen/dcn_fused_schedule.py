@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates the instruction-group schedule of dcn_fused_kernel (crfp_amd/csrc/gather.hip, `#include "dcn_fused_schedule.inc"`).
+"""Generates the instruction-group schedule of dcn_fused_kernel (crfp_amd/csrc/dcn_fused.inc, `#include "dcn_fused_schedule.inc"`).
 
 The kernel computes the 32 -> 216 offset / mask head one cout tile T (0..6) and 16-channel chunk CH (0, 1) at a time: 9 taps of
 3 MFMAs per (T, CH) stage.  Everything else -- activating the raw sums of the previous tile (TR), the coordinates + gathers of a

@@ -2,6 +2,7 @@
 """Kernel resource table of one translation unit before / after a change that must not move its kernels.
 Inputs per side: the host object hipcc wrote and the stderr of the same compile with -Rpass-analysis=kernel-resource-usage.
 usage: python tools/kres_table.py LABEL old.o old.remarks new.o new.remarks [LABEL ...]   (five arguments per table)
+Each of the four files may be a comma-separated list (a.o,b.o and a.remarks,b.remarks) when the kernels moved to another translation unit.
 Columns: VGPRs / AGPRs / LDS bytes / scratch bytes per lane / occupancy (waves per SIMD) as old -> new where they differ, the code
 size in bytes, and whether the kernel's instruction bytes are identical."""
 import hashlib, os, re, subprocess, sys, tempfile
@@ -50,10 +51,18 @@ def demangle(n):
     return subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().split("(")[0].replace("crfp::", "").replace("crfp_bf16::", "")
 
 
+def merged(read, paths):
+    """one table from a comma-separated list of files: the kernels of a translation unit that was split stay comparable"""
+    out = {}
+    for p in paths.split(","):
+        out.update(read(p))
+    return out
+
+
 args = sys.argv[1:]
 for i in range(0, len(args), 5):
     label, o0, r0, o1, r1 = args[i:i + 5]
-    R0, R1, C0, C1 = remarks(r0), remarks(r1), code(o0), code(o1)
+    R0, R1, C0, C1 = merged(remarks, r0), merged(remarks, r1), merged(code, o0), merged(code, o1)
     print(f"## {label}\n")
     print("| kernel | " + " | ".join(k for k, _ in KEYS) + " | code bytes | same ISA | same resources |\n|---|" + "---|" * (len(KEYS) + 3))
     for n in sorted(set(R0) | set(R1), key=demangle):
