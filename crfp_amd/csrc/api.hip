@@ -432,6 +432,27 @@ int crfp_gaze_prep_f32(const float* gt, const int32_t* rows, float* fv, uint8_t*
     return launch_gaze_prep(gt, rows, fv, mk, regions, fg, n, c, h, w, dilate, (hipStream_t)stream);
 }
 
+int crfp_frame_ingest_u8(const uint8_t* lr_u8, const uint8_t* crop_u8, const int32_t* rects, float* lr, float* fv, uint8_t* mk, int n, int h, int w,
+                         int fh, int fw, int H, int W, int flags, void* stream) {
+    if ((lr_u8 == nullptr) != (lr == nullptr)) { set_error("frame_ingest: lr_u8 and lr go together (both given, or both null for the fovea alone)"); return CRFP_E_BADARG; }
+    const int fovea = (crop_u8 != nullptr) + (rects != nullptr) + (fv != nullptr) + (mk != nullptr);
+    if (fovea != 0 && fovea != 4) { set_error("frame_ingest: crop_u8, rects, fv and mk go together (all given, or all null for the LR frame alone)"); return CRFP_E_BADARG; }
+    if (!lr && !fovea) { set_error("frame_ingest: null pointer (nothing to do)"); return CRFP_E_BADARG; }
+    if (n < 1 || h < 1 || w < 1 || fh < 1 || fw < 1 || H < 1 || W < 1) { set_error("frame_ingest: bad argument (need n, h, w, fh, fw, H, W >= 1)"); return CRFP_E_BADARG; }
+    if (flags & ~CRFP_IO_BGR) { set_error("frame_ingest: unknown flags 0x%x (the BGR flag is the only one)", flags); return CRFP_E_BADARG; }
+    return launch_frame_ingest(lr_u8, crop_u8, rects, lr, fv, mk, n, h, w, fh, fw, H, W, flags & CRFP_IO_BGR, (hipStream_t)stream);
+}
+
+int crfp_frame_export_u8(const float* sr, const float* chroma, uint8_t* out_u8, int n, int c, int H, int W, int flags, void* stream) {
+    if (!sr || !out_u8) { set_error("frame_export: null pointer (sr and out_u8 are required)"); return CRFP_E_BADARG; }
+    if (n < 1 || H < 1 || W < 1) { set_error("frame_export: bad argument (need n, H, W >= 1)"); return CRFP_E_BADARG; }
+    if (c != 1 && c != 3) { set_error("frame_export: c must be 1 or 3, got %d", c); return CRFP_E_BADARG; }
+    if (c == 3 && chroma) { set_error("frame_export: chroma goes with c = 1 (a luma frame); c = 3 takes none"); return CRFP_E_BADARG; }
+    if (c == 1 && !chroma) { set_error("frame_export: c = 1 needs the chroma frame"); return CRFP_E_BADARG; }
+    if (flags & ~CRFP_IO_BGR) { set_error("frame_export: unknown flags 0x%x (the BGR flag is the only one)", flags); return CRFP_E_BADARG; }
+    return launch_frame_export(sr, chroma, out_u8, n, c, H, W, flags & CRFP_IO_BGR, (hipStream_t)stream);
+}
+
 int crfp_psnr_partial_f32(const float* a, const float* b, double* acc, int n, int c, int h, int w, void* stream) {
     if (!a || !b || !acc || n < 1 || c < 1 || h < 1 || w < 1) { set_error("psnr_partial: bad argument"); return CRFP_E_BADARG; }
     return launch_psnr_partial(a, b, acc, n, c, h, w, (hipStream_t)stream);

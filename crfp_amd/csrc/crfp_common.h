@@ -497,5 +497,9 @@ int launch_frame_metrics(const float* sr, const float* hr, const uint8_t* masks,
 // gaze.hip: the gaze rig's masks, regions stack and fovea frame of n frames from their rectangle rows (CRFP_GAZE_ROW_INTS ints each)
 int launch_gaze_prep(const float* gt, const int* rows, float* fv, uint8_t* mk, uint8_t* regions, uint8_t* fg, int N, int C, int H, int W,
                      int dilate, hipStream_t s);
+// frameio.hip: 8-bit frames <-> the engines' fp32 API tensors (bgr: the 8-bit side is B,G,R)
+int launch_frame_ingest(const uint8_t* lr_u8, const uint8_t* crop_u8, const int* rects, float* lr, float* fv, uint8_t* mk, int N, int h, int w,
+                        int fh, int fw, int H, int W, int bgr, hipStream_t s);
+int launch_frame_export(const float* sr, const float* chroma, uint8_t* out_u8, int N, int C, int H, int W, int bgr, hipStream_t s);
 
 }  // namespace CRFP_NS

@@ -36,6 +36,8 @@
  *   crfp_window_scores_f32    test_video.py:23-63 foveated_metric (per-window PSNR / SSIM maps)
  *   crfp_frame_metrics_f32    trainer.py:348-369 / test_video.py:360-370 (per-frame, per-region PSNR / SSIM / PSNR-Y / SSIM-Y)
  *   crfp_gaze_prep_f32        test_video.py:335-358,371-375 (fv / mk / mk_fv / mk_out / mk_past / fg of one streamed frame)
+ *   crfp_frame_ingest_u8      dataset/reds.py:196-203,306,409 (8-bit LR frame, fovea crop and rectangle -> lr / fv / mk)
+ *   crfp_frame_export_u8      test_video.py:100-127,396-410 (y_only chroma merge, clip, round, uint8, HWC, RGB -> BGR)
  *   crfp_spynet_forward       model/CRFP.py:554-741 SPyNet.forward (+ SPyNetBasicModule, `conv` :145-152)
  *   crfp_convkxk_f32          model/CRFP.py:145-152 `conv`: ReLU -> nn.Conv2d(k, stride 1, pad k/2)
  *   crfp_upsample_bilinear_ac_f32  F.interpolate(..., bilinear, align_corners=True) (model/CRFP.py:647-651)
@@ -219,6 +221,29 @@ int crfp_frame_metrics_f32(const float* sr, const float* hr, const uint8_t* mask
 #define CRFP_GAZE_COUNTS 2
 int crfp_gaze_prep_f32(const float* gt, const int32_t* rows, float* fv, uint8_t* mk, uint8_t* regions, uint8_t* fg, int n, int c, int h, int w,
                        int dilate, void* stream);
+
+/* 8-bit frame I/O around the fp32 API tensors, two stream kernels (dataset/reds.py:196-203,306,409; test_video.py:100-127,396-410): a host
+ * uploads an 8-bit LR frame, a fovea crop and one rectangle, and downloads an 8-bit frame.
+ * Ingest.  lr_u8 [n,h,w,3] bytes -> lr [n,3,h,w] fp32, lr[c,y,x] = (float)lr_u8[y,x,c'] / 255.0f with IEEE division, c' = c (2 - c under
+ * CRFP_IO_BGR).  crop_u8 [n,fh,fw,3] bytes and rects (DEVICE memory, n rows of CRFP_IO_RECT_INTS int32: y, x, flags, 0; (y, x) = the frame
+ * position of the crop's pixel (0, 0)) -> fv [n,3,H,W] fp32, mk [n,1,H,W] bytes: with R = [y, y + fh) x [x, x + fw) intersected with the frame
+ * (64-bit arithmetic; empty when bit CRFP_IO_HAS_FOVEA of the row's flags is clear), fv = crop / 255.0f of the matching crop pixel and mk = 1
+ * inside R, fv = +0.0f and mk = 0 outside.  A crop may hang over any edge or lie wholly outside.  lr_u8 and lr: both given or both NULL (fovea
+ * only); crop_u8, rects, fv, mk: all given or all NULL (LR only).  At most two launches.
+ * Export.  sr [n,c,H,W] fp32 -> out_u8 [n,H,W,3] bytes, per channel value (uint8)rintf(fminf(fmaxf(v * 255.0f, 0.0f), 255.0f)): round half to
+ * even, NaN gives 0.  c = 3: chroma must be NULL.  c = 1 (a y_only model): chroma [n,3,H,W] RGB fp32 is required and the pixel is, in fp32 with
+ * one rounding per operation, u = ((-0.147f r) - (0.289f g)) + (0.436f b), v = ((0.615f r) - (0.515f g)) - (0.100f b) of the chroma pixel,
+ * R = y + (1.14f v), G = (y + (-0.396f u)) - (0.581f v), B = y + (2.029f u) with y = sr.  CRFP_IO_BGR swaps the byte order of a pixel.
+ * Both: asynchronous on `stream`, no workspace, no atomics, nothing to initialise, every output byte written exactly once; a 4-pixel form when
+ * the plane sizes (ingest's fv / mk: W) are multiples of 4, the fp32 pointers 16-byte and the byte pointers (mk, lr_u8, out_u8) 4-byte aligned,
+ * an element-wise form otherwise.  Errors (CRFP_E_BADARG, before any HIP call): a half-given group, nothing given, a size < 1, c outside {1, 3},
+ * chroma with c = 3 or none with c = 1, unknown flag bits; n > 65535 is CRFP_E_UNSUPPORTED. */
+#define CRFP_IO_BGR 1 /* the 8-bit side is B,G,R per pixel (cv2 order) instead of R,G,B */
+#define CRFP_IO_RECT_INTS 4
+#define CRFP_IO_HAS_FOVEA 1
+int crfp_frame_ingest_u8(const uint8_t* lr_u8, const uint8_t* crop_u8, const int32_t* rects, float* lr, float* fv, uint8_t* mk, int n, int h, int w,
+                         int fh, int fw, int H, int W, int flags, void* stream);
+int crfp_frame_export_u8(const float* sr, const float* chroma, uint8_t* out_u8, int n, int c, int H, int W, int flags, void* stream);
 
 /* ---- CRFP_DSV engine (mid_channels=32, hr_dcn=True, offset_prop=True; y_only selectable).
  * Parameters arrive as CRFP_DSV_NUM_PARAMS device pointers in the order of the reference's

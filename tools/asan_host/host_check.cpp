@@ -204,6 +204,62 @@ int main() {
                     }
         EXPECT(crfp_stub_launches() == l0 + accepted);
     }
+    // 8-bit frame I/O: every refusal before the first launch; an accepted ingest is one launch per half it was given, an export is one
+    {
+        uint8_t* const k16 = reinterpret_cast<uint8_t*>(16);
+        const uint8_t* const c16 = reinterpret_cast<const uint8_t*>(16);
+        const int32_t* const r16 = reinterpret_cast<const int32_t*>(16);
+        const long l0 = crfp_stub_launches();
+        EXPECT(crfp_frame_ingest_u8(nullptr, c16, r16, p16, p16, k16, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);   // lr without lr_u8
+        EXPECT(std::strstr(crfp_last_error_string(), "lr_u8 and lr") != nullptr);
+        EXPECT(crfp_frame_ingest_u8(c16, c16, r16, nullptr, p16, k16, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_ingest_u8(c16, nullptr, r16, p16, p16, k16, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);   // a part of the fovea group
+        EXPECT(std::strstr(crfp_last_error_string(), "go together") != nullptr);
+        EXPECT(crfp_frame_ingest_u8(c16, c16, nullptr, p16, p16, k16, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, nullptr, k16, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, p16, nullptr, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_ingest_u8(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "nothing to do") != nullptr);
+        for (int pos = 0; pos < 7; ++pos) {
+            int a[7] = {2, 24, 32, 8, 8, 192, 256};
+            a[pos] = pos % 2 ? 0 : -1;
+            EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, p16, k16, a[0], a[1], a[2], a[3], a[4], a[5], a[6], 0, nullptr) == CRFP_E_BADARG);
+            EXPECT(std::strstr(crfp_last_error_string(), "bad argument") != nullptr);
+        }
+        EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, p16, k16, 2, 24, 32, 8, 8, 192, 256, 2, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "unknown flags") != nullptr);
+        EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, p16, k16, 70000, 24, 32, 8, 8, 192, 256, 0, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_frame_ingest_u8(nullptr, c16, r16, nullptr, p16, k16, 1, 1, 1, 8, 8, 2147483647, 2147483647, 0, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, p16, k16, 1, 2147483647, 2147483647, 8, 8, 192, 256, 0, nullptr) == CRFP_E_UNSUPPORTED);   // before its fovea half
+        EXPECT(crfp_frame_export_u8(nullptr, nullptr, k16, 2, 3, 24, 32, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, nullptr, 2, 3, 24, 32, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 0, 3, 24, 32, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 2, 3, -1, 32, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 2, 3, 24, 0, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 2, 2, 24, 32, 0, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "c must be 1 or 3") != nullptr);
+        EXPECT(crfp_frame_export_u8(p16, p16, k16, 2, 3, 24, 32, 0, nullptr) == CRFP_E_BADARG);       // chroma with c = 3
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 2, 1, 24, 32, 0, nullptr) == CRFP_E_BADARG);   // none with c = 1
+        EXPECT(std::strstr(crfp_last_error_string(), "chroma") != nullptr);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 2, 3, 24, 32, 4, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 70000, 3, 24, 32, 0, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_frame_export_u8(p16, nullptr, k16, 1, 3, 2147483647, 2147483647, 0, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_stub_launches() == l0);
+        long launches = 0;
+        for (const auto& g : {std::initializer_list<int>{1, 1}, {7, 9}, {16, 64}, {180, 320}})
+            for (int flags : {0, CRFP_IO_BGR})
+                for (uint8_t* m : {k16, reinterpret_cast<uint8_t*>(17)}) {   // aligned and not: both kernel forms
+                    const int h = g.begin()[0], w = g.begin()[1];
+                    EXPECT(crfp_frame_ingest_u8(c16, c16, r16, p16, p16, m, 2, h, w, 96, 96, 8 * h, 8 * w, flags, nullptr) == 0);
+                    EXPECT(crfp_frame_ingest_u8(c16, nullptr, nullptr, p16, nullptr, nullptr, 2, h, w, 96, 96, 8 * h, 8 * w, flags, nullptr) == 0);
+                    EXPECT(crfp_frame_ingest_u8(nullptr, c16, r16, nullptr, p16, m, 2, h, w, 96, 96, 8 * h, 8 * w, flags, nullptr) == 0);
+                    EXPECT(crfp_frame_export_u8(p16, nullptr, m, 2, 3, 8 * h, 8 * w, flags, nullptr) == 0);
+                    EXPECT(crfp_frame_export_u8(p16, p16, m, 2, 1, 8 * h, 8 * w, flags, nullptr) == 0);
+                    launches += 2 + 1 + 1 + 1 + 1;
+                }
+        EXPECT(crfp_stub_launches() == l0 + launches);
+    }
     // the conv probe (test hook): sizing, the launcher's kernel-selection rule, every refusal before the first launch, whole calls on the stub
     {
         crfp_probe_conv q;
