@@ -31,6 +31,26 @@ class ProbeConv(C.Structure):
                 ("strict", C.c_int), ("dst_f32", C.c_int), ("post_scale", C.c_float)]
 
 
+class NarrowStencil(C.Structure):
+    """crfp_narrow_stencil of include/crfp_hip.h: one stencil of a crfp_narrow_probe call (test hook)."""
+    _fields_ = [("src", C.c_void_p * 3), ("weight", C.c_void_p), ("bias", C.c_void_p), ("weight2", C.c_void_p), ("bias2", C.c_void_p),
+                ("residual", C.c_void_p), ("flow", C.c_void_p), ("base_lr", C.c_void_p), ("mask", C.c_void_p),
+                ("dst", C.c_void_p), ("dst_raw", C.c_void_p), ("dst2", C.c_void_p), ("dst2_raw", C.c_void_p),
+                ("nsrc", C.c_int), ("src_kind", C.c_int * 3), ("src_nch", C.c_int * 3), ("src_pad", C.c_int), ("dst_pad", C.c_int),
+                ("cout", C.c_int), ("cout_split", C.c_int), ("act", C.c_int), ("epi", C.c_int), ("y_only", C.c_int), ("gate_h", C.c_int),
+                ("dst2_on", C.c_int), ("post_scale", C.c_float)]
+
+
+class NarrowReport(C.Structure):
+    """crfp_narrow_report: the kernel a narrow launch took, its template arguments, its tiles and workgroups per batch item."""
+    _fields_ = [(k, C.c_int) for k in ("kernel", "kq", "epi", "gate", "st2", "kqg", "res", "tiles", "workgroups")]
+
+
+NARROW_KERNELS = ("none", "narrow", "seq", "pair", "chain")   # CRFP_NARROWK_*
+NARROW_MODES = {"single": 0, "pair": 1, "chain": 2}
+NARROW_EPI = {"plain": 0, "blend": 1, "last": 2, "offmask3": 3}
+_NARROW_HEAD = [C.c_int] + [C.POINTER(NarrowStencil)] * 3 + [C.c_int] * 4
+
 # kernel variants crfp_conv_probe reports (CRFP_CONVK_*)
 CONV_KERNELS = ("none", "mfma_shift_ct2", "mfma_shift", "mfma_ct2", "mfma_rows4", "mfma_rows8", "split8", "split4", "split_dual", "bf16_x8",
                 "bf16_4w", "bf16_pair", "split_pair")
@@ -110,6 +130,9 @@ SIGNATURES = {
     "crfp_conv_probe_kernel": (C.c_int, [C.c_int, C.POINTER(ProbeConv), C.POINTER(ProbeConv)] + [C.c_int] * 3 + [C.POINTER(C.c_int)]),
     "crfp_conv_probe": (C.c_int, [C.c_int, C.POINTER(ProbeConv), C.POINTER(ProbeConv)] + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_int)] +
                         [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "crfp_narrow_probe_workspace_bytes": (C.c_size_t, _NARROW_HEAD),
+    "crfp_narrow_probe_plan": (C.c_int, _NARROW_HEAD + [C.POINTER(NarrowReport)]),
+    "crfp_narrow_probe": (C.c_int, _NARROW_HEAD + [C.c_void_p, C.c_void_p, C.POINTER(NarrowReport), C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_dsv_debug_fetch": (C.c_int, [C.c_char_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p] +
                              [C.POINTER(C.c_int)] * 3 + [C.c_void_p]),
 }
@@ -166,6 +189,9 @@ for _n in ("workspace_bytes", "status_offset", "forward_clip", "stream_frame"):
 
 for _n in ("workspace_bytes", "kernel", ""):
     _n = "crfp_conv_probe" + ("_" + _n if _n else "")
+    SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
+for _n in ("workspace_bytes", "plan", ""):
+    _n = "crfp_narrow_probe" + ("_" + _n if _n else "")
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 
 _lib = None

@@ -90,10 +90,16 @@ __device__ __forceinline__ void narrow_src_index(int dst, float scale, int in_si
 }
 
 // the second destination of an NE_PLAIN epilogue (NarrowArgs::dst2): the arithmetic of lrelu_q4_to_p4_kernel (resample.hip) on the value
-// as dst holds it (bf16 storage: after its rounding)
+// as dst holds it (bf16 storage: after its rounding).  The range guard looks at lrelu of the value BEFORE that rounding, as the fp32 build, the
+// blend epilogue and the MFMA convs' epilogues do: a 65503 that bf16 holds as 65536 raises nothing (tests/test_gpu_narrow_probe.py,
+// test_range_guard_raises_only_the_item_that_stored_65504), and both builds poison the same frames
 __device__ __forceinline__ void narrow_store_state(act_t* d2, long long ppix, cf32x4 v, float& vmax) {
 #ifdef CRFP_ACT_BF16
+    const cf32x4 u = cf32x4{v.x > 0.0f ? v.x : 0.1f * v.x, v.y > 0.0f ? v.y : 0.1f * v.y, v.z > 0.0f ? v.z : 0.1f * v.z, v.w > 0.0f ? v.w : 0.1f * v.w};
+    vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(u.x), fabsf(u.y))), fmaxf(fabsf(u.z), fabsf(u.w)));
     v = quad_from_bits(quad_to_bits(v));
+    stq(d2 + ppix * 4, cf32x4{v.x > 0.0f ? v.x : 0.1f * v.x, v.y > 0.0f ? v.y : 0.1f * v.y, v.z > 0.0f ? v.z : 0.1f * v.z, v.w > 0.0f ? v.w : 0.1f * v.w});
+    return;
 #endif
     const cf32x4 o = cf32x4{v.x > 0.0f ? v.x : 0.1f * v.x, v.y > 0.0f ? v.y : 0.1f * v.y, v.z > 0.0f ? v.z : 0.1f * v.z, v.w > 0.0f ? v.w : 0.1f * v.w};
     stq(d2 + ppix * 4, o);
@@ -1153,9 +1159,7 @@ int launch_narrow_chain(const NarrowArgs& a, const NarrowArgs& b, const NarrowAr
     if (kqg) in_ch += c.src[1].nch;
     const double px = (double)a.N * a.H * a.W;
     ProfScope prof(name, s, px * (in_ch + c.cout + (c.dst2 ? 4 : 0)) * 4.0, 2.0 * px * 9.0 * (in_ch * a.cout + 4.0 * b.cout + 4.0 * c.cout));
-    const int ntl = ((a.W + KCW - 1) / KCW) * ((a.H + KCH - 1) / KCH);
-    const int share = (ntl + 256 * 3 - 1) / (256 * 3);
-    dim3 grid((ntl + share - 1) / share, 1, a.N);
+    dim3 grid(narrow_chain_grid(a).workgroups, 1, a.N);
     if (res) {
         switch (a.kq) {
             case 1: conv3x3_narrow_chain_kernel<1, 0, true><<<grid, 256, 0, s>>>(a, b, c); break;
@@ -1403,9 +1407,7 @@ int launch_narrow_chain(const NarrowArgs& a, const NarrowArgs& b, const NarrowAr
     if (kqg) in_ch += c.src[1].nch;
     const double px = (double)a.N * a.H * a.W;
     ProfScope prof(name, s, px * (in_ch + c.cout + (c.dst2 ? 4 : 0)) * (double)sizeof(act_t), 2.0 * px * 9.0 * (in_ch * a.cout + 4.0 * b.cout + 4.0 * c.cout));
-    const int ntl = ((a.W + KCW - 1) / KCW) * ((a.H + KCH - 1) / KCH);
-    const int share = (ntl + 256 * 3 - 1) / (256 * 3);
-    dim3 grid((ntl + share - 1) / share, 1, a.N);
+    dim3 grid(narrow_chain_grid(a).workgroups, 1, a.N);
     if (res) {
         if (a.kq == 1) conv3x3_narrow_chain_kernel<1, 0, true><<<grid, 256, 0, s>>>(a, b, c);
         else conv3x3_narrow_chain_kernel<2, 0, true><<<grid, 256, 0, s>>>(a, b, c);
@@ -1421,6 +1423,20 @@ int launch_narrow_chain(const NarrowArgs& a, const NarrowArgs& b, const NarrowAr
 }
 #endif
 
+// ceil-balanced shares: `per_cu` workgroups on each of the 256 CUs walk `tiles` tiles, the same number each (up to one)
+static NarrowGrid narrow_shares(int kernel, int tiles, int per_cu) {
+    const int share = (tiles + 256 * per_cu - 1) / (256 * per_cu);
+    return NarrowGrid{kernel, tiles, (tiles + share - 1) / share};
+}
+
+NarrowGrid narrow_chain_grid(const NarrowArgs& a) {   // both builds: 60 x 16 tiles, three workgroups per CU
+    return narrow_shares(NK_CHAIN, ((a.W + KCW - 1) / KCW) * ((a.H + KCH - 1) / KCH), 3);
+}
+
+NarrowGrid narrow_pair_grid(const NarrowArgs& a) {
+    return narrow_shares(NK_PAIR, ((a.W + NTW - 1) / NTW) * ((a.H + NTH - 1) / NTH), a.kq == 1 ? 3 : 2);
+}
+
 int launch_narrow_pair(const NarrowArgs& a, const NarrowArgs& b, const char* name, hipStream_t s) {
     if (a.kq < 1 || a.kq > 3 || a.cout < 1 || a.cout > 4 || b.kq != 1 || b.cout < 1 || b.cout > 4 ||
         (b.epi != NE_PLAIN && b.epi != NE_OFFMASK3) || a.epi != NE_PLAIN || a.resid || a.act == CRFP_ACT_TANH ||
@@ -1433,10 +1449,7 @@ int launch_narrow_pair(const NarrowArgs& a, const NarrowArgs& b, const char* nam
     const double px = (double)a.N * a.H * a.W;
     const double outb = b.epi == NE_OFFMASK3 ? (3 + 2) * 4.0 : (b.cout + (b.resid ? 4 : 0) + (b.dst2 ? 4 : 0)) * (double)sizeof(act_t);
     ProfScope prof(name, s, px * (in_ch * (double)sizeof(act_t) + outb), 2.0 * px * 9.0 * (in_ch * a.cout + 4.0 * b.cout));
-    const int ntl = ((a.W + NTW - 1) / NTW) * ((a.H + NTH - 1) / NTH);
-    const int per_cu = a.kq == 1 ? 3 : 2;
-    const int share = (ntl + 256 * per_cu - 1) / (256 * per_cu);
-    dim3 grid((ntl + share - 1) / share, 1, a.N);
+    dim3 grid(narrow_pair_grid(a).workgroups, 1, a.N);
 #define CRFP_PAIR_LAUNCH(KQ_)                                                                          \
     if (b.epi == NE_PLAIN) conv3x3_narrow_pair_kernel<KQ_, NE_PLAIN><<<grid, 256, 0, s>>>(a, b);       \
     else conv3x3_narrow_pair_kernel<KQ_, NE_OFFMASK3><<<grid, 256, 0, s>>>(a, b);
@@ -1484,6 +1497,36 @@ int launch_narrow_pack(const NarrowArgs& a, const float* w, const float* bias, c
     return 0;
 }
 
+// which of launch_narrow's two kernel families a stencil takes, and its persistent grid: a few workgroups per CU walk the tiles
+NarrowGrid narrow_grid(const NarrowArgs& a) {
+    const int ntl = ((a.W + NTW - 1) / NTW) * ((a.H + NTH - 1) / NTH);
+#ifdef CRFP_LAB
+    static const int per_cu_env = getenv("CRFP_NARROW_WGS_PER_CU") ? atoi(getenv("CRFP_NARROW_WGS_PER_CU")) : 0;   // tuning knob
+#else
+    constexpr int per_cu_env = 0;
+#endif
+    const int per_cu = per_cu_env > 0 ? per_cu_env : (a.kq == 1 ? CRFP_NARROW_OCC1 : (a.kq == 2 ? CRFP_NARROW_OCC2 : CRFP_NARROW_OCC3));
+#ifndef CRFP_ACT_BF16
+    // Round 6: the plain stencils (dcn_3.dcn_block.0 / .2, dcn_3.conv_fuse; forward_resblocks_3 when its chain is off) in the quad-sequential form.
+    // (The bf16 build runs both 8x conv chains as one launch each -- conv3x3_narrow_chain_kernel -- and keeps conv3x3_narrow_kernel for the rest;
+    // a bf16 twin of this form measured dcn3.block0 42.1 -> 37.0 us before the chains superseded it: profiles/r06_narrow_seq_ab.txt.)
+#ifndef CRFP_NARROW_SEQ
+#define CRFP_NARROW_SEQ 1
+#endif
+#ifndef CRFP_NARROW_SEQ_MINKQ
+#define CRFP_NARROW_SEQ_MINKQ 1   // the one-quad plain stencils too: the form carries the interior-tile fast path (A/B builds: 2)
+#endif
+#ifdef CRFP_LAB   // lab library: CRFP_NARROW_SEQ=0 at run time keeps conv3x3_narrow_kernel for the plain stencils
+    static const bool seq_on = getenv("CRFP_NARROW_SEQ") ? atoi(getenv("CRFP_NARROW_SEQ")) != 0 : CRFP_NARROW_SEQ != 0;
+#else
+    constexpr bool seq_on = CRFP_NARROW_SEQ != 0;
+#endif
+    if (seq_on && !a.gate && !a.dst2 && a.epi == NE_PLAIN && a.kq >= CRFP_NARROW_SEQ_MINKQ && a.act != CRFP_ACT_TANH && a.act != CRFP_ACT_SIGMOID)
+        return narrow_shares(NK_SEQ, ntl, CRFP_NARROW_OCC1);   // one quad's halo at a time: the resources of the one-quad kernel for every kq
+#endif
+    return narrow_shares(NK_NARROW, ntl, per_cu);
+}
+
 int launch_narrow(const NarrowArgs& a_in, const char* name, hipStream_t s) {
     NarrowArgs a = a_in;
     a.stamps = nullptr;
@@ -1528,41 +1571,15 @@ int launch_narrow(const NarrowArgs& a_in, const char* name, hipStream_t s) {
         return 0;
     }
 #endif
-    // persistent: a few workgroups per CU walk the tiles (ceil-balanced shares)
-    const int ntl = ((a.W + NTW - 1) / NTW) * ((a.H + NTH - 1) / NTH);
-#ifdef CRFP_LAB
-    static const int per_cu_env = getenv("CRFP_NARROW_WGS_PER_CU") ? atoi(getenv("CRFP_NARROW_WGS_PER_CU")) : 0;   // tuning knob
-#else
-    constexpr int per_cu_env = 0;
-#endif
-    const int per_cu = per_cu_env > 0 ? per_cu_env : (a.kq == 1 ? CRFP_NARROW_OCC1 : (a.kq == 2 ? CRFP_NARROW_OCC2 : CRFP_NARROW_OCC3));
-    const int share = (ntl + 256 * per_cu - 1) / (256 * per_cu);
-    dim3 grid((ntl + share - 1) / share, 1, a.N);
+    const NarrowGrid g = narrow_grid(a);
+    dim3 grid(g.workgroups, 1, a.N);
 #ifndef CRFP_ACT_BF16
-    {
-    // Round 6: the plain stencils (dcn_3.dcn_block.0 / .2, dcn_3.conv_fuse; forward_resblocks_3 when its chain is off) in the quad-sequential form.
-    // (The bf16 build runs both 8x conv chains as one launch each -- conv3x3_narrow_chain_kernel -- and keeps conv3x3_narrow_kernel for the rest;
-    // a bf16 twin of this form measured dcn3.block0 42.1 -> 37.0 us before the chains superseded it: profiles/r06_narrow_seq_ab.txt.)
-#ifndef CRFP_NARROW_SEQ
-#define CRFP_NARROW_SEQ 1
-#endif
-#ifndef CRFP_NARROW_SEQ_MINKQ
-#define CRFP_NARROW_SEQ_MINKQ 1   // the one-quad plain stencils too: the form carries the interior-tile fast path (A/B builds: 2)
-#endif
-#ifdef CRFP_LAB   // lab library: CRFP_NARROW_SEQ=0 at run time keeps conv3x3_narrow_kernel for the plain stencils
-    static const bool seq_on = getenv("CRFP_NARROW_SEQ") ? atoi(getenv("CRFP_NARROW_SEQ")) != 0 : CRFP_NARROW_SEQ != 0;
-#else
-    constexpr bool seq_on = CRFP_NARROW_SEQ != 0;
-#endif
-    if (seq_on && !a.gate && !a.dst2 && a.epi == NE_PLAIN && a.kq >= CRFP_NARROW_SEQ_MINKQ && a.act != CRFP_ACT_TANH && a.act != CRFP_ACT_SIGMOID) {
-        const int share4 = (ntl + 256 * CRFP_NARROW_OCC1 - 1) / (256 * CRFP_NARROW_OCC1);
-        dim3 grid4((ntl + share4 - 1) / share4, 1, a.N);
-        if (a.kq == 1) conv3x3_narrow_seq_kernel<1><<<grid4, 256, 0, s>>>(a);
-        else if (a.kq == 2) conv3x3_narrow_seq_kernel<2><<<grid4, 256, 0, s>>>(a);
-        else conv3x3_narrow_seq_kernel<3><<<grid4, 256, 0, s>>>(a);
+    if (g.kernel == NK_SEQ) {
+        if (a.kq == 1) conv3x3_narrow_seq_kernel<1><<<grid, 256, 0, s>>>(a);
+        else if (a.kq == 2) conv3x3_narrow_seq_kernel<2><<<grid, 256, 0, s>>>(a);
+        else conv3x3_narrow_seq_kernel<3><<<grid, 256, 0, s>>>(a);
         CRFP_CHECK_LAUNCH();
         return 0;
-    }
     }
 #endif
     if (a.gate) {   // mask-gated forms (engine.hip: encoder_hr and the fovea blend)

@@ -402,6 +402,14 @@ int launch_narrow(const NarrowArgs& a, const char* name, hipStream_t s);
 int launch_narrow_pair(const NarrowArgs& a, const NarrowArgs& b, const char* name, hipStream_t s);
 // three stencils in one pass (conv_narrow.hip): a -> b -> c; res: c adds a's output (residual block; the only form of the bf16 build)
 int launch_narrow_chain(const NarrowArgs& a, const NarrowArgs& b, const NarrowArgs& c, bool res, const char* name, hipStream_t s);
+// The sizing of the three launchers above, each in one host function that the launcher and the test hook (narrow_probe.hip) both call: which
+// kernel family the launch takes (launch_narrow: the persistent LDS-tile kernel or, fp32 build, the quad-sequential form), the tiles of its
+// map (64 x 16; chain: 60 x 16) and the workgroups per batch item that walk them.  `a`: the (first) stencil of the launch.
+enum NarrowKernel : int { NK_NONE = 0, NK_NARROW = 1, NK_SEQ = 2, NK_PAIR = 3, NK_CHAIN = 4 };   // = CRFP_NARROWK_* (include/crfp_hip.h)
+struct NarrowGrid { int kernel, tiles, workgroups; };
+NarrowGrid narrow_grid(const NarrowArgs& a);
+NarrowGrid narrow_pair_grid(const NarrowArgs& a);
+NarrowGrid narrow_chain_grid(const NarrowArgs& a);
 // gather.hip (the fused offset head + dcn_g8: dcn_fused.inc, which it includes)
 // src_pad = 1: x is P4 (padded planes, zero pads): validity logic replaced by clamping + hardware range check
 // N > 1: batch strides in elements of each tensor's own type (activations: act_t, flow: float)

@@ -442,3 +442,114 @@ def conv_probe(a, b=None, mode="single", storage="f32", raw=False):
     if raw:
         res["raw"] = [raws_a] + ([raws_b] if b is not None else [])
     return res
+
+
+def _narrow_desc(spec, n, h, w, dev, keep, last, want_raw, elem_bytes):
+    """crfp_narrow_stencil for one stencil of a narrow_probe call -> (struct, dst, dst2, raw, raw2); tensors only where `dev` is given."""
+    d = _lib.NarrowStencil()
+    srcs = spec.get("srcs", [])
+    d.nsrc = len(srcs)
+    for i, s in enumerate(srcs[:3]):
+        kind, t = s[0], s[1]
+        if isinstance(t, torch.Tensor):
+            t = _dev(t, f"srcs[{i}]")
+            want = (n, t.shape[1], h, w) if kind == "q4" else (n, h, w, 2)
+            assert tuple(t.shape) == want, f"narrow_probe: source {i} ({kind}) is {tuple(t.shape)}, expected {want}"
+            keep.append(t)
+            d.src[i], nch = t.data_ptr(), (t.shape[1] if kind == "q4" else 2)
+        else:   # plan only: the channel count stands for the tensor
+            nch = int(t)
+        d.src_kind[i], d.src_nch[i] = _lib.PROBE_SRC[kind], nch
+    for name in ("weight", "bias", "weight2", "bias2", "residual", "flow", "base_lr", "mask"):
+        t = spec.get(name)
+        if isinstance(t, torch.Tensor):
+            t = _dev(t, name, torch.uint8 if name == "mask" else torch.float32)
+            keep.append(t)
+            setattr(d, name, t.data_ptr())
+    if isinstance(spec.get("weight"), torch.Tensor):
+        cout = spec["weight"].shape[0] + (spec["weight2"].shape[0] if spec.get("weight2") is not None else 0)
+        split = spec["weight"].shape[0] if spec.get("weight2") is not None else 0
+    else:
+        cout, split = int(spec["cout"]), int(spec.get("cout_split", 0))
+    d.cout, d.cout_split = cout, split
+    d.act, d.post_scale, d.epi = ACT[spec.get("act", "none")], float(spec.get("post_scale", 1.0)), _lib.NARROW_EPI[spec.get("epi", "plain")]
+    d.y_only, d.src_pad, d.dst_pad = int(bool(spec.get("y_only"))), int(spec.get("src_pad", 0)), int(spec.get("dst_pad", 0))
+    d.gate_h = -1 if spec.get("gate_h") is None else int(spec["gate_h"])
+    d.dst2_on = int(bool(spec.get("dst2")))
+    out = out2 = raw = raw2 = None
+    if last and dev is not None:
+        epi = spec.get("epi", "plain")
+        out = torch.empty((n, (1 if d.y_only else 3) if epi == "last" else 4, h, w), dtype=torch.float32, device=dev)
+        d.dst = out.data_ptr()
+        if want_raw and epi != "last":
+            eb = 4 if epi == "offmask3" else elem_bytes
+            raw = torch.empty(n * (h + d.dst_pad) * (w + d.dst_pad) * 4 * eb, dtype=torch.uint8, device=dev)
+            d.dst_raw = raw.data_ptr()
+        if d.dst2_on:
+            out2 = torch.empty((n, 4, h, w), dtype=torch.float32, device=dev)
+            d.dst2 = out2.data_ptr()
+            if want_raw:
+                raw2 = torch.empty(n * (h + 1) * (w + 1) * 4 * elem_bytes, dtype=torch.uint8, device=dev)
+                d.dst2_raw = raw2.data_ptr()
+    return d, out, out2, raw, raw2
+
+
+def _narrow_report(r):
+    return {"kernel": _lib.NARROW_KERNELS[r.kernel], "kq": r.kq, "epi": {v: k for k, v in _lib.NARROW_EPI.items()}[r.epi], "gate": bool(r.gate),
+            "st2": bool(r.st2), "kqg": r.kqg, "res": bool(r.res), "tiles": r.tiles, "workgroups": r.workgroups}
+
+
+def narrow_probe_plan(a, b=None, c=None, mode="single", storage="f32", res=False, n=1, h=1, w=1):
+    """crfp_narrow_probe_plan: what narrow_probe would report for the same stencils on an [n, ., h, w] map, on the host alone.  Sources are
+    given as (kind, channels), weights as ``cout`` (and ``cout_split``)."""
+    import ctypes as C
+    L = _lib.lib()
+    sfx = "_bf16" if storage == "bf16" else ""
+    specs = [s for s in (a, b, c) if s is not None]
+    ds = [_narrow_desc(s, n, h, w, None, [], i == len(specs) - 1, False, 0)[0] for i, s in enumerate(specs)]
+    ps = [C.byref(d) for d in ds] + [None] * (3 - len(ds))
+    rep = _lib.NarrowReport()
+    _lib.check(getattr(L, "crfp_narrow_probe_plan" + sfx)(_lib.NARROW_MODES[mode], *ps, int(bool(res)), n, h, w, C.byref(rep)), "crfp_narrow_probe_plan" + sfx)
+    return _narrow_report(rep)
+
+
+def narrow_probe(a, b=None, c=None, mode="single", storage="f32", res=False, status=None, raw=False):
+    """Test hook (crfp_narrow_probe / crfp_narrow_probe_bf16): one launch of the engines' own 8x narrow conv kernels on the caller's tensors.
+
+    ``a`` / ``b`` / ``c`` describe a 3x3 stencil each: ``srcs`` = [(kind, tensor)] with kind "q4" ([n, c <= 4, h, w]) or "flow2" ([n, h, w, 2]);
+    ``weight`` / ``bias`` (and ``weight2`` / ``bias2`` for the rows behind them); ``act``, ``post_scale``, ``residual`` [n, 4, h, w]; ``epi``
+    "plain" / "blend" (``mask`` uint8 [n, 1, h, w]) / "last" (``base_lr`` [n, 3, h / 8, w / 8], ``y_only``) / "offmask3" (``flow``);
+    ``src_pad`` / ``dst_pad`` (0, 1 = padded planes, p > 1 = a window inside planes p wider); ``dst2`` (the second destination); ``gate_h``
+    (0 .. 3: the mask-gated form over ``mask``).  mode "single", "pair" (a feeds b) or "chain" (a -> b -> c; ``res``: c adds a's output).
+    ``status``: int32 [n], the range-guard words before the launch.  Returns a dict: ``out`` (the last stencil's destination, NCHW fp32; elements
+    no lane wrote are NaN), ``out2``, ``status`` (int32 [n] after the launch), ``report`` (kernel family, template arguments, tiles and
+    workgroups per batch item), and with raw=True ``raw`` / ``raw2`` (the raw bytes of the destinations, pads included)."""
+    import ctypes as C
+    L = _lib.lib()
+    sfx = "_bf16" if storage == "bf16" else ""
+    first = a["srcs"][0]
+    t0 = first[1]
+    n, h, w = (t0.shape[0], t0.shape[1], t0.shape[2]) if first[0] == "flow2" else (t0.shape[0], t0.shape[2], t0.shape[3])
+    dev = t0.device
+    keep = []
+    specs = [s for s in (a, b, c) if s is not None]
+    eb = 2 if storage == "bf16" else 4
+    descs = [_narrow_desc(s, n, h, w, dev, keep, i == len(specs) - 1, raw, eb) for i, s in enumerate(specs)]
+    ps = [C.byref(d[0]) for d in descs] + [None] * (3 - len(descs))
+    m = mode if isinstance(mode, int) else _lib.NARROW_MODES[mode]
+    with _on(*keep):
+        nb = getattr(L, "crfp_narrow_probe_workspace_bytes" + sfx)(m, *ps, int(bool(res)), n, h, w)
+        if nb == 0:
+            _lib.check(-1, "crfp_narrow_probe_workspace_bytes" + sfx)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        st_in = None if status is None else _dev(status, "status", torch.int32)
+        st_out = torch.zeros(n, dtype=torch.int32, device=dev)
+        rep = _lib.NarrowReport()
+        _lib.check(getattr(L, "crfp_narrow_probe" + sfx)(m, *ps, int(bool(res)), n, h, w, None if st_in is None else st_in.data_ptr(), st_out.data_ptr(),
+                                                         C.byref(rep), ws.data_ptr(), nb, _stream()), "crfp_narrow_probe" + sfx)
+        torch.cuda.current_stream().synchronize()   # the workspace goes away with this call
+    _, out, out2, rw, rw2 = descs[-1]
+    result = {"out": out, "out2": out2, "status": st_out, "report": _narrow_report(rep)}
+    if raw:
+        result["raw"], result["raw2"] = rw, rw2
+    return result

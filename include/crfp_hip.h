@@ -540,6 +540,85 @@ int crfp_conv_probe_kernel_bf16(int mode, const crfp_probe_conv* a, const crfp_p
 int crfp_conv_probe_bf16(int mode, const crfp_probe_conv* a, const crfp_probe_conv* b, int n, int h, int w, unsigned* status, int* kernel,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Test hook: ONE launch of the engines' own 8x narrow conv kernels (csrc/conv_narrow.hip) on caller-supplied tensors
+ * (tests/test_gpu_narrow_probe.py).  Not a product entry: every call builds the plans, packs the weights, binds the launch arguments and builds
+ * the gate flags as the engines do, converts the API tensors to the build's storage type (fp32, or bf16 for crfp_narrow_probe_bf16), launches,
+ * converts back, and reports which kernel the launcher chose and on how many workgroups.  All tensors are contiguous fp32 device memory
+ * (mask: bytes).  One crfp_narrow_stencil per 3x3 stencil:
+ *   src[i]:   CRFP_PROBE_SRC_Q4 [n, nch <= 4, h, w] or CRFP_PROBE_SRC_FLOW2 [n, h, w, 2] (dx, dy); at most 3 input quads per stencil
+ *   src_pad / dst_pad: 0; 1: source 0 / the destination is held in padded planes ((h + 1) x (w + 1), the pad row and column never written);
+ *             p > 1: the tensor is a window inside planes p wider and p higher (the regional engine's pitch excess); what surrounds a window
+ *             source is filled with non-zero data, what surrounds a window destination keeps the prefill
+ *   weight [cout <= 4, cin, 3, 3], bias [cout]; with weight2 / bias2: rows >= cout_split come from weight2 [cout - cout_split, cin, 3, 3]
+ *   act CRFP_ACT_NONE / RELU / LRELU01, post_scale, residual [n, 4, h, w]
+ *   epi CRFP_NEPI_PLAIN:    dst [n, 4, h, w] = act(conv + bias) * post_scale (+ residual), channels >= cout zero
+ *       CRFP_NEPI_BLEND:    dst [n, 4, h, w] = lrelu_0.1(mask ? conv + bias : centre value of source 0); mask [n, 1, h, w] bytes
+ *       CRFP_NEPI_LAST:     dst [n, 3 or 1 (y_only), h, w] = conv + bias + x8 bilinear of base_lr [n, 3, h / 8, w / 8] (y_only: its luma); h, w
+ *                           multiples of 8; a batch item whose status word is set on entry comes back NaN
+ *       CRFP_NEPI_OFFMASK3: dst [n, 4, h, w] = (10 tanh(o0) + flow_y, 10 tanh(o1) + flow_x, sigmoid(o2), 0); flow [n, h, w, 2]
+ *   dst2_on:  (plain stencils) dst2 [n, 4, h, w] = lrelu_0.1 of what dst receives, held in padded planes on the device
+ *   gate_h:   < 0 dense; 0 .. 3: the mask-gated form, the flag bytes built by launch_mask_gate from `mask` (w a multiple of 4)
+ *   dst_raw / dst2_raw (optional): the raw destination buffers, n * (h + pad) * (w + pad) * 4 elements of the storage type (OFFMASK3: float).
+ * Every destination is filled with 0xFF bytes before the launch, so an element no lane wrote comes back NaN.
+ * mode CRFP_NPROBE_SINGLE: a.  CRFP_NPROBE_PAIR: a feeds b (b brings no source of its own: its one quad is a's output, 4 channels).
+ * CRFP_NPROBE_CHAIN: a -> b -> c; res: c adds a's output; c may bring one more global Q4 source.  In a pair or chain only the last stencil
+ * has destinations, an epilogue other than PLAIN, or a status word; the launcher's own refusals come back unchanged.
+ * status_in (device, n words, may be null = zeros): the range-guard words before the launch; status_out (device, n words): after it; batch
+ * item k raises word k.  crfp_narrow_probe_plan fills the report on the host alone (no launch, tensor pointers ignored). */
+#define CRFP_NPROBE_SINGLE 0
+#define CRFP_NPROBE_PAIR 1
+#define CRFP_NPROBE_CHAIN 2
+#define CRFP_NEPI_PLAIN 0
+#define CRFP_NEPI_BLEND 1
+#define CRFP_NEPI_LAST 2
+#define CRFP_NEPI_OFFMASK3 3
+#define CRFP_NARROWK_NONE 0
+#define CRFP_NARROWK_NARROW 1 /* conv3x3_narrow_kernel<kq, epi, gate, st2> */
+#define CRFP_NARROWK_SEQ 2    /* conv3x3_narrow_seq_kernel<kq> (fp32 build) */
+#define CRFP_NARROWK_PAIR 3   /* conv3x3_narrow_pair_kernel<kq, epi> */
+#define CRFP_NARROWK_CHAIN 4  /* conv3x3_narrow_chain_kernel<kq, kqg, res> */
+typedef struct crfp_narrow_stencil {
+    const float* src[3];
+    const float* weight;
+    const float* bias;
+    const float* weight2;
+    const float* bias2;
+    const float* residual;
+    const float* flow;
+    const float* base_lr;
+    const unsigned char* mask;
+    float* dst;
+    void* dst_raw;
+    float* dst2;
+    void* dst2_raw;
+    int nsrc;
+    int src_kind[3], src_nch[3];
+    int src_pad, dst_pad;
+    int cout, cout_split, act, epi, y_only, gate_h, dst2_on;
+    float post_scale;
+} crfp_narrow_stencil;
+typedef struct crfp_narrow_report {
+    int kernel;              /* CRFP_NARROWK_* */
+    int kq, epi;             /* template arguments: input quads of stencil a, epilogue of the last stencil */
+    int gate, st2;           /* conv3x3_narrow_kernel's GATE and ST2 */
+    int kqg, res;            /* conv3x3_narrow_chain_kernel's KQG and RES */
+    int tiles, workgroups;   /* tiles of the map and workgroups that walk them, per batch item */
+} crfp_narrow_report;
+size_t crfp_narrow_probe_workspace_bytes(int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res,
+                                         int n, int h, int w);   /* 0: refused (crfp_last_error) */
+int crfp_narrow_probe_plan(int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res, int n, int h,
+                           int w, crfp_narrow_report* report);
+int crfp_narrow_probe(int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res, int n, int h, int w,
+                      const unsigned* status_in, unsigned* status_out, crfp_narrow_report* report, void* workspace, size_t workspace_bytes,
+                      void* stream);
+size_t crfp_narrow_probe_workspace_bytes_bf16(int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c,
+                                              int res, int n, int h, int w);
+int crfp_narrow_probe_plan_bf16(int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res, int n,
+                                int h, int w, crfp_narrow_report* report);
+int crfp_narrow_probe_bf16(int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res, int n, int h,
+                           int w, const unsigned* status_in, unsigned* status_out, crfp_narrow_report* report, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- The benchmark-only regional wiring, model/CRFP_runtime.py::MRCF_simple_v18.forward(lrs, fvs, warp_size) (:8469-8664;
  * built and timed by the reference's test_runtime.py:41,142) as ONE call per clip.  mid_channels = 32, split_ratio = 3, offset_prop.
  * Same conventions as the CRFP_DSV engine above: parameters as CRFP_RT_NUM_PARAMS device pointers in state_dict order

@@ -389,6 +389,167 @@ int main() {
         EXPECT(crfp_conv_probe(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62, st, k, wsp, crfp_conv_probe_workspace_bytes(CRFP_PROBE_S3_CHAIN, &a0, &two, 2, 8, 62), nullptr) == 0);
         EXPECT(crfp_stub_launches() > l0);
     }
+    // the narrow probe (test hook): the launchers' sizing functions (tiles and workgroups of launch_narrow's two branches, of the pair and of the
+    // chain launcher), the kernel family per build, every refusal of the probe before the first launch, and the launchers' own refusals passed
+    // through from whole calls on the stub
+    {
+        crfp_narrow_stencil q;
+        std::memset(&q, 0, sizeof(q));
+        q.nsrc = 1; q.src_kind[0] = CRFP_PROBE_SRC_Q4; q.src_nch[0] = 4; q.cout = 4; q.post_scale = 1.0f; q.gate_h = -1;
+        crfp_narrow_stencil fed = q;      // the second / third stencil of a pair / chain: its quad is the stencil before it
+        fed.nsrc = 0;
+        crfp_narrow_stencil q2 = q, q3 = q;
+        q2.nsrc = 2; q2.src_kind[1] = CRFP_PROBE_SRC_Q4; q2.src_nch[1] = 4;
+        q3 = q2; q3.nsrc = 3; q3.src_kind[2] = CRFP_PROBE_SRC_FLOW2; q3.src_nch[2] = 2;
+        crfp_narrow_report r;
+        const long l0 = crfp_stub_launches();
+        auto plan = [&](bool bf16, int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res, int h, int w) {
+            std::memset(&r, 0xEE, sizeof(r));
+            return bf16 ? crfp_narrow_probe_plan_bf16(mode, a, b, c, res, 1, h, w, &r) : crfp_narrow_probe_plan(mode, a, b, c, res, 1, h, w, &r);
+        };
+        // one tile; 17 x 65 = 2 x 2 tiles; a 650 x 2040 map = 41 x 32 = 1 312 tiles of 64 x 16, 41 x 34 = 1 394 of 60 x 16
+        EXPECT(plan(false, CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 1, 1) == 0 && r.kernel == CRFP_NARROWK_SEQ && r.kq == 1 && r.tiles == 1 && r.workgroups == 1);
+        EXPECT(plan(true, CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 17, 65) == 0 && r.kernel == CRFP_NARROWK_NARROW && r.epi == CRFP_NEPI_PLAIN && !r.gate && !r.st2 && r.tiles == 4 && r.workgroups == 4);
+        // fp32 build: the quad-sequential form at four workgroups per CU whatever kq (1 024 slots -> shares of 2 -> 656 workgroups)
+        EXPECT(plan(false, CRFP_NPROBE_SINGLE, &q3, nullptr, nullptr, 0, 650, 2040) == 0 && r.kernel == CRFP_NARROWK_SEQ && r.kq == 3 && r.tiles == 1312 && r.workgroups == 656);
+        EXPECT(plan(false, CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 512, 2048) == 0 && r.tiles == 1024 && r.workgroups == 1024);
+        EXPECT(plan(false, CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 513, 2048) == 0 && r.tiles == 1056 && r.workgroups == 528);
+        // bf16 build: conv3x3_narrow_kernel at 5 / 3 / 2 workgroups per CU
+        EXPECT(plan(true, CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 650, 2040) == 0 && r.kernel == CRFP_NARROWK_NARROW && r.workgroups == 656);    // 1 280 slots: shares of 2
+        EXPECT(plan(true, CRFP_NPROBE_SINGLE, &q2, nullptr, nullptr, 0, 650, 2040) == 0 && r.kq == 2 && r.workgroups == 656);                           // 768 slots: shares of 2
+        EXPECT(plan(true, CRFP_NPROBE_SINGLE, &q3, nullptr, nullptr, 0, 650, 2040) == 0 && r.kq == 3 && r.workgroups == 438);                           // 512 slots: shares of 3
+        {   // the forms that stay on conv3x3_narrow_kernel in the fp32 build: an epilogue, a gate, a second destination
+            crfp_narrow_stencil e = q2;
+            e.epi = CRFP_NEPI_BLEND;
+            EXPECT(plan(false, CRFP_NPROBE_SINGLE, &e, nullptr, nullptr, 0, 650, 2040) == 0 && r.kernel == CRFP_NARROWK_NARROW && r.epi == CRFP_NEPI_BLEND && r.workgroups == 656);
+            e.gate_h = 2;
+            EXPECT(plan(false, CRFP_NPROBE_SINGLE, &e, nullptr, nullptr, 0, 72, 328) == 0 && r.kernel == CRFP_NARROWK_NARROW && r.gate && r.tiles == 30);
+            e = q; e.dst2_on = 1;
+            EXPECT(plan(false, CRFP_NPROBE_SINGLE, &e, nullptr, nullptr, 0, 17, 65) == 0 && r.kernel == CRFP_NARROWK_NARROW && r.st2 && !r.gate);
+            e = q; e.epi = CRFP_NEPI_LAST; e.cout = 3;
+            EXPECT(plan(false, CRFP_NPROBE_SINGLE, &e, nullptr, nullptr, 0, 16, 64) == 0 && r.kernel == CRFP_NARROWK_NARROW && r.epi == CRFP_NEPI_LAST);
+            EXPECT(plan(false, CRFP_NPROBE_SINGLE, &e, nullptr, nullptr, 0, 17, 64) == CRFP_E_BADARG);                  // the x8 base needs multiples of 8
+        }
+        // pair: three workgroups per CU for one input quad, two otherwise; chain: 60-column tiles, three per CU
+        EXPECT(plan(false, CRFP_NPROBE_PAIR, &q, &fed, nullptr, 0, 650, 2040) == 0 && r.kernel == CRFP_NARROWK_PAIR && r.kq == 1 && r.tiles == 1312 && r.workgroups == 656);
+        EXPECT(plan(true, CRFP_NPROBE_PAIR, &q3, &fed, nullptr, 0, 650, 2040) == 0 && r.kq == 3 && r.workgroups == 438);
+        EXPECT(plan(false, CRFP_NPROBE_CHAIN, &q2, &fed, &fed, 1, 650, 2040) == 0 && r.kernel == CRFP_NARROWK_CHAIN && r.kq == 2 && r.kqg == 0 && r.res && r.tiles == 1394 && r.workgroups == 697);
+        EXPECT(plan(true, CRFP_NPROBE_CHAIN, &q, &fed, &q, 0, 16, 60) == 0 && r.kqg == 1 && !r.res && r.tiles == 1 && r.workgroups == 1);
+        EXPECT(crfp_narrow_probe_plan(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 1, 16, 64, nullptr) == CRFP_E_BADARG);
+        // the probe's own refusals, sizes-only and both builds
+        auto refused = [&](int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, const char* text) {
+            const bool zero = crfp_narrow_probe_workspace_bytes(mode, a, b, c, 0, 2, 16, 64) == 0 && std::strstr(crfp_last_error_string(), text) != nullptr;
+            return zero && crfp_narrow_probe_workspace_bytes_bf16(mode, a, b, c, 0, 2, 16, 64) == 0 && std::strstr(crfp_last_error_string(), text) != nullptr;
+        };
+        EXPECT(crfp_narrow_probe_workspace_bytes(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64) > 2ull * 2 * 16 * 64 * 16);
+        EXPECT(crfp_narrow_probe_workspace_bytes_bf16(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64) < crfp_narrow_probe_workspace_bytes(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64));
+        EXPECT(refused(3, &q, &fed, &fed, "unknown mode") && refused(-1, &q, nullptr, nullptr, "unknown mode"));
+        EXPECT(refused(CRFP_NPROBE_PAIR, &q, nullptr, nullptr, "null stencil") && refused(CRFP_NPROBE_CHAIN, &q, &fed, nullptr, "null stencil"));
+        EXPECT(refused(CRFP_NPROBE_PAIR, &q, &q, nullptr, "a pair's second stencil reads one quad"));
+        EXPECT(refused(CRFP_NPROBE_CHAIN, &q, &q, &fed, "at most 0 global quad") && refused(CRFP_NPROBE_CHAIN, &q, &fed, &q2, "at most 1 global quad"));
+        for (int bad = 0; bad < 12; ++bad) {
+            crfp_narrow_stencil d = q;
+            switch (bad) {
+                case 0: d.cout = 5; break;
+                case 1: d.cout = 0; break;
+                case 2: d.nsrc = 4; break;                                     // more than 3 input quads
+                case 3: d.nsrc = 0; break;
+                case 4: d.src_kind[0] = CRFP_PROBE_SRC_UNSHUF4; break;
+                case 5: d.src_nch[0] = 5; break;                               // a source is one quad
+                case 6: d.act = CRFP_ACT_TANH; break;                          // no engine item uses tanh / sigmoid
+                case 7: d.epi = 4; break;
+                case 8: d.cout_split = 4; break;
+                case 9: d.src_kind[0] = CRFP_PROBE_SRC_FLOW2; d.src_nch[0] = 2; d.src_pad = 1; break;   // only a Q4 source is padded
+                case 10: d.gate_h = 4; break;
+                default: d.epi = CRFP_NEPI_OFFMASK3; d.dst_pad = 1; break;     // only Q4 destinations are padded
+            }
+            EXPECT(crfp_narrow_probe_workspace_bytes(CRFP_NPROBE_SINGLE, &d, nullptr, nullptr, 0, 2, 16, 64) == 0);
+            EXPECT(crfp_narrow_probe_workspace_bytes_bf16(CRFP_NPROBE_SINGLE, &d, nullptr, nullptr, 0, 2, 16, 64) == 0);
+        }
+        {
+            crfp_narrow_stencil g = q;
+            g.gate_h = 1;
+            EXPECT(crfp_narrow_probe_workspace_bytes(CRFP_NPROBE_SINGLE, &g, nullptr, nullptr, 0, 2, 16, 66) == 0);   // the mask is read four bytes at a time
+            crfp_narrow_stencil gf = fed;
+            gf.gate_h = 0;
+            EXPECT(refused(CRFP_NPROBE_PAIR, &q, &gf, nullptr, "no mask-gated form of a pair or chain"));
+            g.dst2_on = 1;
+            EXPECT(refused(CRFP_NPROBE_SINGLE, &g, nullptr, nullptr, "no mask-gated form with a second destination"));
+            crfp_narrow_stencil a2 = q;
+            a2.dst2_on = 1;
+            EXPECT(refused(CRFP_NPROBE_PAIR, &a2, &fed, nullptr, "only the last stencil"));
+            crfp_narrow_stencil pd = q;
+            pd.src_pad = 1;
+            EXPECT(refused(CRFP_NPROBE_PAIR, &pd, &fed, nullptr, "unpadded tensors"));
+        }
+        // the call: null tensors, null status / report, a short workspace -- all before the first launch
+        unsigned* const st = reinterpret_cast<unsigned*>(16);
+        const size_t w32 = crfp_narrow_probe_workspace_bytes(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64);
+        EXPECT(crfp_narrow_probe(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64, nullptr, st, &r, p16, w32, nullptr) == CRFP_E_BADARG);   // null tensors
+        EXPECT(crfp_stub_launches() == l0);
+        char* const dev = reinterpret_cast<char*>(0x300000000000ull);
+        auto fab = [&](crfp_narrow_stencil& d, int slot) {
+            float* const base = reinterpret_cast<float*>(dev + ((size_t)slot << 32));
+            for (int i = 0; i < 3; ++i) d.src[i] = base + (i << 24);
+            d.weight = base + (5 << 24); d.bias = base + (6 << 24); d.weight2 = base + (7 << 24); d.bias2 = base + (8 << 24);
+            d.flow = base + (9 << 24); d.base_lr = base + (10 << 24); d.mask = reinterpret_cast<const unsigned char*>(base + (11 << 24));
+            d.dst = base + (12 << 24); d.dst_raw = base + (13 << 24); d.dst2 = base + (14 << 24); d.dst2_raw = base + (15 << 24);
+        };
+        fab(q, 0); fab(fed, 1); fab(q2, 2); fab(q3, 3);
+        void* const wsp = dev + (100ull << 32);
+        EXPECT(crfp_narrow_probe(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64, nullptr, nullptr, &r, wsp, w32, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_narrow_probe(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64, nullptr, st, nullptr, wsp, w32, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_narrow_probe(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64, nullptr, st, &r, wsp, w32 - 1, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_narrow_probe(CRFP_NPROBE_SINGLE, &q, nullptr, nullptr, 0, 2, 16, 64, nullptr, st, &r, nullptr, w32, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_stub_launches() == l0);
+        // accepted calls on the stub runtime, device pointers fabricated: every mode, epilogue and pad, both builds
+        auto call = [&](bool bf16, int mode, const crfp_narrow_stencil* a, const crfp_narrow_stencil* b, const crfp_narrow_stencil* c, int res, int n, int h, int w) {
+            const size_t bytes = bf16 ? crfp_narrow_probe_workspace_bytes_bf16(mode, a, b, c, res, n, h, w) : crfp_narrow_probe_workspace_bytes(mode, a, b, c, res, n, h, w);
+            if (!bytes) return -1000;
+            return bf16 ? crfp_narrow_probe_bf16(mode, a, b, c, res, n, h, w, st, st, &r, wsp, bytes, nullptr)
+                        : crfp_narrow_probe(mode, a, b, c, res, n, h, w, st, st, &r, wsp, bytes, nullptr);
+        };
+        crfp_narrow_stencil win = q, blend = q2, lastq = q, om = q, st2 = q, gated = q2;
+        win.src_pad = 37; win.dst_pad = 37; win.residual = p16; win.act = CRFP_ACT_LRELU01;
+        blend.epi = CRFP_NEPI_BLEND;
+        lastq.epi = CRFP_NEPI_LAST; lastq.cout = 1; lastq.y_only = 1;
+        om.epi = CRFP_NEPI_OFFMASK3; om.cout = 3; om.cout_split = 2;
+        st2.dst2_on = 1; st2.src_pad = 1; st2.dst_pad = 1;
+        gated.gate_h = 3;
+        const crfp_narrow_stencil* singles[] = {&q, &q2, &q3, &win, &blend, &lastq, &om, &st2, &gated};
+        for (const crfp_narrow_stencil* c : singles)
+            for (const auto& g : {std::initializer_list<int>{1, 8, 8}, {3, 16, 64}, {2, 72, 328}})
+                for (int bf16 = 0; bf16 < 2; ++bf16)
+                    EXPECT(call(bf16 != 0, CRFP_NPROBE_SINGLE, c, nullptr, nullptr, 0, g.begin()[0], g.begin()[1], g.begin()[2]) == 0);
+        crfp_narrow_stencil fed_om = fed, fed_st2 = fed;
+        fed_om.epi = CRFP_NEPI_OFFMASK3; fed_om.cout = 3; fed_om.cout_split = 2;
+        fed_st2.dst2_on = 1; fed_st2.residual = p16;
+        for (int bf16 = 0; bf16 < 2; ++bf16) {
+            EXPECT(call(bf16 != 0, CRFP_NPROBE_PAIR, &q3, &fed_om, nullptr, 0, 2, 17, 65) == 0 && r.kernel == CRFP_NARROWK_PAIR && r.epi == CRFP_NEPI_OFFMASK3);
+            EXPECT(call(bf16 != 0, CRFP_NPROBE_PAIR, &q, &fed_st2, nullptr, 0, 2, 17, 65) == 0);
+            EXPECT(call(bf16 != 0, CRFP_NPROBE_CHAIN, &q2, &fed, &fed_st2, 1, 2, 17, 61) == CRFP_E_UNSUPPORTED);      // c has a residual of its own
+            EXPECT(call(bf16 != 0, CRFP_NPROBE_CHAIN, &q3, &fed, &q, 0, 2, 17, 61) == 0 && r.kernel == CRFP_NARROWK_CHAIN && r.kqg == 1);
+            EXPECT(call(bf16 != 0, CRFP_NPROBE_CHAIN, &q, &fed, &q, 1, 2, 17, 61) == CRFP_E_UNSUPPORTED);             // a residual chain has no global quad in c
+            EXPECT(std::strstr(crfp_last_error_string(), "conv_narrow_chain narrow_probe:chain: unsupported chain (kqA=1 kqB=1 kqC=2 res=1)") != nullptr);
+        }
+        // the launchers' own refusals come back unchanged: chain shapes per build, the gated and the second-destination forms, a residual on a pair's a
+        EXPECT(call(false, CRFP_NPROBE_CHAIN, &q3, &fed, &fed, 1, 2, 17, 61) == 0 && call(true, CRFP_NPROBE_CHAIN, &q3, &fed, &fed, 1, 2, 17, 61) == CRFP_E_UNSUPPORTED);
+        EXPECT(call(false, CRFP_NPROBE_CHAIN, &q, &fed, &fed, 0, 2, 17, 61) == 0 && call(true, CRFP_NPROBE_CHAIN, &q, &fed, &fed, 0, 2, 17, 61) == CRFP_E_UNSUPPORTED);
+        {
+            crfp_narrow_stencil g3 = q3, gb = q, d2 = q2, ra = q;
+            g3.gate_h = 0; gb.gate_h = 0; gb.epi = CRFP_NEPI_BLEND; d2.dst2_on = 1; ra.residual = p16;
+            for (int bf16 = 0; bf16 < 2; ++bf16) {
+                EXPECT(call(bf16 != 0, CRFP_NPROBE_SINGLE, &g3, nullptr, nullptr, 0, 2, 16, 64) == CRFP_E_UNSUPPORTED);
+                EXPECT(std::strstr(crfp_last_error_string(), "conv_narrow narrow_probe:a: no mask-gated form for kq=3 epi=0") != nullptr);
+                EXPECT(call(bf16 != 0, CRFP_NPROBE_SINGLE, &gb, nullptr, nullptr, 0, 2, 16, 64) == CRFP_E_UNSUPPORTED);
+                EXPECT(call(bf16 != 0, CRFP_NPROBE_SINGLE, &d2, nullptr, nullptr, 0, 2, 16, 64) == CRFP_E_UNSUPPORTED);
+                EXPECT(std::strstr(crfp_last_error_string(), "a second destination needs a plain one-quad stencil (kq=2 epi=0)") != nullptr);
+                EXPECT(call(bf16 != 0, CRFP_NPROBE_PAIR, &ra, &fed, nullptr, 0, 2, 16, 64) == CRFP_E_UNSUPPORTED);
+                EXPECT(std::strstr(crfp_last_error_string(), "conv_narrow_pair narrow_probe:pair: unsupported pair") != nullptr);
+            }
+        }
+        EXPECT(crfp_stub_launches() > l0);
+    }
     // ---- whole engine calls on the stub runtime (tools/asan_host/hip_stub.cpp: every HIP call succeeds, no kernel runs): the host side of a
     // call -- argument checks, Layout arenas, the launch-argument tables of ~50 launches per frame, the fork / join of the side stream, the
     // per-thread stream table and crfp_shutdown() -- under the sanitizers.  Device pointers are fabricated and never dereferenced on the host.

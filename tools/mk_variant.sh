@@ -15,11 +15,11 @@ LABDEF="-DCRFP_LAB"; OBJDIR=build_lab
 if [ "${LAB:-1}" = 0 ]; then LABDEF=""; OBJDIR=build; fi   # LAB=0: a variant of the PRODUCT build (no lab switches compiled in)
 /opt/rocm/bin/hipcc $FLAGS $LABDEF $SCHED $extra -c $C/$base.hip -o $ROOT/_ab/obj/$base.$name.o 2>&1 | grep -v "not a recognized feature" | grep -E "error|warning: fail" || true
 objs=""
-for f in runtime conv_mfma conv_narrow gather resample metrics gaze frameio engine engine_rt api spynet conv_probe; do   # = SRCS of csrc/Makefile
+for f in runtime conv_mfma conv_narrow gather resample metrics gaze frameio engine engine_rt api spynet conv_probe narrow_probe; do   # = SRCS of csrc/Makefile
   if [ $f = $base ]; then objs="$objs $ROOT/_ab/obj/$base.$name.o"; else objs="$objs $C/$OBJDIR/$f.o"; fi
 done
 # BF16=1: the bf16-storage object of the same source is recompiled with the same flags too (default: the product's bf16 objects)
-for f in conv_mfma conv_narrow gather resample engine conv_probe; do   # = BF16_SRCS of csrc/Makefile
+for f in conv_mfma conv_narrow gather resample engine conv_probe narrow_probe; do   # = BF16_SRCS of csrc/Makefile
   if [ "${BF16:-0}" = 1 ] && [ $f = $base ]; then
     /opt/rocm/bin/hipcc $FLAGS -DCRFP_ACT_BF16 $SCHED $extra -c $C/$base.hip -o $ROOT/_ab/obj/$base.$name.bf16.o 2>&1 | grep -v "not a recognized feature" | grep -E "error|warning: fail" || true
     objs="$objs $ROOT/_ab/obj/$base.$name.bf16.o"
