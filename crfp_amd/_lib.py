@@ -17,6 +17,7 @@ DSV_INPUTS_RESIDENT = 8   # crfp_dsv_stream_frame only
 METRICS_LUMA = 1   # flag of crfp_frame_metrics_f32
 GAZE_ROW_INTS, GAZE_EXISTS, GAZE_COUNTS = 24, 1, 2   # row length and entry flags of crfp_gaze_prep_f32
 IO_BGR, IO_RECT_INTS, IO_HAS_FOVEA = 1, 4, 1   # call flag, row length and row flag of crfp_frame_ingest_u8 / crfp_frame_export_u8
+IO_OUT_F32, IO_TWO_PASS = 2, 4   # flags of crfp_resize_bicubic_u8: fp32 planar output; the two-pass path whatever the geometry
 
 c_float_p = C.POINTER(C.c_float)
 
@@ -103,6 +104,10 @@ SIGNATURES = {
     "crfp_gaze_prep_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
     "crfp_frame_ingest_u8": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 8 + [C.c_void_p]),
     "crfp_frame_export_u8": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "crfp_bicubic_taps": (C.c_int, [C.c_int] * 2 + [C.POINTER(C.c_int32)] * 2 + [C.c_int]),
+    "crfp_resize_bicubic_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    "crfp_resize_bicubic_u8": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "crfp_frame_export_y_bicubic_u8": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_dsv_param_name": (C.c_char_p, [C.c_int]),
     "crfp_dsv_param_numel": (C.c_int, [C.c_int, C.c_int]),
     "crfp_dsv_packed_weight_bytes": (C.c_size_t, [C.c_int]),

@@ -453,6 +453,48 @@ int crfp_frame_export_u8(const float* sr, const float* chroma, uint8_t* out_u8, 
     return launch_frame_export(sr, chroma, out_u8, n, c, H, W, flags & CRFP_IO_BGR, (hipStream_t)stream);
 }
 
+int crfp_bicubic_taps(int in_size, int out_size, int32_t* bounds, int32_t* taps, int taps_capacity) {
+    if (!bounds || !taps) { set_error("bicubic_taps: null pointer"); return CRFP_E_BADARG; }
+    if (in_size < 1 || out_size < 1) { set_error("bicubic_taps: bad argument (need in_size, out_size >= 1)"); return CRFP_E_BADARG; }
+    const long long ksize = bicubic_ksize(in_size, out_size);
+    if (ksize * out_size > 0x7fffffffLL) { set_error("bicubic_taps: a table of %lld x %d taps does not fit an int", ksize, out_size); return CRFP_E_UNSUPPORTED; }
+    if (taps_capacity < ksize * out_size) { set_error("bicubic_taps: taps holds %d ints, %lld x %d are needed", taps_capacity, ksize, out_size); return CRFP_E_WORKSPACE; }
+    bicubic_taps_host(in_size, out_size, (int)ksize, bounds, taps);
+    return (int)ksize;
+}
+
+size_t crfp_resize_bicubic_workspace_bytes(int n, int h, int w, int H, int W) { return bicubic_workspace_bytes(n, h, w, H, W); }
+
+// the checks the two bicubic entry points share, after their pointers and flags
+static int bicubic_check(const char* what, int n, int h, int w, int H, int W, const void* workspace, size_t workspace_bytes) {
+    if (n < 1 || h < 1 || w < 1 || H < 1 || W < 1) { set_error("%s: bad argument (need n, h, w, H, W >= 1)", what); return CRFP_E_BADARG; }
+    const size_t need = bicubic_workspace_bytes(n, h, w, H, W);
+    if (!need) {
+        set_error("%s: more than 65535 frames per call, tap tables beyond an int or a frame beyond the launch grid", what);
+        return CRFP_E_UNSUPPORTED;
+    }
+    if (!workspace || workspace_bytes < need) { set_error("%s: workspace too small (%zu bytes, %zu are needed)", what, workspace ? workspace_bytes : (size_t)0, need); return CRFP_E_WORKSPACE; }
+    if ((uintptr_t)workspace % 16) { set_error("%s: the workspace must be 16-byte aligned", what); return CRFP_E_BADARG; }
+    return 0;
+}
+
+int crfp_resize_bicubic_u8(const uint8_t* src, void* dst, int n, int h, int w, int H, int W, int flags, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    if (!src || !dst) { set_error("resize_bicubic: null pointer (src and dst are required)"); return CRFP_E_BADARG; }
+    if (flags & ~(CRFP_IO_BGR | CRFP_IO_OUT_F32 | CRFP_IO_TWO_PASS)) { set_error("resize_bicubic: unknown flags 0x%x", flags); return CRFP_E_BADARG; }
+    if (const int rc = bicubic_check("resize_bicubic", n, h, w, H, W, workspace, workspace_bytes)) return rc;
+    return launch_bicubic(src, dst, nullptr, n, h, w, H, W, flags & CRFP_IO_OUT_F32 ? BC_EPI_F32 : BC_EPI_U8, flags & CRFP_IO_BGR,
+                          flags & CRFP_IO_TWO_PASS, workspace, (hipStream_t)stream);
+}
+
+int crfp_frame_export_y_bicubic_u8(const float* luma, const uint8_t* lr_u8, uint8_t* out_u8, int n, int h, int w, int H, int W, int flags,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (!luma || !lr_u8 || !out_u8) { set_error("frame_export_y_bicubic: null pointer (luma, lr_u8 and out_u8 are required)"); return CRFP_E_BADARG; }
+    if (flags & ~CRFP_IO_BGR) { set_error("frame_export_y_bicubic: unknown flags 0x%x (the BGR flag is the only one)", flags); return CRFP_E_BADARG; }
+    if (const int rc = bicubic_check("frame_export_y_bicubic", n, h, w, H, W, workspace, workspace_bytes)) return rc;
+    return launch_bicubic(lr_u8, out_u8, luma, n, h, w, H, W, BC_EPI_MERGE, flags & CRFP_IO_BGR, 0, workspace, (hipStream_t)stream);
+}
+
 int crfp_psnr_partial_f32(const float* a, const float* b, double* acc, int n, int c, int h, int w, void* stream) {
     if (!a || !b || !acc || n < 1 || c < 1 || h < 1 || w < 1) { set_error("psnr_partial: bad argument"); return CRFP_E_BADARG; }
     return launch_psnr_partial(a, b, acc, n, c, h, w, (hipStream_t)stream);

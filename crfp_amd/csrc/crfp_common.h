@@ -509,5 +509,14 @@ int launch_gaze_prep(const float* gt, const int* rows, float* fv, uint8_t* mk, u
 int launch_frame_ingest(const uint8_t* lr_u8, const uint8_t* crop_u8, const int* rects, float* lr, float* fv, uint8_t* mk, int N, int h, int w,
                         int fh, int fw, int H, int W, int bgr, hipStream_t s);
 int launch_frame_export(const float* sr, const float* chroma, uint8_t* out_u8, int N, int C, int H, int W, int bgr, hipStream_t s);
+#ifndef CRFP_ACT_BF16
+// bicubic.hip (fp32 build only): PIL's 8-bit bicubic resize.  epi: where the resized bytes go
+enum { BC_EPI_U8 = 0, BC_EPI_F32 = 1, BC_EPI_MERGE = 2 };   // bytes [N,H,W,3]; fp32 planes [N,3,H,W]; the y_only merge under `luma` -> bytes
+long long bicubic_ksize(int in, int out);                                  // ints per output index of an axis' tap table
+void bicubic_taps_host(int in, int out, int ksize, int* bounds, int* taps);
+size_t bicubic_workspace_bytes(int N, int h, int w, int H, int W);         // 0: outside what launch_bicubic takes
+int launch_bicubic(const uint8_t* src, void* dst, const float* luma, int N, int h, int w, int H, int W, int epi, int bgr, int two_pass,
+                   void* workspace, hipStream_t s);
+#endif
 
 }  // namespace CRFP_NS

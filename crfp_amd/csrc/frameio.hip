@@ -14,14 +14,10 @@
 // VEC: a thread owns 4 consecutive pixels -- one 16-byte access per fp32 plane, three 4-byte accesses of interleaved bytes, one 4-byte mask store;
 // the scalar form (sizes off a multiple of 4 or pointers off their alignment) owns one pixel.  Every output byte is written exactly once; no
 // atomics, no LDS, nothing to initialise.
+#include "frameio_px.h"
 #include "rects.h"
 
 namespace crfp {
-
-__device__ __forceinline__ float io_unit(unsigned byte) { return (float)byte / 255.0f; }
-__device__ __forceinline__ unsigned io_q(float v) { return (unsigned)rintf(fminf(fmaxf(v * 255.0f, 0.0f), 255.0f)); }
-// byte k (k < 12) of three little-endian words
-__device__ __forceinline__ unsigned io_byte(const unsigned (&w)[3], int k) { return w[k / 4] >> 8 * (k % 4) & 0xffu; }
 
 // NPX pixels of interleaved bytes at `s` -> ch[c][i] = channel c (memory order) of pixel i, as a fraction of 255
 template <int NPX>
@@ -35,24 +31,6 @@ __device__ __forceinline__ void io_load_px(const uint8_t* __restrict__ s, float 
 #pragma unroll
         for (int c = 0; c < 3; ++c) ch[c][0] = io_unit(s[c]);
     }
-}
-
-// NPX consecutive floats of a plane
-template <int NPX>
-__device__ __forceinline__ void io_load_plane(const float* __restrict__ s, float (&v)[NPX]) {
-    if constexpr (NPX == 4) {
-        const cf32x4 q = *reinterpret_cast<const cf32x4*>(s);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-        v[0] = *s;
-    }
-}
-
-// ... and their store
-template <int NPX>
-__device__ __forceinline__ void io_store_plane(float* __restrict__ d, const float (&v)[NPX]) {
-    if constexpr (NPX == 4) *reinterpret_cast<cf32x4*>(d) = cf32x4{v[0], v[1], v[2], v[3]};
-    else *d = v[0];
 }
 
 // hw = h * w pixels per plane; VEC: hw % 4 == 0, src 4-byte and dst 16-byte aligned
@@ -123,27 +101,13 @@ __global__ __launch_bounds__(256) void frame_export_kernel(const float* __restri
         io_load_plane<NPX>(a, yy); io_load_plane<NPX>(b, r); io_load_plane<NPX>(b + hw, g); io_load_plane<NPX>(b + 2 * hw, bl);
 #pragma unroll
         for (int i = 0; i < NPX; ++i) {
-            const float u = ((-0.147f * r[i]) - (0.289f * g[i])) + (0.436f * bl[i]);
-            const float v = ((0.615f * r[i]) - (0.515f * g[i])) - (0.100f * bl[i]);
-            ch[0][i] = yy[i] + (1.14f * v);
-            ch[1][i] = (yy[i] + (-0.396f * u)) - (0.581f * v);
-            ch[2][i] = yy[i] + (2.029f * u);
+            io_merge(yy[i], r[i], g[i], bl[i], ch[0][i], ch[1][i], ch[2][i]);
         }
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c) io_load_plane<NPX>(a + c * hw, ch[c]);
     }
-    uint8_t* o = out + (n * hw + p) * 3;
-    if constexpr (VEC) {
-        unsigned w[3] = {0u, 0u, 0u};
-#pragma unroll
-        for (int k = 0; k < 12; ++k) w[k / 4] |= io_q(bgr ? ch[2 - k % 3][k / 3] : ch[k % 3][k / 3]) << 8 * (k % 4);
-        unsigned* o4 = reinterpret_cast<unsigned*>(o);
-        o4[0] = w[0]; o4[1] = w[1]; o4[2] = w[2];
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[bgr ? 2 - c : c] = (uint8_t)io_q(ch[c][0]);
-    }
+    io_store_px<NPX>(out + (n * hw + p) * 3, ch, bgr);
 }
 
 // grid of one thread per NPX pixels of `threads` per frame; false (with the error set) beyond the launch grid

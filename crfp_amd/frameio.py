@@ -8,6 +8,8 @@ window and a full-frame ``mk``, all fp32 / byte planes, and return fp32 NCHW.  T
 
   * ``ingest`` turns an 8-bit LR frame, an 8-bit fovea crop and one rectangle into ``(lr, fv, mk)`` on the device,
   * ``export`` turns the model's output into the 8-bit HWC frame on the device,
+  * ``resize_bicubic`` is PIL's 8-bit ``Image.resize(..., BICUBIC)`` on the device, byte for byte (csrc/bicubic.hip): the reference's baseline
+    frames (test_video.py:241), and ``export_y_bicubic`` puts that frame's chroma under a y_only model's luma in the same launch,
   * ``HostStreamer`` moves only those 8-bit tensors over PCIe and downloads frame i - 1 on a stream of its own while frame i computes,
 
 so that a 180 x 320 frame costs 11.3 MB of transfers instead of 92.8 MB (``pcie_bytes``).  ``python -m crfp_amd.frameio`` times the four ways
@@ -88,6 +90,57 @@ def export(sr, chroma=None, bgr: bool = False, out=None):
     return out
 
 
+def _workspace(n: int, h: int, w: int, H: int, W: int, device, what: str) -> torch.Tensor:
+    nbytes = _lib.lib().crfp_resize_bicubic_workspace_bytes(n, h, w, H, W)
+    if nbytes == 0:
+        raise ValueError(f"crfp_amd.frameio.{what}: {n} frames {h}x{w} -> {H}x{W} are outside what the bicubic kernels take")
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def resize_bicubic(src_u8, H: int, W: int, out: str = "u8", bgr: bool = False):
+    """src_u8 [n,h,w,3] uint8 on the device -> PIL's ``Image.resize((W, H), Image.BICUBIC)`` of every frame, byte for byte: uint8 [n,H,W,3]
+    (out="u8"), or those bytes / 255 as fp32 [n,3,H,W] RGB planes (out="f32"; bgr: src_u8 is B,G,R per pixel, and so is a uint8 result).  Any
+    sizes >= 1, shrinking included.  One call on the current stream, nothing synchronised, no host copy: it can be captured in a graph."""
+    if out not in ("u8", "f32"):
+        raise ValueError(f"crfp_amd.frameio.resize_bicubic: out must be 'u8' or 'f32', got {out!r}")
+    src_u8 = _dev_as(src_u8, "src_u8", torch.uint8, (None, None, 3))
+    n, h, w = src_u8.shape[:3]
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"crfp_amd.frameio.resize_bicubic: H and W must be >= 1, got {H}, {W}")
+    with _on(src_u8):
+        ws = _workspace(n, h, w, H, W, src_u8.device, "resize_bicubic")
+        dst = (torch.empty((n, H, W, 3), dtype=torch.uint8, device=src_u8.device) if out == "u8" else
+               torch.empty((n, 3, H, W), dtype=torch.float32, device=src_u8.device))
+        flags = (_lib.IO_BGR if bgr else 0) | (_lib.IO_OUT_F32 if out == "f32" else 0)
+        _lib.check(_lib.lib().crfp_resize_bicubic_u8(src_u8.data_ptr(), dst.data_ptr(), n, h, w, H, W, flags, ws.data_ptr(), ws.numel(), _stream()),
+                   "crfp_resize_bicubic_u8")
+    return dst
+
+
+def export_y_bicubic(luma, lr_u8, bgr: bool = False, out=None):
+    """A y_only model's display frame as the reference makes it (test_video.py:396-410): luma [n,1,H,W] fp32 and the 8-bit LR frame lr_u8
+    [n,h,w,3], both on the device -> uint8 [n,H,W,3] = ``export(luma, chroma=resize_bicubic(lr_u8, H, W, "f32"))`` in one launch that never
+    writes the chroma frame.  H >= h and W >= w.  bgr: lr_u8 and the result are B,G,R per pixel.  out: a contiguous uint8 [n,H,W,3] device
+    tensor to fill.  (``export`` keeps its four arguments; this is its c = 1 form on an 8-bit LR frame.)"""
+    luma = _dev_as(luma, "luma", torch.float32, (1, None, None))
+    n, _, H, W = luma.shape
+    lr_u8 = _dev_as(lr_u8, "lr_u8", torch.uint8, (None, None, 3))
+    if lr_u8.shape[0] != n:
+        raise ValueError(f"crfp_amd.frameio.export_y_bicubic: lr_u8 holds {lr_u8.shape[0]} frames, luma {n}")
+    h, w = lr_u8.shape[1:3]
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=luma.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (n, H, W, 3) and out.is_contiguous()):
+        raise ValueError(f"crfp_amd.frameio.export_y_bicubic: `out` must be a contiguous uint8 device tensor [{n},{H},{W},3]")
+    with _on(luma, lr_u8, out):
+        ws = _workspace(n, h, w, H, W, luma.device, "export_y_bicubic")
+        _lib.check(_lib.lib().crfp_frame_export_y_bicubic_u8(luma.data_ptr(), lr_u8.data_ptr(), out.data_ptr(), n, h, w, H, W,
+                                                            _lib.IO_BGR if bgr else 0, ws.data_ptr(), ws.numel(), _stream()),
+                   "crfp_frame_export_y_bicubic_u8")
+    return out
+
+
 def pcie_bytes(h: int, w: int, fv_size: int, out_channels: int = 3) -> dict:
     """Bytes over PCIe per streamed frame, from shapes: the fp32 API tensors (lr, fv, mk up; the output down) against the 8-bit ones (LR frame,
     fovea crop, rectangle up; the HWC frame down)."""
@@ -96,10 +149,13 @@ def pcie_bytes(h: int, w: int, fv_size: int, out_channels: int = 3) -> dict:
             "u8": 3 * h * w + 3 * fv_size * fv_size + 4 * _lib.IO_RECT_INTS + 3 * H * W}
 
 
-def _model_frame(model, lr, fv, mk, bgr: bool, y_only: bool):
-    """One frame through a one-frame-per-call model and the export kernel: lr [1,3,h,w], fv [1,3,H,W], mk [1,1,H,W] -> uint8 [1,H,W,3]."""
+def _model_frame(model, lr, fv, mk, bgr: bool, y_only: bool, lr_u8=None):
+    """One frame through a one-frame-per-call model and the export kernel: lr [1,3,h,w], fv [1,3,H,W], mk [1,1,H,W] -> uint8 [1,H,W,3].  A
+    y_only model's chroma: the bicubic frame of lr_u8 [1,h,w,3] when that is given, else the bilinear x8 frame of lr."""
     sr = model(lrs=lr.unsqueeze(0), fvs=fv.unsqueeze(0), mks=mk.unsqueeze(0), fgs=None)
     sr = sr.reshape(1, -1, fv.shape[2], fv.shape[3])
+    if y_only and lr_u8 is not None:
+        return export_y_bicubic(sr, lr_u8, bgr=bgr)
     return export(sr, upsample_bilinear(lr, scale_factor=8) if y_only else None, bgr=bgr)
 
 
@@ -113,10 +169,13 @@ class HostStreamer:
     section 3.7): the process then holds five streams -- the default one, three here and the library's side stream -- on four hardware queues,
     the download and the side stream share one, and every frame's side work waits behind an 11 MB copy.  `depth` staging slots per direction:
     at most `depth` frames may be queued and not yet fetched.  The output handed to the download stream gets ``record_stream``.  A y_only
-    model's chroma is the bilinear x8 LR frame (``ops.upsample_bilinear``).  The model's ``inputs_resident`` must stay off: the ingest kernel
+    model's chroma is the bilinear x8 LR frame (``ops.upsample_bilinear``), or with chroma="bicubic" the reference's: PIL's bicubic resize of
+    the staged 8-bit LR frame, merged in the export launch (``export_y_bicubic``).  The model's ``inputs_resident`` must stay off: the ingest kernel
     that writes its inputs runs on the compute stream right in front of it, which is what that promise excludes."""
 
-    def __init__(self, model, h: int, w: int, fv_size: int, depth: int = 2, bgr: bool = False, device=None):
+    def __init__(self, model, h: int, w: int, fv_size: int, depth: int = 2, bgr: bool = False, device=None, chroma: str = "bilinear"):
+        if chroma not in ("bilinear", "bicubic"):
+            raise ValueError(f"crfp_amd.frameio.HostStreamer: chroma must be 'bilinear' or 'bicubic', got {chroma!r}")
         if depth < 1:
             raise ValueError("crfp_amd.frameio.HostStreamer: depth must be >= 1")
         if getattr(model, "inputs_resident", False):
@@ -127,6 +186,7 @@ class HostStreamer:
         self.model, self.h, self.w, self.fv, self.depth, self.bgr, self.dev = model, h, w, fv_size, depth, bool(bgr), device
         self.H, self.W = 8 * h, 8 * w
         self.y_only = bool(getattr(model, "y_only", False))
+        self.chroma = chroma
         # one upload per frame: the rectangle, then the LR frame, then the crop (each 4-byte aligned)
         self._o_lr = 4 * _lib.IO_RECT_INTS
         self._o_crop = self._o_lr + (3 * h * w + 3) // 4 * 4
@@ -172,10 +232,11 @@ class HostStreamer:
                 staged = pin.to(self.dev, non_blocking=True)
                 self._uploaded[slot].record(self._comp)
                 self._used[slot] = True
-                lr, fv, mk = ingest(staged[self._o_lr:self._o_lr + 3 * self.h * self.w].view(1, self.h, self.w, 3),
+                lr_u8 = staged[self._o_lr:self._o_lr + 3 * self.h * self.w].view(1, self.h, self.w, 3)
+                lr, fv, mk = ingest(lr_u8,
                                     staged[self._o_crop:].view(1, self.fv, self.fv, 3), staged[:self._o_lr].view(torch.int32).view(1, -1),
                                     self.H, self.W, bgr=self.bgr)
-                out = _model_frame(self.model, lr, fv, mk, self.bgr, self.y_only)
+                out = _model_frame(self.model, lr, fv, mk, self.bgr, self.y_only, lr_u8 if self.chroma == "bicubic" else None)
                 self._computed[slot].record(self._comp)
             out.record_stream(self._down)
             with torch.cuda.stream(self._down):

@@ -268,7 +268,10 @@ def main(argv=None):
     ap.add_argument("--cra", action="store_true",
                     help="with --model-code 18: MRCF_simple_v18_cra, the streaming form of the cross-resolution wiring CRFP_DSV_CRA")
     ap.add_argument("--score-maps", action="store_true",
-                    help="also time the stream with the per-window score maps of the output and of the bilinear x8 baseline")
+                    help="also time the stream with the per-window score maps of the output and of the x8 baseline (--baseline)")
+    ap.add_argument("--baseline", choices=("bilinear", "bicubic"), default="bilinear",
+                    help="the baseline frame of --score-maps: the bilinear x8 frame, or the rig's own (PIL's 8-bit bicubic resize of the 8-bit LR "
+                         "frame, / 255: frameio.resize_bicubic)")
     ap.add_argument("--fused-metrics", action="store_true",
                     help="also time the stream with the four regions of a frame scored by one fused call and fetched once at the end")
     ap.add_argument("--fused-masks", action="store_true",
@@ -312,8 +315,13 @@ def main(argv=None):
     dt_model = time.perf_counter() - t0
     res.pop("per_frame"); res.pop("trajectory")
     extra = {}
-    if a.score_maps:   # the same stream once more with both score maps per frame; the baseline is the bilinear x8 frame, unclamped
-        base = F.interpolate(lr, scale_factor=8, mode="bilinear", align_corners=False)
+    if a.score_maps:   # the same stream once more with both score maps per frame; the baseline is the bilinear x8 frame, unclamped, or ...
+        if a.baseline == "bicubic":   # ... test_video.py:241 on the device: the 8-bit LR frames through PIL's bicubic, as fractions of 255
+            from . import frameio
+            lr_u8 = torch.from_numpy(np.ascontiguousarray(np.rint(lrs * 255.0).astype(np.uint8).transpose(0, 2, 3, 1))).to(dev)
+            base = frameio.resize_bicubic(lr_u8, 8 * a.lr_h, 8 * a.lr_w, out="f32")
+        else:
+            base = F.interpolate(lr, scale_factor=8, mode="bilinear", align_corners=False)
         run_gaze_video(m, lr[:3], gt[:3], a.sigma, a.fv_size, a.seed, score_maps=True, baseline=base[:3])   # warm-up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -322,6 +330,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         extra["frames_per_sec_with_score_maps"] = a.frames / (time.perf_counter() - t0)
         extra["score_extrema"] = [float(v) for v in sm["score_extrema"].cpu()]
+        extra["baseline"] = a.baseline
     if a.fused_metrics:
         run_gaze_video(m, lr[:3], gt[:3], a.sigma, a.fv_size, a.seed, fused_metrics=True)   # warm-up
         torch.cuda.synchronize()

@@ -245,6 +245,40 @@ int crfp_frame_ingest_u8(const uint8_t* lr_u8, const uint8_t* crop_u8, const int
                          int fh, int fw, int H, int W, int flags, void* stream);
 int crfp_frame_export_u8(const float* sr, const float* chroma, uint8_t* out_u8, int n, int c, int H, int W, int flags, void* stream);
 
+/* Bicubic resize of 8-bit frames, byte for byte what PIL's Image.resize(..., BICUBIC) gives on an 8-bit RGB image (the reference's baseline and
+ * y_only chroma frames: test_video.py:241,396-402, dataset/reds.py:281,394,480, trainer.py:331-335).  Integer arithmetic on bytes; only the tap
+ * tables are computed in IEEE double.  Per axis with input size I and output size O: scale = I / O, fs = max(scale, 1), support = 2 fs,
+ * ksize = (int)ceil(support) * 2 + 1; for output index xx: center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0),
+ * cnt = min((int)(center + support + 0.5), I) - xmin, w[x] = f((x + xmin - center + 0.5) / fs) for x < cnt with the a = -0.5 cubic f, divided by
+ * their sum in index order unless that is 0, k[x] = (int)(w[x] * 4194304 -+ 0.5) (truncating, sign of w[x]).  A pixel is
+ * clamp(((1 << 21) + sum over x < cnt of byte[xmin + x] * k[x]) >> 22, 0, 255) in 32-bit ints with an arithmetic shift.  An image is resampled
+ * along x into an 8-bit image [h,W], then along y; channels are independent.  (PIL skips an axis whose size does not change; the taps of such
+ * an axis are the identity, so the bytes are the same.)
+ * crfp_bicubic_taps: the tables of one axis on the HOST (no GPU call), from the function the device runs: bounds[2 xx] = xmin, bounds[2 xx + 1]
+ * = cnt, taps[ksize xx + x] = k[x], zero for x >= cnt.  Returns ksize; CRFP_E_BADARG for a null pointer or a size < 1, CRFP_E_UNSUPPORTED when
+ * ksize * out_size does not fit an int, CRFP_E_WORKSPACE when taps_capacity (in ints) < ksize * out_size.
+ * crfp_resize_bicubic_u8: src [n,h,w,3] bytes -> dst [n,H,W,3] bytes, or with CRFP_IO_OUT_F32 dst [n,3,H,W] fp32 = (float)byte / 255.0f (IEEE
+ * division) of that byte.  crfp_frame_export_y_bicubic_u8: a y_only model's display frame without the fp32 chroma frame -- luma [n,1,H,W] fp32
+ * and the LR frame lr_u8 [n,h,w,3] -> out_u8 [n,H,W,3], equal to crfp_frame_export_u8 with c = 1 on chroma = the resized LR frame's bytes / 255.
+ * CRFP_IO_BGR: the 8-bit input and the 8-bit output are B,G,R per pixel (the fp32 planes are R,G,B).
+ * One call is a table kernel (both axes, one thread per output row or column, into the workspace: no host copy, no synchronisation, so the call
+ * can be captured in a graph) and then either one fused launch -- taken when H >= h and W >= w: a workgroup stages the input patch of its 32 x 64
+ * output tile in LDS, resamples it along x into LDS and along y into its epilogue (bytes, fp32 planes, or the y_only merge) -- or, for any
+ * other geometry, for CRFP_IO_TWO_PASS and for plain resizes only, a kernel along x into an 8-bit image in the workspace and one along y.  The
+ * merge exists on the fused path only: another geometry is CRFP_E_UNSUPPORTED and nothing is written.  The workspace (any contents, 16-byte
+ * aligned) begins with the tables as int32: bounds of x [2 W], taps of x [ksize_x W], bounds of y [2 H], taps of y [ksize_y H].  Every output
+ * byte is written exactly once; no atomics; 4-pixel stores when W % 4 == 0, the fp32 pointers are 16-byte and the byte output 4-byte aligned,
+ * one-pixel stores otherwise.  Errors before any HIP call: null pointer, size < 1, unknown flag bits (CRFP_E_BADARG); a short or missing
+ * workspace (CRFP_E_WORKSPACE); n > 65535, tables beyond an int or a frame beyond the launch grid (CRFP_E_UNSUPPORTED; the size query gives 0). */
+#define CRFP_IO_OUT_F32 2  /* crfp_resize_bicubic_u8: dst is fp32 planar [n,3,H,W] instead of bytes [n,H,W,3] */
+#define CRFP_IO_TWO_PASS 4 /* crfp_resize_bicubic_u8: take the two-pass path whatever the geometry (A/B and tests) */
+int crfp_bicubic_taps(int in_size, int out_size, int32_t* bounds, int32_t* taps, int taps_capacity);
+size_t crfp_resize_bicubic_workspace_bytes(int n, int h, int w, int H, int W);
+int crfp_resize_bicubic_u8(const uint8_t* src, void* dst, int n, int h, int w, int H, int W, int flags, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int crfp_frame_export_y_bicubic_u8(const float* luma, const uint8_t* lr_u8, uint8_t* out_u8, int n, int h, int w, int H, int W, int flags,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CRFP_DSV engine (mid_channels=32, hr_dcn=True, offset_prop=True; y_only selectable).
  * Parameters arrive as CRFP_DSV_NUM_PARAMS device pointers in the order of the reference's
  * state_dict (weight then bias of each conv, list in crfp_dsv_param_name). */

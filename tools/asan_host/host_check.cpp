@@ -260,6 +260,73 @@ int main() {
                 }
         EXPECT(crfp_stub_launches() == l0 + launches);
     }
+    // the bicubic resize: the host tap tables into exactly sized heap blocks (one int short is refused and nothing is written), sizing, every
+    // refusal before the first launch; an accepted resize is the table kernel plus one fused launch or two passes, a merge table + fused
+    {
+        const int axes[][2] = {{1, 8}, {180, 1440}, {96, 12}};
+        for (const auto& ax : axes) {
+            const int in = ax[0], out = ax[1], ks = in > out ? 33 : 5;   // 96 -> 12: support 16
+            int32_t* bounds = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * 2 * out));
+            int32_t* taps = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * ks * out));
+            int32_t* small = static_cast<int32_t*>(std::malloc(sizeof(int32_t) * (ks * out - 1)));
+            EXPECT(crfp_bicubic_taps(in, out, bounds, small, ks * out - 1) == CRFP_E_WORKSPACE);   // a capacity one too small
+            EXPECT(crfp_bicubic_taps(in, out, bounds, taps, ks * out) == ks);
+            for (int xx = 0; xx < out; ++xx) {
+                const int x0 = bounds[2 * xx], cnt = bounds[2 * xx + 1];
+                long long sum = 0;
+                for (int k = 0; k < ks; ++k) sum += taps[ks * xx + k];
+                EXPECT(x0 >= 0 && cnt >= 1 && cnt <= ks && x0 + cnt <= in);
+                EXPECT(sum > (1 << 22) - ks && sum < (1 << 22) + ks);       // normalised taps, each rounded once
+                for (int k = cnt; k < ks; ++k) EXPECT(taps[ks * xx + k] == 0);
+            }
+            std::free(bounds); std::free(taps); std::free(small);
+        }
+        int32_t b2[2], k5[5];
+        EXPECT(crfp_bicubic_taps(1, 1, nullptr, k5, 5) == CRFP_E_BADARG && crfp_bicubic_taps(1, 1, b2, nullptr, 5) == CRFP_E_BADARG);
+        EXPECT(crfp_bicubic_taps(0, 1, b2, k5, 5) == CRFP_E_BADARG && crfp_bicubic_taps(1, -1, b2, k5, 5) == CRFP_E_BADARG);
+        EXPECT(crfp_bicubic_taps(2147483647, 1, b2, k5, 5) == CRFP_E_UNSUPPORTED && crfp_bicubic_taps(2147483647, 2147483647, b2, k5, 5) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_bicubic_taps(1, 1, b2, k5, 5) == 5 && b2[0] == 0 && b2[1] == 1 && k5[0] == 1 << 22);
+        uint8_t* const k16 = reinterpret_cast<uint8_t*>(16);
+        const uint8_t* const c16 = reinterpret_cast<const uint8_t*>(16);
+        const size_t need = crfp_resize_bicubic_workspace_bytes(2, 180, 320, 1440, 2560);
+        EXPECT(need == 4ull * 7 * (1440 + 2560) + 2ull * 180 * 2560 * 3);
+        EXPECT(crfp_resize_bicubic_workspace_bytes(0, 8, 8, 8, 8) == 0 && crfp_resize_bicubic_workspace_bytes(1, 8, 0, 8, 8) == 0);
+        EXPECT(crfp_resize_bicubic_workspace_bytes(70000, 8, 8, 8, 8) == 0 && crfp_resize_bicubic_workspace_bytes(1, 2147483647, 8, 1, 8) == 0);
+        EXPECT(crfp_resize_bicubic_workspace_bytes(1, 2147483647, 2147483647, 2147483647, 2147483647) == 0);
+        const long l0 = crfp_stub_launches();
+        EXPECT(crfp_resize_bicubic_u8(nullptr, k16, 2, 180, 320, 1440, 2560, 0, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_resize_bicubic_u8(c16, nullptr, 2, 180, 320, 1440, 2560, 0, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_resize_bicubic_u8(c16, k16, 2, 0, 320, 1440, 2560, 0, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_resize_bicubic_u8(c16, k16, 2, 180, 320, 1440, 2560, 8, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "unknown flags") != nullptr);
+        EXPECT(crfp_resize_bicubic_u8(c16, k16, 2, 180, 320, 1440, 2560, 0, k16, need - 1, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_resize_bicubic_u8(c16, k16, 2, 180, 320, 1440, 2560, 0, nullptr, need, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_resize_bicubic_u8(c16, k16, 2, 180, 320, 1440, 2560, 0, reinterpret_cast<void*>(20), need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_resize_bicubic_u8(c16, k16, 70000, 180, 320, 1440, 2560, 0, k16, (size_t)1 << 44, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_frame_export_y_bicubic_u8(nullptr, c16, k16, 2, 180, 320, 1440, 2560, 0, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_y_bicubic_u8(p16, nullptr, k16, 2, 180, 320, 1440, 2560, 0, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_y_bicubic_u8(p16, c16, nullptr, 2, 180, 320, 1440, 2560, 0, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_y_bicubic_u8(p16, c16, k16, 2, 180, 320, 1440, 2560, CRFP_IO_OUT_F32, k16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_frame_export_y_bicubic_u8(p16, c16, k16, 2, 180, 320, 1440, 2560, 0, k16, need - 1, nullptr) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_frame_export_y_bicubic_u8(p16, c16, k16, 2, 180, 320, 179, 2560, 0, k16, (size_t)1 << 40, nullptr) == CRFP_E_UNSUPPORTED);   // shrinks along y
+        EXPECT(std::strstr(crfp_last_error_string(), "fused path") != nullptr);
+        EXPECT(crfp_stub_launches() == l0);
+        long launches = 0;
+        for (const auto& g : {std::initializer_list<int>{1, 1, 8, 8}, {17, 23, 136, 184}, {9, 11, 10, 13}, {64, 96, 8, 12}, {180, 320, 1440, 2560}})
+            for (int flags : {0, CRFP_IO_BGR, CRFP_IO_OUT_F32, CRFP_IO_OUT_F32 | CRFP_IO_BGR | CRFP_IO_TWO_PASS})
+                for (uint8_t* d : {k16, reinterpret_cast<uint8_t*>(17)}) {   // aligned and not: both kernel forms
+                    const int h = g.begin()[0], w = g.begin()[1], H = g.begin()[2], W = g.begin()[3];
+                    const size_t ws = crfp_resize_bicubic_workspace_bytes(2, h, w, H, W);
+                    const bool fused = H >= h && W >= w;
+                    EXPECT(ws > 0 && crfp_resize_bicubic_u8(c16, d, 2, h, w, H, W, flags, k16, ws, nullptr) == 0);
+                    launches += fused && !(flags & CRFP_IO_TWO_PASS) ? 2 : 3;
+                    if (fused && !(flags & ~CRFP_IO_BGR)) {
+                        EXPECT(crfp_frame_export_y_bicubic_u8(p16, c16, d, 2, h, w, H, W, flags, k16, ws, nullptr) == 0);
+                        launches += 2;
+                    }
+                }
+        EXPECT(crfp_stub_launches() == l0 + launches);
+    }
     // the conv probe (test hook): sizing, the launcher's kernel-selection rule, every refusal before the first launch, whole calls on the stub
     {
         crfp_probe_conv q;
