@@ -70,6 +70,35 @@ int crfp_dcnv2_forward_f32(const float* x, const float* offset, const float* mas
     return launch_dcn_generic(x, offset, mask, weight, bias, out, n, cin, cout, h, w, dg, s);
 }
 
+// ---- DCNv2 backward (dcn_backward.hip): the forward's domain up to 64 channels, every argument error before any HIP call
+static int dcnv2_backward_domain(int n, int cin, int cout, int h, int w, int k, int pad, int dil, int dg) {
+    if (n < 1 || cin < 1 || cout < 1 || h < 1 || w < 1 || dg < 1) { set_error("dcnv2_backward: bad argument (need n, cin, cout, h, w, dg >= 1)"); return CRFP_E_BADARG; }
+    if (k != 3 || pad != 1 || dil != 1) { set_error("dcnv2_backward: only kernel 3, padding 1, dilation 1 (got %d,%d,%d)", k, pad, dil); return CRFP_E_UNSUPPORTED; }
+    if (cin % dg != 0) { set_error("dcnv2_backward: cin %d not divisible by deformable_groups %d", cin, dg); return CRFP_E_UNSUPPORTED; }
+    if (!dcn_backward_shape_ok(n, cin, cout, h, w, dg)) {
+        set_error("dcnv2_backward: up to 64 channels, 65535 images, 262140 rows and 2^58 tensor elements (got cin %d, cout %d, n %d, h %d, w %d)", cin, cout, n, h, w);
+        return CRFP_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+size_t crfp_dcnv2_backward_workspace_bytes(int n, int cin, int cout, int h, int w, int k, int dg) {
+    if (dcnv2_backward_domain(n, cin, cout, h, w, k, 1, 1, dg)) return 0;
+    return dcn_backward_workspace_bytes(n, cin, cout, h, w, dg);
+}
+
+int crfp_dcnv2_backward_f32(const float* x, const float* offset, const float* mask, const float* weight, const float* grad_out,
+                            float* grad_x, float* grad_offset, float* grad_mask, float* grad_weight, float* grad_bias,
+                            int n, int cin, int cout, int h, int w, int k, int pad, int dil, int dg,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !offset || !mask || !weight || !grad_out) { set_error("dcnv2_backward: null pointer (x, offset, mask, weight and grad_out are required)"); return CRFP_E_BADARG; }
+    if (!grad_x && !grad_offset && !grad_mask && !grad_weight && !grad_bias) { set_error("dcnv2_backward: all five outputs are null (nothing to do)"); return CRFP_E_BADARG; }
+    if (const int rc = dcnv2_backward_domain(n, cin, cout, h, w, k, pad, dil, dg)) return rc;
+    if (!workspace || workspace_bytes < dcn_backward_workspace_bytes(n, cin, cout, h, w, dg)) { set_error("dcnv2_backward: workspace too small"); return CRFP_E_WORKSPACE; }
+    return launch_dcn_backward(x, offset, mask, weight, grad_out, grad_x, grad_offset, grad_mask, grad_weight, grad_bias, n, cin, cout, h, w, dg,
+                               workspace, (hipStream_t)stream);
+}
+
 // ---- DCNv2 4 -> 4, one deformable group, ONE (dy, dx) and ONE mask per pixel shared by the 9 taps (the
 // `offset_mask_shared_across_taps` form).  The reference builds this by tiling the 2 + 1 channels 9x before the DCNv2 call
 // (model/CRFP.py:341-347); here they stay compact: offset [n,2,h,w], mask [n,1,h,w].

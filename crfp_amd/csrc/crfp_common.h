@@ -517,6 +517,11 @@ void bicubic_taps_host(int in, int out, int ksize, int* bounds, int* taps);
 size_t bicubic_workspace_bytes(int N, int h, int w, int H, int W);         // 0: outside what launch_bicubic takes
 int launch_bicubic(const uint8_t* src, void* dst, const float* luma, int N, int h, int w, int H, int W, int epi, int bgr, int two_pass,
                    void* workspace, hipStream_t s);
+// dcn_backward.hip (fp32 build only): the gradients of the DCNv2 operator; a null output is not computed
+bool dcn_backward_shape_ok(int n, int cin, int cout, int h, int w, int dg);             // what launch_dcn_backward takes
+size_t dcn_backward_workspace_bytes(int n, int cin, int cout, int h, int w, int dg);    // 0: outside it
+int launch_dcn_backward(const float* x, const float* offset, const float* mask, const float* weight, const float* go, float* gx, float* goff,
+                        float* gmask, float* gw, float* gb, int N, int cin, int cout, int H, int W, int dg, void* workspace, hipStream_t s);
 #endif
 
 }  // namespace CRFP_NS

@@ -1,6 +1,8 @@
 """Drop-in for the third-party ``dcn_v2`` package the reference imports (``from dcn_v2 import DCNv2``,
 reference model/CRFP.py:6, test_runtime.py:11): same constructor, same ``weight``/``bias`` parameters
-(which the reference mutates in place, model/CRFP.py:359-370), forward on the HIP kernels."""
+(which the reference mutates in place, model/CRFP.py:359-370), forward and backward on the HIP kernels: under grad mode with an input
+or parameter requiring grad the result carries a ``grad_fn`` (``ops.dcnv2``: fp32, first order, up to 64 channels), so the module trains
+inside the reference's own ``model/``; under ``no_grad`` it is the plain forward call."""
 import math
 
 import torch

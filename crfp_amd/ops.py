@@ -130,9 +130,20 @@ def flow_warp(x, flow, interpolation="bilinear", padding_mode="zeros", align_cor
 
 
 def dcnv2(x, offset, mask, weight, bias, kernel_size=3, padding=1, dilation=1, deformable_groups=1):
-    """Drop-in for ``dcn_v2.DCNv2.forward`` (reference model/CRFP.py:350)."""
+    """Drop-in for ``dcn_v2.DCNv2.forward`` (reference model/CRFP.py:350), forward and backward.  With grad mode on and at least one of
+    the five tensors requiring grad the result carries a ``grad_fn`` whose backward is crfp_dcnv2_backward_f32 (fp32, first order only;
+    grad_input is an unordered float atomic sum, the other four gradients are bitwise reproducible); otherwise this is the plain
+    forward call.  The other wrappers of this module (``dcnv2_shared``, ``dcnv2_g8_packed``, ``flow_warp``, ``conv3x3*``) are
+    forward-only."""
     x, offset, mask = _dev(x, "input"), _dev(offset, "offset"), _dev(mask, "mask")
     weight, bias = _dev(weight, "weight"), _dev(bias, "bias")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, offset, mask, weight, bias)):
+        return _DCNv2Function.apply(x, offset, mask, weight, bias, kernel_size, padding, dilation, deformable_groups)
+    return _dcnv2_forward(x, offset, mask, weight, bias, kernel_size, padding, dilation, deformable_groups)
+
+
+def _dcnv2_forward(x, offset, mask, weight, bias, kernel_size, padding, dilation, deformable_groups):
+    """crfp_dcnv2_forward_f32 on float32, contiguous device tensors."""
     n, cin, h, w = x.shape
     cout = weight.shape[0]
     K = kernel_size * kernel_size
@@ -150,6 +161,38 @@ def dcnv2(x, offset, mask, weight, bias, kernel_size=3, padding=1, dilation=1, d
                                             dilation, deformable_groups, ws.data_ptr(), ws.numel(), _stream()),
                    "crfp_dcnv2_forward_f32")
     return out
+
+
+class _DCNv2Function(torch.autograd.Function):
+    """``dcnv2`` under autograd: forward = ``_dcnv2_forward``, backward = crfp_dcnv2_backward_f32 with a NULL pointer for every gradient
+    ``ctx.needs_input_grad`` does not ask for."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, weight, bias, kernel_size, padding, dilation, deformable_groups):
+        ctx.save_for_backward(x, offset, mask, weight)
+        ctx.cfg = (kernel_size, padding, dilation, deformable_groups)
+        return _dcnv2_forward(x, offset, mask, weight, bias, kernel_size, padding, dilation, deformable_groups)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, offset, mask, weight = ctx.saved_tensors
+        k, pad, dil, dg = ctx.cfg
+        grad_out = _dev(grad_out, "grad_out")
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        L = _lib.lib()
+        with _on(x, offset, mask, weight, grad_out):
+            like = (x, offset, mask, weight)
+            grads = [torch.empty_like(t) if need else None for t, need in zip(like, ctx.needs_input_grad[:4])]
+            grads.append(torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[4] else None)
+            nb = L.crfp_dcnv2_backward_workspace_bytes(n, cin, cout, h, w, k, dg)
+            ws = _ws(nb, x.device)
+            _lib.check(L.crfp_dcnv2_backward_f32(x.data_ptr(), offset.data_ptr(), mask.data_ptr(), weight.data_ptr(), grad_out.data_ptr(),
+                                                 *(g.data_ptr() if g is not None else None for g in grads),
+                                                 n, cin, cout, h, w, k, pad, dil, dg, ws.data_ptr(), ws.numel(), _stream()),
+                       "crfp_dcnv2_backward_f32")
+        return (*grads, None, None, None, None)
 
 
 def dcnv2_shared(x, offset, mask, weight, bias):

@@ -25,6 +25,7 @@
  * Reference interfaces replaced (paths relative to the reference repo eugenelet/CRFP):
  *   crfp_flow_warp_f32        model/CRFP.py:90-130   flow_warp()  (ATen grid_sampler_2d underneath)
  *   crfp_dcnv2_forward_f32    model/CRFP.py:6,318-320,350  third-party dcn_v2.DCNv2.forward
+ *   crfp_dcnv2_backward_f32   the same extension's backward (autograd of self.dcn(pre_x, offset, mask), model/CRFP.py:350)
  *   crfp_conv3x3_f32          every nn.Conv2d(k=3,s=1,p=1) on the path (e.g. model/CRFP.py:48-50,303-317)
  *   crfp_upsample_bilinear_f32  nn.Upsample / F.interpolate(align_corners=False) (model/CRFP.py:808-812,1471-1478)
  *   crfp_fnet_*               model/CRFP.py:743-814  FNet.forward, :1483-1508 compute_flow
@@ -90,6 +91,30 @@ size_t crfp_dcnv2_workspace_bytes(int n, int cin, int cout, int h, int w, int k,
 int crfp_dcnv2_forward_f32(const float* x, const float* offset, const float* mask, const float* weight,
                            const float* bias, float* out, int n, int cin, int cout, int h, int w, int k,
                            int pad, int dil, int dg, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- DCNv2 backward: the gradients of crfp_dcnv2_forward_f32's out = bias + sum weight * mask * bilinear(x at offset) for a given
+ * grad_out[n,cout,h,w]: grad_x[n,cin,h,w], grad_offset[n,2*dg*9,h,w], grad_mask[n,dg*9,h,w], grad_weight[cout,cin,3,3], grad_bias[cout]
+ * (the bias itself is not an input: its gradient is the sum of grad_out).  The forward's semantics exactly: (dy, dx) interleaved per
+ * (group, tap), a sample counts only when -1 < py < h and -1 < px < w, each corner zero-padded on its own, the sample multiplied by the
+ * mask.  grad_offset is the derivative inside the bilinear cell the forward's floor picked (the right-hand derivative at integer
+ * positions); corners and samples the forward drops contribute exactly 0, and a NaN or infinite offset counts as outside.  Offsets are
+ * unbounded: every corner is checked before its 64-bit index is formed.
+ * Outputs: a NULL output pointer means "not wanted" and its work is skipped (no clear and no scatter for a NULL grad_x, no reduction
+ * pass when grad_weight and grad_bias are both NULL); all five NULL is CRFP_E_BADARG.  Every element of a wanted output is defined by
+ * the call: the caller initialises nothing (grad_x is cleared on `stream` by the call), and the workspace needs no initialisation.
+ * Domain: the forward's -- k = 3, pad = 1, dil = 1, cin % dg == 0 -- with cin, cout <= 64, (32, 32, dg 8) and (4, 4, dg 1) included;
+ * anything else (also n > 65535, h > 262140) is CRFP_E_UNSUPPORTED and the size query returns 0.  A null input or a size < 1 is
+ * CRFP_E_BADARG, a missing or short workspace CRFP_E_WORKSPACE; every argument error is returned before any HIP call.  Asynchronous
+ * on `stream`, no host synchronisation.
+ * Numbers: fp32 throughout (no split-fp16: gradients have no bounded range).  Determinism: grad_offset, grad_mask, grad_weight and
+ * grad_bias are bitwise reproducible from run to run (plain stores; grad_weight / grad_bias through per-workgroup partial slabs in the
+ * workspace added in a fixed order).  grad_x is NOT: it is a data-dependent scatter of float atomic adds, whose sum depends on the
+ * order in which the adds arrive, so its last bits can differ between runs. */
+size_t crfp_dcnv2_backward_workspace_bytes(int n, int cin, int cout, int h, int w, int k, int dg);
+int crfp_dcnv2_backward_f32(const float* x, const float* offset, const float* mask, const float* weight, const float* grad_out,
+                            float* grad_x, float* grad_offset, float* grad_mask, float* grad_weight, float* grad_bias,
+                            int n, int cin, int cout, int h, int w, int k, int pad, int dil, int dg,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- DCNv2 with ONE (dy, dx) and ONE mask per pixel shared by the 9 taps (cin = cout = 4, deformable_groups = 1): what
  * DCN_module(repeat=True) computes after tiling its 2 + 1 channels 9x (model/CRFP.py:341-347,350); the tiled tensors never exist.

@@ -327,6 +327,56 @@ int main() {
                 }
         EXPECT(crfp_stub_launches() == l0 + launches);
     }
+    // the DCNv2 backward: sizing, every refusal before the first launch, the launches each subset of wanted outputs takes
+    {
+        const size_t need = crfp_dcnv2_backward_workspace_bytes(2, 8, 6, 9, 11, 3, 2);
+        EXPECT(need > 0 && crfp_dcnv2_backward_workspace_bytes(1, 32, 32, 360, 640, 3, 8) > 0 && crfp_dcnv2_backward_workspace_bytes(1, 4, 4, 1440, 2560, 3, 1) > 0);
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(1, 64, 64, 8, 8, 3, 64) > crfp_dcnv2_backward_workspace_bytes(1, 64, 32, 8, 8, 3, 64));
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(0, 8, 6, 9, 11, 3, 2) == 0 && crfp_dcnv2_backward_workspace_bytes(2, 8, 6, 9, 11, 5, 2) == 0);
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(2, 8, 6, 9, 11, 3, 3) == 0 && crfp_dcnv2_backward_workspace_bytes(2, 65, 6, 9, 11, 3, 1) == 0);
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(2, 8, 66, 9, 11, 3, 2) == 0 && crfp_dcnv2_backward_workspace_bytes(2, 8, 6, 9, 11, 3, 0) == 0);
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(70000, 8, 6, 9, 11, 3, 2) == 0 && crfp_dcnv2_backward_workspace_bytes(1, 8, 6, 300000, 1, 3, 2) == 0);
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(65535, 64, 64, 262140, 2147483647, 3, 1) == 0);   // element counts beyond 64-bit indexing
+        EXPECT(crfp_dcnv2_backward_workspace_bytes(8, 64, 64, 4320, 7680, 3, 8) > 0 && crfp_dcnv2_backward_workspace_bytes(1, 1, 1, 262140, 100000, 3, 1) > 0);
+        const long l0 = crfp_stub_launches();
+#define DCNB(X, OFF, M, W, GO, GX, GOFF, GM, GW, GB, N, CIN, COUT, K, PAD, DIL, DG, WS, WSB) \
+    crfp_dcnv2_backward_f32(X, OFF, M, W, GO, GX, GOFF, GM, GW, GB, N, CIN, COUT, 9, 11, K, PAD, DIL, DG, WS, WSB, nullptr)
+        EXPECT(DCNB(nullptr, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(DCNB(p16, nullptr, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNB(p16, p16, nullptr, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNB(p16, p16, p16, nullptr, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNB(p16, p16, p16, p16, nullptr, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, nullptr, 2, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "nothing to do") != nullptr);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 0, 8, 6, 3, 1, 1, 2, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 0, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 5, 2, 1, 2, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "kernel 3") != nullptr);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 0, 1, 2, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 2, 2, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 3, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "deformable_groups") != nullptr);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 65, 6, 3, 1, 1, 1, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 128, 3, 1, 1, 2, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 70000, 8, 6, 3, 1, 1, 2, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need - 1) == CRFP_E_WORKSPACE);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, nullptr, need) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_stub_launches() == l0);
+        // weight transpose + pixel kernel when grad_x, grad_offset or grad_mask is wanted; slab pass + slab sum when grad_weight or grad_bias is
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == 0 && crfp_stub_launches() == l0 + 4);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, 2, 8, 6, 3, 1, 1, 2, p16, need) == 0 && crfp_stub_launches() == l0 + 6);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, nullptr, p16, p16, nullptr, nullptr, 2, 8, 6, 3, 1, 1, 2, p16, need) == 0 && crfp_stub_launches() == l0 + 8);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, p16, nullptr, 2, 8, 6, 3, 1, 1, 2, p16, need) == 0 && crfp_stub_launches() == l0 + 10);
+        EXPECT(DCNB(p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, p16, 2, 8, 6, 3, 1, 1, 2, p16, need) == 0 && crfp_stub_launches() == l0 + 12);
+#undef DCNB
+        for (const auto& g : {std::initializer_list<int>{1, 32, 32, 8, 360, 640}, {1, 4, 4, 1, 1440, 2560}, {3, 64, 64, 64, 1, 1}, {2, 33, 7, 11, 5, 300}}) {
+            const int n = g.begin()[0], ci = g.begin()[1], co = g.begin()[2], dg = g.begin()[3], h = g.begin()[4], w = g.begin()[5];
+            const size_t ws = crfp_dcnv2_backward_workspace_bytes(n, ci, co, h, w, 3, dg);
+            EXPECT(ws > 0 && crfp_dcnv2_backward_f32(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, n, ci, co, h, w, 3, 1, 1, dg, p16, ws, nullptr) == 0);
+        }
+        EXPECT(crfp_stub_launches() == l0 + 12 + 4 * 4);
+    }
     // the conv probe (test hook): sizing, the launcher's kernel-selection rule, every refusal before the first launch, whole calls on the stub
     {
         crfp_probe_conv q;
