@@ -96,7 +96,74 @@ int crfp_dcnv2_backward_f32(const float* x, const float* offset, const float* ma
     if (const int rc = dcnv2_backward_domain(n, cin, cout, h, w, k, pad, dil, dg)) return rc;
     if (!workspace || workspace_bytes < dcn_backward_workspace_bytes(n, cin, cout, h, w, dg)) { set_error("dcnv2_backward: workspace too small"); return CRFP_E_WORKSPACE; }
     return launch_dcn_backward(x, offset, mask, weight, grad_out, grad_x, grad_offset, grad_mask, grad_weight, grad_bias, n, cin, cout, h, w, dg,
+                               0, workspace, (hipStream_t)stream);
+}
+
+// ---- the backward of crfp_dcnv2_shared_f32 (dcn_backward.hip in its shared form): 4 -> 4 only, the compact offset / mask and their gradients
+static int dcnv2_shared_backward_domain(int n, int cin, int cout, int h, int w) {
+    if (n < 1 || cin < 1 || cout < 1 || h < 1 || w < 1) { set_error("dcnv2_shared_backward: bad argument (need n, cin, cout, h, w >= 1)"); return CRFP_E_BADARG; }
+    if (cin != 4 || cout != 4) { set_error("dcnv2_shared_backward: the shared-offset form is built for 4 -> 4 channels (got %d -> %d)", cin, cout); return CRFP_E_UNSUPPORTED; }
+    if (!dcn_backward_shape_ok(n, 4, 4, h, w, 1)) {
+        set_error("dcnv2_shared_backward: up to 65535 images, 262140 rows and 2^58 tensor elements (got n %d, h %d, w %d)", n, h, w);
+        return CRFP_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+size_t crfp_dcnv2_shared_backward_workspace_bytes(int n, int c, int h, int w) {
+    if (dcnv2_shared_backward_domain(n, c, c, h, w)) return 0;
+    return dcn_backward_workspace_bytes(n, 4, 4, h, w, 1);
+}
+
+int crfp_dcnv2_shared_backward_f32(const float* x, const float* offset, const float* mask, const float* weight, const float* grad_out,
+                                   float* grad_x, float* grad_offset, float* grad_mask, float* grad_weight, float* grad_bias,
+                                   int n, int cin, int cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!x || !offset || !mask || !weight || !grad_out) { set_error("dcnv2_shared_backward: null pointer (x, offset, mask, weight and grad_out are required)"); return CRFP_E_BADARG; }
+    if (!grad_x && !grad_offset && !grad_mask && !grad_weight && !grad_bias) { set_error("dcnv2_shared_backward: all five outputs are null (nothing to do)"); return CRFP_E_BADARG; }
+    if (const int rc = dcnv2_shared_backward_domain(n, cin, cout, h, w)) return rc;
+    if (!workspace || workspace_bytes < dcn_backward_workspace_bytes(n, 4, 4, h, w, 1)) { set_error("dcnv2_shared_backward: workspace too small"); return CRFP_E_WORKSPACE; }
+    return launch_dcn_backward(x, offset, mask, weight, grad_out, grad_x, grad_offset, grad_mask, grad_weight, grad_bias, n, 4, 4, h, w, 1, 1,
                                workspace, (hipStream_t)stream);
+}
+
+// ---- flow_warp backward (warp_backward.hip): every argument error before any HIP call
+static int flow_warp_backward_domain(int n, int c, int h, int w, int padding_mode) {
+    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("flow_warp_backward: bad argument (need n, c, h, w >= 1)"); return CRFP_E_BADARG; }
+    if (padding_mode != CRFP_PAD_ZEROS && padding_mode != CRFP_PAD_BORDER) { set_error("flow_warp_backward: padding_mode %d unsupported", padding_mode); return CRFP_E_UNSUPPORTED; }
+    if (!flow_warp_backward_shape_ok(n, c, h, w)) {
+        set_error("flow_warp_backward: up to 65535 images, 262140 rows, 2^30 columns and 2^58 tensor elements (got n %d, c %d, h %d, w %d)", n, c, h, w);
+        return CRFP_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+// the kernel needs no scratch; one aligned unit is reserved so that the call has the shape of every other one (query, allocate, pass)
+size_t crfp_flow_warp_backward_workspace_bytes(int n, int c, int h, int w) {
+    if (flow_warp_backward_domain(n, c, h, w, CRFP_PAD_ZEROS)) return 0;
+    return 256;
+}
+
+static int flow_warp_backward_call(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow, int n, int c, int h,
+                                   int w, int padding_mode, int displaced, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!flow || !grad_out) { set_error("flow_warp_backward: null pointer (flow and grad_out are required)"); return CRFP_E_BADARG; }
+    if (!grad_x && !grad_flow) { set_error("flow_warp_backward: both outputs are null (nothing to do)"); return CRFP_E_BADARG; }
+    if (grad_flow && !x) { set_error("flow_warp_backward: null pointer (x is required for grad_flow)"); return CRFP_E_BADARG; }
+    if (const int rc = flow_warp_backward_domain(n, c, h, w, padding_mode)) return rc;
+    if (!workspace || workspace_bytes < 256) { set_error("flow_warp_backward: workspace too small"); return CRFP_E_WORKSPACE; }
+    return launch_flow_warp_backward(x, flow, grad_out, grad_x, grad_flow, n, c, h, w, padding_mode == CRFP_PAD_BORDER, displaced, (hipStream_t)stream);
+}
+
+int crfp_flow_warp_backward_f32(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow,
+                                int n, int c, int h, int w, int padding_mode, void* workspace, size_t workspace_bytes, void* stream) {
+    return flow_warp_backward_call(x, flow, grad_out, grad_x, grad_flow, n, c, h, w, padding_mode, 1, workspace, workspace_bytes, stream);
+}
+
+// measurement hook (tools/warp_backward_time.py): the same call with the LDS window of grad_x on the undisplaced tile (window = 0)
+int crfp_flow_warp_backward_window_f32(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow,
+                                       int n, int c, int h, int w, int padding_mode, int window, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    if (window != 0 && window != 1) { set_error("flow_warp_backward: window %d (0: on the tile, 1: displaced by the centre flow)", window); return CRFP_E_BADARG; }
+    return flow_warp_backward_call(x, flow, grad_out, grad_x, grad_flow, n, c, h, w, padding_mode, window, workspace, workspace_bytes, stream);
 }
 
 // ---- DCNv2 4 -> 4, one deformable group, ONE (dy, dx) and ONE mask per pixel shared by the 9 taps (the

@@ -521,7 +521,13 @@ int launch_bicubic(const uint8_t* src, void* dst, const float* luma, int N, int 
 bool dcn_backward_shape_ok(int n, int cin, int cout, int h, int w, int dg);             // what launch_dcn_backward takes
 size_t dcn_backward_workspace_bytes(int n, int cin, int cout, int h, int w, int dg);    // 0: outside it
 int launch_dcn_backward(const float* x, const float* offset, const float* mask, const float* weight, const float* go, float* gx, float* goff,
-                        float* gmask, float* gw, float* gb, int N, int cin, int cout, int H, int W, int dg, void* workspace, hipStream_t s);
+                        float* gmask, float* gw, float* gb, int N, int cin, int cout, int H, int W, int dg, int shared, void* workspace,
+                        hipStream_t s);   // shared: offset [n,2,h,w], mask [n,1,h,w] and their gradients, one per pixel for the 9 taps (4 -> 4, dg 1)
+// warp_backward.hip (fp32 build only): the gradients of flow_warp; a null output is not computed.  displaced: the LDS window of grad_x
+// follows the flow of the tile's centre pixel (the product) or stays on the tile (0: kept for measurement)
+bool flow_warp_backward_shape_ok(int n, int c, int h, int w);
+int launch_flow_warp_backward(const float* x, const float* flow, const float* go, float* gx, float* gflow, int N, int C, int H, int W,
+                              int border, int displaced, hipStream_t s);
 #endif
 
 }  // namespace CRFP_NS

@@ -20,6 +20,8 @@
 // Determinism: grad_offset, grad_mask, grad_weight and grad_bias are bitwise reproducible from run to run (fixed summation orders, no
 // atomics; J depends on the shape alone).  grad_x is NOT: a float atomic sum depends on the order in which the adds arrive.
 // All global indices are 64-bit; weight reads are wave-uniform.
+// The same kernels in their compile-time SHARED form are the backward of crfp_dcnv2_shared_f32 (4 -> 4, one (dy, dx) and one mask per
+// pixel for the 9 taps): grad_offset [n,2,h,w] and grad_mask [n,1,h,w] are the sums over the taps, formed in registers.
 #include "crfp_common.h"
 
 namespace crfp {
@@ -81,7 +83,9 @@ __device__ __forceinline__ void bwd_scatter(float (*win)[DB_WW], int ty0, int tx
 // chunk is summed in the LDS window first (LDS float atomics) and the window is then added to memory row by row -- 6.25 global atomics per
 // thread and channel in contiguous rows instead of 36 scattered ones; corners outside the window (offsets beyond ~6 px) go to memory
 // directly.  Every thread of the workgroup reaches every barrier: pixels outside the frame only skip the sampling.
-template <int CO>
+// SHARED: the compact form of crfp_dcnv2_shared_f32 -- one group, offset [n,2,h,w] and mask [n,1,h,w] read by all 9 taps; the owning
+// thread adds the taps' d/dy, d/dx and d/dmask in tap order in registers and stores once (the tiled tensors never exist).
+template <int CO, bool SHARED>
 __global__ void __launch_bounds__(256) dcn_bwd_pixel_kernel(const float* __restrict__ x, const float* __restrict__ offset,
                                                             const float* __restrict__ mask, const float* __restrict__ wt,
                                                             const float* __restrict__ go, float* gx, float* __restrict__ goff,
@@ -106,9 +110,11 @@ __global__ void __launch_bounds__(256) dcn_bwd_pixel_kernel(const float* __restr
                 for (int i = tid; i < nch * DB_WH * DB_WW; i += 256) winf[i] = 0.0f;
                 __syncthreads();
             }
-            if (active)
+            if (active) {
+                float s_y = 0.0f, s_x = 0.0f, s_m = 0.0f;   // SHARED: the sums over the taps
                 for (int tap = 0; tap < 9; ++tap) {
-                    const long long och = (long long)n * 2 * dg * 9 + 2 * (gi * 9 + tap), mch = (long long)n * dg * 9 + gi * 9 + tap;
+                    const long long och = SHARED ? (long long)n * 2 : (long long)n * 2 * dg * 9 + 2 * (gi * 9 + tap);
+                    const long long mch = SHARED ? (long long)n : (long long)n * dg * 9 + gi * 9 + tap;
                     const float dy = offset[och * HW + pix], dx = offset[(och + 1) * HW + pix], m = mask[mch * HW + pix];
                     const BwdSample s = bwd_sample((float)(py - 1 + tap / 3) + dy, (float)(px - 1 + tap % 3) + dx, H, W);
                     const float w00 = s.hy * s.hx, w01 = s.hy * s.lx, w10 = s.ly * s.hx, w11 = s.ly * s.lx;
@@ -137,17 +143,24 @@ __global__ void __launch_bounds__(256) dcn_bwd_pixel_kernel(const float* __restr
                         }
                     }
                     // a group of more than DB_CH channels: the owning thread adds its later chunks to what it stored (a fixed order)
+                    if (SHARED) {
+                        s_y += a_y * m; s_x += a_x * m; s_m += a_m;
+                        if (tap < 8) continue;
+                    }
                     if (goff) {
                         float* const qy = goff + och * HW + pix;
                         float* const qx = goff + (och + 1) * HW + pix;
-                        *qy = c0 ? *qy + a_y * m : a_y * m;
-                        *qx = c0 ? *qx + a_x * m : a_x * m;
+                        const float vy = SHARED ? s_y : a_y * m, vx = SHARED ? s_x : a_x * m;
+                        *qy = c0 ? *qy + vy : vy;
+                        *qx = c0 ? *qx + vx : vx;
                     }
                     if (gmask) {
                         float* const qm = gmask + mch * HW + pix;
-                        *qm = c0 ? *qm + a_m : a_m;
+                        const float vm = SHARED ? s_m : a_m;
+                        *qm = c0 ? *qm + vm : vm;
                     }
                 }
+            }
             if (gx) {
                 __syncthreads();   // the window holds the chunk's sums
                 for (int i = tid; i < nch * DB_WH * DB_WW; i += 256) {
@@ -164,6 +177,7 @@ __global__ void __launch_bounds__(256) dcn_bwd_pixel_kernel(const float* __restr
 // Workgroup (j = blockIdx.x of J, c = blockIdx.y).  Per tile: thread t samples channel c at pixel tile * 256 + t for the 9 taps into
 // col[k][t] (row 9: 1 for a real pixel -- the "tap" whose sum over pixels is grad_bias); then, 32 output channels at a time, thread t
 // owns the sums q = t, t + 256 of the 32 x 10 (o, k) pairs, o = q % 32, k = q / 32, and adds the tile's 256 products in a fixed order (four interleaved chains).
+template <bool SHARED>
 __global__ void __launch_bounds__(DB_TILE) dcn_bwd_weight_kernel(const float* __restrict__ x, const float* __restrict__ offset,
                                                                  const float* __restrict__ mask, const float* __restrict__ go,
                                                                  float* __restrict__ wslab, float* __restrict__ bslab, int N, int cin,
@@ -183,7 +197,7 @@ __global__ void __launch_bounds__(DB_TILE) dcn_bwd_weight_kernel(const float* __
         for (int tap = 0; tap < 9; ++tap) {
             float v = 0.0f;
             if (real) {
-                const long long och = n * 2 * dg * 9 + 2 * (gi * 9 + tap), mch = n * dg * 9 + gi * 9 + tap;
+                const long long och = SHARED ? n * 2 : n * 2 * dg * 9 + 2 * (gi * 9 + tap), mch = SHARED ? n : n * dg * 9 + gi * 9 + tap;
                 const float dy = offset[och * HW + pix], dx = offset[(och + 1) * HW + pix], m = mask[mch * HW + pix];
                 const BwdSample s = bwd_sample((float)(py - 1 + tap / 3) + dy, (float)(px - 1 + tap % 3) + dx, H, W);
                 const long long plane = (n * cin + c) * HW;
@@ -279,9 +293,10 @@ size_t dcn_backward_workspace_bytes(int n, int cin, int cout, int h, int w, int 
 }
 
 int launch_dcn_backward(const float* x, const float* offset, const float* mask, const float* weight, const float* go, float* gx, float* goff,
-                        float* gmask, float* gw, float* gb, int N, int cin, int cout, int H, int W, int dg, void* workspace, hipStream_t s) {
+                        float* gmask, float* gw, float* gb, int N, int cin, int cout, int H, int W, int dg, int shared, void* workspace, hipStream_t s) {
     const double px = (double)N * H * W;
-    ProfScope prof("dcnv2_backward_nchw", s, px * (2.0 * cin + 54.0 * dg + cout) * 4.0, 6.0 * px * cin * cout * 9);
+    ProfScope prof(shared ? "dcnv2_shared_backward_nchw" : "dcnv2_backward_nchw", s, px * (2.0 * cin + (shared ? 6.0 : 54.0 * dg) + cout) * 4.0,
+                   6.0 * px * cin * cout * 9);
     char* p = (char*)workspace;
     float* wt = (float*)p; p += bwd_wt_bytes(cin, cout);
     float* wslab = (float*)p; p += bwd_wslab_bytes(N, cin, cout, H, W);
@@ -292,15 +307,17 @@ int launch_dcn_backward(const float* x, const float* offset, const float* mask, 
         dcn_bwd_wt_kernel<<<(nwt + 255) / 256, 256, 0, s>>>(weight, wt, cin, cout, CO);
         CRFP_CHECK_LAUNCH();
         dim3 grid((W + 63) / 64, (H + 3) / 4, N);
-        if (CO == 8) dcn_bwd_pixel_kernel<8><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);
-        else if (CO == 32) dcn_bwd_pixel_kernel<32><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);
-        else dcn_bwd_pixel_kernel<DB_MAXC><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);
+        if (shared) dcn_bwd_pixel_kernel<8, true><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);   // 4 -> 4: CO = 8
+        else if (CO == 8) dcn_bwd_pixel_kernel<8, false><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);
+        else if (CO == 32) dcn_bwd_pixel_kernel<32, false><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);
+        else dcn_bwd_pixel_kernel<DB_MAXC, false><<<grid, 256, 0, s>>>(x, offset, mask, wt, go, gx, goff, gmask, cin, cout, H, W, dg);
         CRFP_CHECK_LAUNCH();
     }
     if (gw || gb) {
         const int J = bwd_slabs(N, cin, H, W), nw = cout * cin * 9;
         const long long tiles = ((long long)N * H * W + DB_TILE - 1) / DB_TILE;
-        dcn_bwd_weight_kernel<<<dim3(J, cin), DB_TILE, 0, s>>>(x, offset, mask, go, wslab, bslab, N, cin, cout, H, W, dg, tiles);
+        if (shared) dcn_bwd_weight_kernel<true><<<dim3(J, cin), DB_TILE, 0, s>>>(x, offset, mask, go, wslab, bslab, N, cin, cout, H, W, dg, tiles);
+        else dcn_bwd_weight_kernel<false><<<dim3(J, cin), DB_TILE, 0, s>>>(x, offset, mask, go, wslab, bslab, N, cin, cout, H, W, dg, tiles);
         CRFP_CHECK_LAUNCH();
         dcn_bwd_slab_sum_kernel<<<(nw + cout + 255) / 256, 256, 0, s>>>(wslab, bslab, gw, gb, nw, cout, J);
         CRFP_CHECK_LAUNCH();

@@ -108,7 +108,10 @@ def dcnv2_g8_packed(x, offset, mask, packed, bias):
 
 
 def flow_warp(x, flow, interpolation="bilinear", padding_mode="zeros", align_corners=True):
-    """Drop-in for the reference's ``flow_warp`` (model/CRFP.py:90-130): x[n,c,h,w], flow[n,h,w,2]."""
+    """Drop-in for the reference's ``flow_warp`` (model/CRFP.py:90-130): x[n,c,h,w], flow[n,h,w,2], forward and backward.  With grad mode
+    on and ``x`` or ``flow`` requiring grad the result carries a ``grad_fn`` whose backward is crfp_flow_warp_backward_f32 (fp32, first
+    order only; the gradient of ``x`` is an unordered float atomic sum, that of ``flow`` is bitwise reproducible); otherwise this is the
+    plain forward call."""
     if tuple(x.shape[-2:]) != tuple(flow.shape[1:3]):
         raise ValueError(f"The spatial sizes of input ({tuple(x.shape[-2:])}) and flow "
                          f"({tuple(flow.shape[1:3])}) are not the same.")
@@ -117,6 +120,14 @@ def flow_warp(x, flow, interpolation="bilinear", padding_mode="zeros", align_cor
     if padding_mode not in ("zeros", "border"):
         raise NotImplementedError(f"flow_warp: padding_mode {padding_mode!r}")
     x, flow = _dev(x, "x"), _dev(flow, "flow")
+    border = 1 if padding_mode == "border" else 0
+    if torch.is_grad_enabled() and (x.requires_grad or flow.requires_grad):
+        return _FlowWarpFunction.apply(x, flow, border)
+    return _flow_warp_forward(x, flow, border)
+
+
+def _flow_warp_forward(x, flow, border):
+    """crfp_flow_warp_f32 on float32, contiguous device tensors."""
     n, c, h, w = x.shape
     L = _lib.lib()
     out = torch.empty_like(x)
@@ -124,17 +135,47 @@ def flow_warp(x, flow, interpolation="bilinear", padding_mode="zeros", align_cor
     ws = _ws(nb, x.device)
     with _on(x, flow):
         _lib.check(L.crfp_flow_warp_f32(x.data_ptr(), flow.data_ptr(), out.data_ptr(), n, c, h, w,
-                                        1 if padding_mode == "border" else 0, ws.data_ptr(), ws.numel(), _stream()),
+                                        border, ws.data_ptr(), ws.numel(), _stream()),
                    "crfp_flow_warp_f32")
     return out
+
+
+class _FlowWarpFunction(torch.autograd.Function):
+    """``flow_warp`` under autograd: forward = ``_flow_warp_forward``, backward = crfp_flow_warp_backward_f32 with a NULL pointer for
+    every gradient ``ctx.needs_input_grad`` does not ask for (and for ``x``, which only the gradient of the flow reads)."""
+
+    @staticmethod
+    def forward(ctx, x, flow, border):
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, flow)
+        ctx.border = border
+        ctx.shape = tuple(x.shape)
+        return _flow_warp_forward(x, flow, border)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, flow = ctx.saved_tensors
+        grad_out = _dev(grad_out, "grad_out")
+        n, c, h, w = ctx.shape
+        L = _lib.lib()
+        with _on(flow, grad_out):
+            gx = torch.empty_like(grad_out) if ctx.needs_input_grad[0] else None
+            gflow = torch.empty_like(flow) if ctx.needs_input_grad[1] else None
+            ws = _ws(L.crfp_flow_warp_backward_workspace_bytes(n, c, h, w), flow.device)
+            _lib.check(L.crfp_flow_warp_backward_f32(x.data_ptr() if x is not None else None, flow.data_ptr(), grad_out.data_ptr(),
+                                                     gx.data_ptr() if gx is not None else None,
+                                                     gflow.data_ptr() if gflow is not None else None,
+                                                     n, c, h, w, ctx.border, ws.data_ptr(), ws.numel(), _stream()),
+                       "crfp_flow_warp_backward_f32")
+        return gx, gflow, None
 
 
 def dcnv2(x, offset, mask, weight, bias, kernel_size=3, padding=1, dilation=1, deformable_groups=1):
     """Drop-in for ``dcn_v2.DCNv2.forward`` (reference model/CRFP.py:350), forward and backward.  With grad mode on and at least one of
     the five tensors requiring grad the result carries a ``grad_fn`` whose backward is crfp_dcnv2_backward_f32 (fp32, first order only;
     grad_input is an unordered float atomic sum, the other four gradients are bitwise reproducible); otherwise this is the plain
-    forward call.  The other wrappers of this module (``dcnv2_shared``, ``dcnv2_g8_packed``, ``flow_warp``, ``conv3x3*``) are
-    forward-only."""
+    forward call.  ``dcnv2_shared`` and ``flow_warp`` have a backward of their own in the same mould; the other wrappers of this module
+    (``dcnv2_g8_packed``, ``conv3x3*``, ``fovea_head``, the resamplers) are forward-only."""
     x, offset, mask = _dev(x, "input"), _dev(offset, "offset"), _dev(mask, "mask")
     weight, bias = _dev(weight, "weight"), _dev(bias, "bias")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, offset, mask, weight, bias)):
@@ -197,11 +238,22 @@ class _DCNv2Function(torch.autograd.Function):
 
 def dcnv2_shared(x, offset, mask, weight, bias):
     """DCNv2 (4 -> 4 channels, one group) with one (dy, dx) [n,2,h,w] and one mask [n,1,h,w] per pixel shared by the 9 taps: equal to
-    ``dcnv2(x, offset.repeat(1, 9, 1, 1), mask.repeat(1, 9, 1, 1), ...)`` (reference model/CRFP.py:341-350) without the tiled tensors."""
+    ``dcnv2(x, offset.repeat(1, 9, 1, 1), mask.repeat(1, 9, 1, 1), ...)`` (reference model/CRFP.py:341-350) without the tiled tensors,
+    forward and backward.  With grad mode on and at least one of the five tensors requiring grad the result carries a ``grad_fn`` whose
+    backward is crfp_dcnv2_shared_backward_f32: the gradients of the compact offset and mask are the sums over the 9 taps, formed in
+    registers (fp32, first order only; grad_input is an unordered float atomic sum, the other four are bitwise reproducible)."""
     x, offset, mask, weight, bias = _dev(x, "input"), _dev(offset, "offset"), _dev(mask, "mask"), _dev(weight, "weight"), _dev(bias, "bias")
     n, cin, h, w = x.shape
-    cout = weight.shape[0]
     assert tuple(offset.shape) == (n, 2, h, w) and tuple(mask.shape) == (n, 1, h, w), "dcnv2_shared: offset [n,2,h,w], mask [n,1,h,w]"
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, offset, mask, weight, bias)):
+        return _DCNv2SharedFunction.apply(x, offset, mask, weight, bias)
+    return _dcnv2_shared_forward(x, offset, mask, weight, bias)
+
+
+def _dcnv2_shared_forward(x, offset, mask, weight, bias):
+    """crfp_dcnv2_shared_f32 on float32, contiguous device tensors."""
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
     L = _lib.lib()
     out = torch.empty((n, cout, h, w), dtype=torch.float32, device=x.device)
     with _on(x, offset, mask, weight, bias):
@@ -210,6 +262,35 @@ def dcnv2_shared(x, offset, mask, weight, bias):
         _lib.check(L.crfp_dcnv2_shared_f32(x.data_ptr(), offset.data_ptr(), mask.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
                                            n, cin, cout, h, w, ws.data_ptr(), ws.numel(), _stream()), "crfp_dcnv2_shared_f32")
     return out
+
+
+class _DCNv2SharedFunction(torch.autograd.Function):
+    """``dcnv2_shared`` under autograd: forward = ``_dcnv2_shared_forward``, backward = crfp_dcnv2_shared_backward_f32 with a NULL pointer
+    for every gradient ``ctx.needs_input_grad`` does not ask for."""
+
+    @staticmethod
+    def forward(ctx, x, offset, mask, weight, bias):
+        ctx.save_for_backward(x, offset, mask, weight)
+        return _dcnv2_shared_forward(x, offset, mask, weight, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, offset, mask, weight = ctx.saved_tensors
+        grad_out = _dev(grad_out, "grad_out")
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        L = _lib.lib()
+        with _on(x, offset, mask, weight, grad_out):
+            like = (x, offset, mask, weight)
+            grads = [torch.empty_like(t) if need else None for t, need in zip(like, ctx.needs_input_grad[:4])]
+            grads.append(torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[4] else None)
+            ws = _ws(L.crfp_dcnv2_shared_backward_workspace_bytes(n, cin, h, w), x.device)
+            _lib.check(L.crfp_dcnv2_shared_backward_f32(x.data_ptr(), offset.data_ptr(), mask.data_ptr(), weight.data_ptr(), grad_out.data_ptr(),
+                                                        *(g.data_ptr() if g is not None else None for g in grads),
+                                                        n, cin, cout, h, w, ws.data_ptr(), ws.numel(), _stream()),
+                       "crfp_dcnv2_shared_backward_f32")
+        return tuple(grads)
 
 
 def conv3x3(x, weight, bias=None, act="none", post_scale=1.0):

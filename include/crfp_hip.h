@@ -24,6 +24,8 @@
  *
  * Reference interfaces replaced (paths relative to the reference repo eugenelet/CRFP):
  *   crfp_flow_warp_f32        model/CRFP.py:90-130   flow_warp()  (ATen grid_sampler_2d underneath)
+ *   crfp_flow_warp_backward_f32  autograd of flow_warp (ATen grid_sampler_2d_backward and the normalisation in front of it)
+ *   crfp_dcnv2_shared_backward_f32  autograd of DCN_module's repeat path (model/CRFP.py:341-350) without the tiled tensors
  *   crfp_dcnv2_forward_f32    model/CRFP.py:6,318-320,350  third-party dcn_v2.DCNv2.forward
  *   crfp_dcnv2_backward_f32   the same extension's backward (autograd of self.dcn(pre_x, offset, mask), model/CRFP.py:350)
  *   crfp_conv3x3_f32          every nn.Conv2d(k=3,s=1,p=1) on the path (e.g. model/CRFP.py:48-50,303-317)
@@ -122,6 +124,41 @@ int crfp_dcnv2_backward_f32(const float* x, const float* offset, const float* ma
 size_t crfp_dcnv2_shared_workspace_bytes(int n, int c, int h, int w);
 int crfp_dcnv2_shared_f32(const float* x, const float* offset, const float* mask, const float* weight, const float* bias, float* out,
                           int n, int cin, int cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- backward of crfp_dcnv2_shared_f32: crfp_dcnv2_backward_f32's kernels in their shared form.  offset [n,2,h,w] and mask [n,1,h,w]
+ * stay compact, and so do grad_offset [n,2,h,w] and grad_mask [n,1,h,w]: the thread that owns a pixel adds the 9 taps' d/dy, d/dx and
+ * d/dmask in tap order in registers and stores once, so the 9x-tiled tensors and their gradients never exist (not in the workspace
+ * either).  Everything else is crfp_dcnv2_backward_f32's contract: NULL outputs skipped (all five NULL: CRFP_E_BADARG), grad_offset,
+ * grad_mask, grad_weight and grad_bias bitwise reproducible, grad_x an atomic sum, argument errors before any HIP call.  Domain: the
+ * forward's, cin = cout = 4 (anything else CRFP_E_UNSUPPORTED, size query 0), n <= 65535, h <= 262140, 2^58 tensor elements. */
+size_t crfp_dcnv2_shared_backward_workspace_bytes(int n, int c, int h, int w);
+int crfp_dcnv2_shared_backward_f32(const float* x, const float* offset, const float* mask, const float* weight, const float* grad_out,
+                                   float* grad_x, float* grad_offset, float* grad_mask, float* grad_weight, float* grad_bias,
+                                   int n, int cin, int cout, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- flow_warp backward: the gradients of crfp_flow_warp_f32's out for a given grad_out[n,c,h,w]: grad_x[n,c,h,w] and
+ * grad_flow[n,h,w,2] = (d/dx, d/dy).  The function differentiated is the forward kernel's own: the sample coordinate goes through the
+ * same float32 normalisation round trip, border mode clamps it to [0, size - 1] before the floor, and the cell and the four weights are
+ * the forward's.  grad_x adds grad_out * weight at each corner inside the plane (the call clears grad_x on `stream` first; a float atomic
+ * sum, NOT bitwise reproducible).  grad_flow is the derivative inside the cell the forward's floor picked (the floor's cell at integer
+ * positions, as ATen), an invalid corner's value taken as 0, times the chain factor ((size-1)/2) * (2/max(size-1,1)) formed in float32
+ * (0 along an axis of size 1), and in border mode times 0 where the unclamped coordinate is <= 0 or >= size - 1; one plain store per
+ * element, bitwise reproducible.  A flow that is NaN, infinite or huge has the gradient of the constant the forward computes there:
+ * zeros mode adds nothing to grad_x, border mode adds grad_out at the clamped pixel, grad_flow is 0; no address is formed from an
+ * unvalidated position.
+ * A NULL output is not computed (no clear and no scatter without grad_x); x is read only for grad_flow and may be NULL without it.
+ * Both outputs NULL, a NULL flow or grad_out, x NULL with grad_flow wanted, or a size < 1: CRFP_E_BADARG.  padding_mode other than
+ * CRFP_PAD_ZEROS / CRFP_PAD_BORDER, n > 65535, h > 262140, w > 2^30 or more than 2^58 tensor elements: CRFP_E_UNSUPPORTED (size query
+ * 0).  A missing or short workspace: CRFP_E_WORKSPACE.  Every argument error is returned before any HIP call. */
+size_t crfp_flow_warp_backward_workspace_bytes(int n, int c, int h, int w);
+int crfp_flow_warp_backward_f32(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow,
+                                int n, int c, int h, int w, int padding_mode, void* workspace, size_t workspace_bytes, void* stream);
+/* measurement hook: the same call with the kernel's on-chip summation window of grad_x placed on the pixel tile itself (window = 0)
+ * instead of the tile displaced by its centre flow (window = 1, what crfp_flow_warp_backward_f32 does).  Same results up to the order of
+ * the atomic sum. */
+int crfp_flow_warp_backward_window_f32(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow,
+                                       int n, int c, int h, int w, int padding_mode, int window, void* workspace, size_t workspace_bytes,
+                                       void* stream);
 
 /* ---- 3x3 stride-1 pad-1 convolution, NCHW f32, fused bias + activation (fp32 MFMA). */
 size_t crfp_conv3x3_workspace_bytes(int n, int cin, int cout, int h, int w);

@@ -377,6 +377,85 @@ int main() {
         }
         EXPECT(crfp_stub_launches() == l0 + 12 + 4 * 4);
     }
+    // the shared-offset DCNv2 backward: the 4 -> 4 domain, the compact route's scratch (no tiled tensor), refusals before the first launch
+    {
+        const size_t need = crfp_dcnv2_shared_backward_workspace_bytes(1, 4, 24, 40);
+        EXPECT(need > 0 && need == crfp_dcnv2_backward_workspace_bytes(1, 4, 4, 24, 40, 3, 1));
+        const size_t big = crfp_dcnv2_shared_backward_workspace_bytes(1, 4, 1440, 2560);
+        EXPECT(big > 0 && big < (1u << 20));   // weight transpose + per-workgroup slabs: nowhere near 27 planes of 1440 x 2560
+        EXPECT(crfp_dcnv2_shared_backward_workspace_bytes(1, 8, 24, 40) == 0 && crfp_dcnv2_shared_backward_workspace_bytes(1, 3, 24, 40) == 0);
+        EXPECT(crfp_dcnv2_shared_backward_workspace_bytes(0, 4, 24, 40) == 0 && crfp_dcnv2_shared_backward_workspace_bytes(1, 4, 0, 40) == 0);
+        EXPECT(crfp_dcnv2_shared_backward_workspace_bytes(70000, 4, 24, 40) == 0 && crfp_dcnv2_shared_backward_workspace_bytes(1, 4, 300000, 40) == 0);
+        EXPECT(crfp_dcnv2_shared_backward_workspace_bytes(65535, 4, 262140, 2147483647) == 0);
+        const long l0 = crfp_stub_launches();
+#define DCNS(X, OFF, M, W, GO, GX, GOFF, GM, GW, GB, N, CIN, COUT, WS, WSB) \
+    crfp_dcnv2_shared_backward_f32(X, OFF, M, W, GO, GX, GOFF, GM, GW, GB, N, CIN, COUT, 24, 40, WS, WSB, nullptr)
+        EXPECT(DCNS(nullptr, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(DCNS(p16, nullptr, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNS(p16, p16, nullptr, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNS(p16, p16, p16, nullptr, p16, p16, p16, p16, p16, p16, 1, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNS(p16, p16, p16, p16, nullptr, p16, p16, p16, p16, p16, 1, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "nothing to do") != nullptr);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 0, 4, 4, p16, need) == CRFP_E_BADARG);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 8, 4, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "4 -> 4") != nullptr);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 8, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 70000, 4, 4, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "65535 images") != nullptr);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, p16, need - 1) == CRFP_E_WORKSPACE);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, nullptr, need) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_stub_launches() == l0);
+        // the launches of crfp_dcnv2_backward_f32: transpose + pixel kernel for grad_x / grad_offset / grad_mask, slab pass + slab sum for the rest
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, p16, need) == 0 && crfp_stub_launches() == l0 + 4);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, 1, 4, 4, p16, need) == 0 && crfp_stub_launches() == l0 + 6);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, nullptr, p16, p16, nullptr, nullptr, 1, 4, 4, p16, need) == 0 && crfp_stub_launches() == l0 + 8);
+        EXPECT(DCNS(p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, p16, 1, 4, 4, p16, need) == 0 && crfp_stub_launches() == l0 + 10);
+#undef DCNS
+        EXPECT(crfp_dcnv2_shared_backward_f32(p16, p16, p16, p16, p16, p16, p16, p16, p16, p16, 1, 4, 4, 1440, 2560, p16, big, nullptr) == 0);
+        EXPECT(crfp_stub_launches() == l0 + 14);
+    }
+    // the flow_warp backward: sizing, the NULL-output rules, every refusal before the first launch, one launch per accepted call
+    {
+        const size_t need = crfp_flow_warp_backward_workspace_bytes(2, 5, 9, 11);
+        EXPECT(need > 0 && crfp_flow_warp_backward_workspace_bytes(1, 32, 360, 640) > 0 && crfp_flow_warp_backward_workspace_bytes(1, 4, 1440, 2560) > 0);
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(1, 3, 1, 7) > 0 && crfp_flow_warp_backward_workspace_bytes(1, 3, 6, 1) > 0);
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(0, 5, 9, 11) == 0 && crfp_flow_warp_backward_workspace_bytes(2, 0, 9, 11) == 0);
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(2, 5, 0, 11) == 0 && crfp_flow_warp_backward_workspace_bytes(2, 5, 9, 0) == 0);
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(70000, 5, 9, 11) == 0 && crfp_flow_warp_backward_workspace_bytes(2, 5, 300000, 11) == 0);
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(2, 5, 9, (1 << 30) + 1) == 0);
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(65535, 1 << 20, 262140, 1 << 30) == 0);   // element counts beyond 64-bit indexing
+        EXPECT(crfp_flow_warp_backward_workspace_bytes(8, 64, 4320, 7680) > 0 && crfp_flow_warp_backward_workspace_bytes(1, 1, 262140, 100000) > 0);
+        const long l0 = crfp_stub_launches();
+#define WARPB(X, FLOW, GO, GX, GFLOW, N, C, MODE, WS, WSB) crfp_flow_warp_backward_f32(X, FLOW, GO, GX, GFLOW, N, C, 9, 11, MODE, WS, WSB, nullptr)
+        EXPECT(WARPB(p16, p16, p16, nullptr, nullptr, 2, 5, CRFP_PAD_ZEROS, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "nothing to do") != nullptr);
+        EXPECT(WARPB(nullptr, p16, p16, p16, p16, 2, 5, CRFP_PAD_ZEROS, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "grad_flow") != nullptr);
+        EXPECT(WARPB(nullptr, p16, p16, nullptr, p16, 2, 5, CRFP_PAD_BORDER, p16, need) == CRFP_E_BADARG);
+        EXPECT(WARPB(p16, nullptr, p16, p16, p16, 2, 5, CRFP_PAD_ZEROS, p16, need) == CRFP_E_BADARG);
+        EXPECT(WARPB(p16, p16, nullptr, p16, p16, 2, 5, CRFP_PAD_ZEROS, p16, need) == CRFP_E_BADARG);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 0, 5, CRFP_PAD_ZEROS, p16, need) == CRFP_E_BADARG);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 0, CRFP_PAD_ZEROS, p16, need) == CRFP_E_BADARG);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 5, 2, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "padding_mode") != nullptr);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 5, -1, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 70000, 5, CRFP_PAD_ZEROS, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "2^58") != nullptr);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 5, CRFP_PAD_ZEROS, p16, need - 1) == CRFP_E_WORKSPACE);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 5, CRFP_PAD_BORDER, nullptr, need) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_flow_warp_backward_window_f32(p16, p16, p16, p16, p16, 2, 5, 9, 11, CRFP_PAD_ZEROS, 2, p16, need, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_stub_launches() == l0);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 5, CRFP_PAD_ZEROS, p16, need) == 0 && crfp_stub_launches() == l0 + 1);
+        EXPECT(WARPB(p16, p16, p16, p16, p16, 2, 5, CRFP_PAD_BORDER, p16, need) == 0 && crfp_stub_launches() == l0 + 2);
+        EXPECT(WARPB(nullptr, p16, p16, p16, nullptr, 2, 5, CRFP_PAD_ZEROS, p16, need) == 0 && crfp_stub_launches() == l0 + 3);   // x is read for grad_flow only
+        EXPECT(WARPB(p16, p16, p16, nullptr, p16, 2, 5, CRFP_PAD_BORDER, p16, need) == 0 && crfp_stub_launches() == l0 + 4);
+#undef WARPB
+        EXPECT(crfp_flow_warp_backward_window_f32(p16, p16, p16, p16, p16, 1, 32, 360, 640, CRFP_PAD_ZEROS, 0, p16, need, nullptr) == 0);
+        EXPECT(crfp_flow_warp_backward_f32(p16, p16, p16, p16, p16, 1, 4, 1440, 2560, CRFP_PAD_BORDER, p16, need, nullptr) == 0);
+        EXPECT(crfp_stub_launches() == l0 + 6);
+    }
     // the conv probe (test hook): sizing, the launcher's kernel-selection rule, every refusal before the first launch, whole calls on the stub
     {
         crfp_probe_conv q;
