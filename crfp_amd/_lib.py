@@ -134,6 +134,7 @@ SIGNATURES = {
     "crfp_fnet_forward": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_rt_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
     "crfp_rt_forward_clip": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "crfp_rt_debug_fetch": (C.c_int, [C.c_char_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p] + [C.POINTER(C.c_int)] * 3 + [C.c_void_p]),
     "crfp_prof_enable": (C.c_int, [C.c_int]),
     "crfp_prof_reset": (C.c_int, []),
     "crfp_debug_side_tables": (C.c_int, []),
@@ -169,13 +170,13 @@ _DSV = _STREAM | {"fnet_forward", "debug_fetch"}
 _NUMEL = frozenset(("param_numel",))   # shapes do not depend on the storage type
 # dsv: CRFP_DSV.  cra: CRFP_DSV_CRA, its own parameter table, clip forward and the one-frame-per-call form (MRCF_simple_v18_cra).  simple /
 # dense: the CRFP_simple / CRFP wirings -- CRFP_DSV's parameter names with their own shapes -- clip forward and the one-frame-per-call form
-# (MRCF_simple_v13 / v15).  rt: the regional benchmark wiring, fp32 storage only, with a forward call and a workspace query of its own.
+# (MRCF_simple_v13 / v15).  rt: the regional benchmark wiring, fp32 storage only, with a forward call, a workspace query and a debug fetch of its own.
 FAMILIES = {
     "dsv": Family("crfp_dsv_", "dsv", NUM_PARAMS, "CRFP_DSV", _DSV, _DSV - _NUMEL),
     "cra": Family("crfp_cra_", "cra", CRA_NUM_PARAMS, "CRFP_DSV_CRA", _STREAM, _STREAM - _NUMEL),
     "simple": Family("crfp_simple_", "dsv", NUM_PARAMS, "CRFP_simple", _STREAM, _STREAM - _NUMEL),
     "dense": Family("crfp_dense_", "dsv", NUM_PARAMS, "CRFP", _STREAM, _STREAM - _NUMEL),
-    "rt": Family("crfp_rt_", "rt", RT_NUM_PARAMS, "MRCF_simple_v18", _PACK | {"workspace_bytes", "forward_clip"}, frozenset()),
+    "rt": Family("crfp_rt_", "rt", RT_NUM_PARAMS, "MRCF_simple_v18", _PACK | {"workspace_bytes", "forward_clip", "debug_fetch"}, frozenset()),
 }
 
 

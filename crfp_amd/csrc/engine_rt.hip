@@ -217,6 +217,55 @@ struct Layout {
     size_t bytes() const { return cur; }
 };
 
+// ------------------------------------------------------------------ crfp_rt_debug_fetch: the buffers a test may read back, by name
+// res: the map a buffer lives on.  kind: Q4 (converted to NCHW, the P4 pad stripped), an [H][W][2] flow field or an SRC_S3 image (both copied
+// as they are).  items: one, one per frame, or one per flow.  A `moving` buffer is written by frames >= 1 only (none with t = 1).
+// par: the parity set of the clip's last frame, (t - 1) & 1.
+enum { FR_LR, FR_FOVEA, FR_WLR, FR_W2, FR_W8, FR_FRAME8 };
+enum { FK_Q4, FK_FLOW, FK_S3 };
+enum { FN_ONE, FN_FRAMES, FN_FLOWS };
+struct FetchDef {
+    const char* name;
+    size_t (*off)(const Layout& L, int par);
+    int nq, res, pad, kind, items, moving;
+};
+#define RT_OFF(expr) [](const Layout& L, int par) -> size_t { (void)par; return L.expr; }
+static const FetchDef kFetch[] = {
+    {"flow_lr", RT_OFF(flow_lr), 1, FR_WLR, 0, FK_Q4, FN_FLOWS, 1},   // channels 0, 1 = (dx, dy); 2, 3 are the quad's padding
+    {"x_lr", RT_OFF(x_lr), 8, FR_LR, 0, FK_Q4, FN_FRAMES, 0},
+    {"x_hr", RT_OFF(x_hr), 1, FR_FOVEA, 0, FK_Q4, FN_FRAMES, 0},
+    {"state", RT_OFF(state), 1, FR_W8, 1, FK_Q4, FN_ONE, 0},
+    {"state_w", RT_OFF(state_w), 1, FR_W8, 0, FK_Q4, FN_ONE, 1},
+    {"prev2", RT_OFF(prev2), 8, FR_W2, 1, FK_Q4, FN_ONE, 1},
+    {"prev2w", RT_OFF(prev2w), 8, FR_W2, 0, FK_Q4, FN_ONE, 1},
+    {"carry", RT_OFF(carry), 6, FR_W2, 1, FK_Q4, FN_ONE, 0},
+    {"carryw", RT_OFF(carryw), 6, FR_W2, 0, FK_Q4, FN_ONE, 1},
+    {"offfeat0", RT_OFF(offfeat[0]), 8, FR_W2, 0, FK_S3, FN_ONE, 1},
+    {"offfeat1", RT_OFF(offfeat[1]), 8, FR_W2, 0, FK_S3, FN_ONE, 1},
+    {"offfeat2", RT_OFF(offfeat[2]), 8, FR_W2, 0, FK_S3, FN_ONE, 1},
+    {"aligned0", RT_OFF(aligned[0]), 8, FR_W2, 0, FK_Q4, FN_ONE, 1},
+    {"aligned1", RT_OFF(aligned[1]), 8, FR_W2, 0, FK_Q4, FN_ONE, 1},
+    {"aligned2", RT_OFF(aligned[2]), 8, FR_W2, 0, FK_Q4, FN_ONE, 1},
+    {"poff", RT_OFF(poff), 1, FR_W8, 0, FK_Q4, FN_ONE, 1},
+    {"al3", RT_OFF(al3), 1, FR_W8, 0, FK_Q4, FN_ONE, 1},
+    {"feat2", RT_OFF(feat2), 1, FR_FRAME8, 0, FK_Q4, FN_ONE, 0},
+    {"flow2", [](const Layout& L, int par) -> size_t { return L.flow2[par]; }, 0, FR_W2, 0, FK_FLOW, FN_ONE, 1},
+    {"flow8", [](const Layout& L, int par) -> size_t { return L.flow8[par]; }, 0, FR_W8, 0, FK_FLOW, FN_ONE, 1},
+    {"win", [](const Layout& L, int par) -> size_t { return L.win[par]; }, 6, FR_W2, 0, FK_Q4, FN_ONE, 1},
+    {"upw", [](const Layout& L, int par) -> size_t { return L.upw[par]; }, 1, FR_W8, 0, FK_Q4, FN_ONE, 1},
+};
+#undef RT_OFF
+static void fetch_size(const Layout& L, int res, int* H, int* W) {
+    switch (res) {
+        case FR_LR: *H = L.h; *W = L.w; break;
+        case FR_FOVEA: *H = L.fh; *W = L.fw; break;
+        case FR_WLR: *H = L.whl; *W = L.wwl; break;
+        case FR_W2: *H = L.wh2; *W = L.ww2; break;
+        case FR_W8: *H = L.wh8; *W = L.ww8; break;
+        default: *H = 8 * L.h; *W = 8 * L.w; break;
+    }
+}
+
 // ------------------------------------------------------------------ small layout kernels (window <-> frame)
 // dst[q][y][x] = src[q][y][x] for the top-left dH x dW pixels; either side may be a P4 tensor (pitch + 1, plane + 1 row)
 __global__ void rt_copy_q4_kernel(const float4* __restrict__ src, int sH, int sW, int spad, float4* __restrict__ dst, int dH, int dW, int dpad,
@@ -613,6 +662,33 @@ int crfp_rt_forward_clip(const void* packed, int flags, const float* lrs, const 
     for (int i = 0; i < t && !R.rc; ++i) R.frame(i, t, lrs + (long long)i * 3 * h * w, out + (long long)i * co * 64 * h * w);
     R.join_all();
     return R.rc;
+}
+
+int crfp_rt_debug_fetch(const char* name, int t, int h, int w, int fh, int fw, int wph, int wpw, const void* workspace, float* out_nchw,
+                        int* c_out, int* h_out, int* w_out, void* stream) {
+    if (!name || !workspace) { set_error("rt_debug_fetch: null argument"); return CRFP_E_BADARG; }
+    if (int rc = rt_check_dims(t, h, w, fh, fw, wph, wpw)) return rc;
+    const Layout L(t, h, w, fh, fw, wph, wpw);
+    for (const FetchDef& d : kFetch) {
+        if (strcmp(d.name, name) != 0) continue;
+        if (d.moving && t < 2) { set_error("rt_debug_fetch: '%s' is written by frames >= 1 only (t = %d)", name, t); return CRFP_E_BADARG; }
+        int H, W;
+        fetch_size(L, d.res, &H, &W);
+        const int N = d.items == FN_FRAMES ? t : (d.items == FN_FLOWS ? t - 1 : 1), C = d.kind == FK_FLOW ? 2 : 4 * d.nq;
+        if (c_out) *c_out = C;
+        if (h_out) *h_out = H;
+        if (w_out) *w_out = W;
+        if (!out_nchw) return N;
+        const float* p = reinterpret_cast<const float*>((const char*)workspace + d.off(L, (t - 1) & 1));
+        if (d.kind == FK_Q4) return launch_q4_to_nchw(p, out_nchw, N, C, H, W, d.pad, (hipStream_t)stream);
+        if (hipMemcpyAsync(out_nchw, p, (size_t)N * C * H * W * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+            set_error("rt_debug_fetch: hipMemcpyAsync failed");
+            return 1;
+        }
+        return 0;
+    }
+    set_error("rt_debug_fetch: unknown buffer '%s'", name);
+    return CRFP_E_BADARG;
 }
 
 }  // extern "C"

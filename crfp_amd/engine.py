@@ -114,7 +114,7 @@ _REFUSALS = {
     "stream_batch": "a clip handle; the one-frame-per-call schedules are DSVEngine's and, for CRFP_DSV_CRA / CRFP_simple / CRFP, "
                     "CRAStreamEngine's / SimpleStreamEngine's / DenseStreamEngine's",
     "fnet_forward": "use the model's flow network modules ({model}.compute_flow)",
-    "debug_fetch": "debug_fetch reads the CRFP_DSV workspace layout",
+    "debug_fetch": "debug_fetch reads the CRFP_DSV workspace layout (DSVEngine) or the regional one (RuntimeEngine)",
 }
 
 
@@ -414,6 +414,7 @@ class RuntimeEngine(_Handle):
 
     def __init__(self, state_dict, device, y_only: bool = False):
         super().__init__(device, y_only)
+        self._last_key = None        # geometry of the last forward(): what debug_fetch reads
         self.pack(state_dict)
 
     @staticmethod
@@ -458,6 +459,29 @@ class RuntimeEngine(_Handle):
                 if ovf is not None:
                     ovf |= ws[:4].view(torch.int32)
         self._ovf = ovf if ovf is not None else ws[:4].view(torch.int32)
+        self._last_key = key
+        return out
+
+    def debug_fetch(self, name):
+        """Copy a named workspace intermediate of the last ``forward`` (its last clip, its geometry) to a device tensor (tests and
+        diagnosis only; the names: ``crfp_rt_debug_fetch``, include/crfp_hip.h).  Q4 / P4 buffers come back NCHW, ``flow2`` / ``flow8`` as
+        [1,H,W,2]; the split-fp16 images ``offfeat0..2`` are decoded here to their 32 fp32 channels.  RuntimeError before any forward."""
+        fetch = self._call("debug_fetch")
+        key = getattr(self, "_last_key", None)
+        if key is None or key not in self._ws:
+            raise RuntimeError("crfp_amd: RuntimeEngine.debug_fetch before any forward on this handle: there is no workspace to read")
+        ws = self._ws[key]
+        c, hh, ww = C.c_int(), C.c_int(), C.c_int()
+        n = fetch(name.encode(), *key, ws.data_ptr(), None, C.byref(c), C.byref(hh), C.byref(ww), _stream())
+        if n < 0:
+            _lib.check(n, fetch.__name__)
+        flow = name in ("flow2", "flow8")
+        out = torch.empty((n, hh.value, ww.value, 2) if flow else (n, c.value, hh.value, ww.value), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(fetch(name.encode(), *key, ws.data_ptr(), out.data_ptr(), None, None, None, _stream()), fetch.__name__)
+        if name.startswith("offfeat"):   # SRC_S3: planes [0, c / 8) hold fp16(x), planes [c / 8, c / 4) fp16((x - x0) * 2^11), 8 channels per element
+            s3 = out.view(torch.float16).view(n, 2, c.value // 8, hh.value, ww.value, 8).float()
+            out = (s3[:, 0] + s3[:, 1] * 2.0 ** -11).permute(0, 1, 4, 2, 3).reshape(n, c.value, hh.value, ww.value).contiguous()
         return out
 
 

@@ -734,6 +734,15 @@ int crfp_rt_pack_weights(const float* const* params, int y_only, void* packed, s
 size_t crfp_rt_workspace_bytes(int t, int h, int w, int fh, int fw, int wp_h, int wp_w);   /* 0: bad geometry (crfp_last_error) */
 int crfp_rt_forward_clip(const void* packed, int flags, const float* lrs, const float* fvs, float* out, int t, int h, int w,
                          int fh, int fw, int wp_h, int wp_w, void* workspace, size_t workspace_bytes, void* stream);
+/* debug (tests and diagnosis only): copy a named intermediate of the last crfp_rt_forward_clip on `workspace` (same geometry) out of it,
+ * with the contract of crfp_dsv_debug_fetch: out_nchw == NULL returns the item count and fills c / h / w_out; otherwise Q4 / P4 buffers
+ * are converted to NCHW on `stream` (the pad stripped), the [H][W][2] flow fields `flow2` / `flow8` and the split-fp16 images
+ * `offfeat0..2` (c = 32: 2 x 4 planes of [H][W] 8 x fp16, x = x0 + x1 * 2^-11) are copied as they are.  Names: flow_lr (t - 1 items, channels
+ * 0 and 1 = dx, dy), x_lr, x_hr (t items); of the last frame: state, state_w, prev2, prev2w, carry, carryw, offfeat0..2, aligned0..2,
+ * poff, al3, feat2 and its parity set's flow2, flow8, win, upw.  CRFP_E_BADARG (crfp_last_error) for an unknown name, a bad geometry, or a
+ * buffer only frames >= 1 write when t = 1. */
+int crfp_rt_debug_fetch(const char* name, int t, int h, int w, int fh, int fw, int wp_h, int wp_w, const void* workspace,
+                        float* out_nchw, int* c_out, int* h_out, int* w_out, void* stream);
 
 #ifdef __cplusplus
 }

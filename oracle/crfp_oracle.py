@@ -63,11 +63,11 @@ _TAP = [None]
 @contextlib.contextmanager
 def tapping(store: dict):
     """Record named intermediates of dsv_frame (names = workspace buffers of the engine, crfp_dsv_debug_fetch) for bisecting."""
-    _TAP[0] = store
+    outer, _TAP[0] = _TAP[0], store
     try:
         yield store
     finally:
-        _TAP[0] = None
+        _TAP[0] = outer
 
 
 def tap(name: str, x: Tensor) -> Tensor:

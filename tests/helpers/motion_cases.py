@@ -81,6 +81,45 @@ def steered_case(regime, t, h, w, seed=CLIP_SEED, y_only=False, weights_seed=7):
     return (sd,) + steered_frames(seed, t, h, w, REGIMES[regime])
 
 
+# ----------------------------------------------------------------------------- the regional wiring: steered window cases
+# MRCF_simple_v18's FNet sees only the top-left LR window (warp_size / 8) of the frames, so every regime statistic of these cases is taken
+# "in-window": ``flow_stats(flow, whl, wwl)`` on the window's own flow.  The `edge` regime is for windows of 8 to 13 LR pixels: a +-24 px
+# flow empties such a window, and FNet's three poolings leave one nearly uniform vector per frame.  Seeds were picked on the CPU oracle like
+# CLIP_SEED (tests/test_motion_cases.py re-checks every row); pick another seed rather than loosen a condition.
+WINDOW_REGIMES = dict(REGIMES, edge=5.0)
+#                name: (frame h x w, warp_size, fovea fh x fw, regimes, seed)
+WINDOW_CASES = {
+    "inside": ((33, 47), (192, 320), (64, 64), ("moderate", "large", "saturating"), 8),
+    "full-width": ((24, 40), (128, 320), (64, 64), ("moderate", "large", "saturating"), 8),
+    "whole-ragged": ((17, 27), (136, 216), (40, 40), ("moderate", "saturating"), 8),      # large at seed 8 leaves 1 % in-window: not used
+    "ragged-window": ((21, 30), (72, 104), (96, 56), ("edge",), 7),    # FNet resizes 9 x 13 to 8 x 8; the fovea crosses the window's bottom edge
+    "smallest": ((16, 40), (64, 64), (48, 48), ("edge",), 3),           # the smallest legal window, with state carried
+}
+WINDOW_BATCH_SEED = 4     # full-width/large with this seed is the second clip of the n = 2 test: in the large regime as well (y_only weights)
+WINDOW_ROWS = [(name, regime) for name, row in WINDOW_CASES.items() for regime in row[3]]
+
+
+def runtime_shapes(y_only=False):
+    """{key: shape} of the regional model's state dict (crfp_amd.model.CRFP_runtime.MRCF_simple_v18, mid_channels = 32), built on the CPU."""
+    from crfp_amd.model import CRFP_runtime
+    m = CRFP_runtime.MRCF_simple_v18(torch.device("cpu"), mid_channels=32, y_only=y_only, hr_dcn=True, offset_prop=True, split_ratio=3)
+    return {k: tuple(v.shape) for k, v in m.state_dict().items()}
+
+
+def window_case(name, regime=None, seed=None, t=3, y_only=False, weights_seed=3):
+    """(steered state dict, lrs[1,t,3,h,w], fvs[1,t,3,fh,fw], warp_size) of one row of WINDOW_CASES: ``steer_fnet`` over
+    ``make_state_dict_like`` of the regional model's shapes, ``steered_frames`` (blk = 8) at the regime's M, and a random fovea crop."""
+    (h, w), warp, (fh, fw), regimes, row_seed = WINDOW_CASES[name]
+    regime = regimes[0] if regime is None else regime
+    if regime not in regimes:
+        raise KeyError(f"window case {name!r} has no {regime!r} regime")
+    seed = row_seed if seed is None else seed
+    sd = steer_fnet(synth.make_state_dict_like(runtime_shapes(y_only), weights_seed))
+    lrs = steered_frames(seed, t, h, w, WINDOW_REGIMES[regime])[0]
+    fvs = np.random.RandomState(1000 + seed).rand(1, t, 3, fh, fw).astype(np.float32)
+    return sd, lrs, fvs, warp
+
+
 def flow_stats(flow, h, w):
     """flow[..., 2, h, w] in pixels (x, y) -> in-frame share (-1 < x + fx < w and -1 < y + fy < h), share of max(|fx|, |fy|) > 8 (and > 16),
     share of positive values per component, absolute maximum."""
@@ -102,6 +141,11 @@ def assert_regime(s, regime):
     """The regime conditions: conditions on the flow a test really uses, not measurements."""
     if regime == "saturating":
         assert s["in_frame"] <= 0.05 and s["absmax"] >= 200.0, s
+        return
+    if regime == "edge":      # windows of 8 to 13 LR pixels: above the 2 px of every small-motion test, both signs on both axes over the clip's flows
+        assert 0.15 <= s["in_frame"] <= 0.85, s
+        assert s["absmax"] >= 2.5, s
+        assert all(0.0 < p < 1.0 for p in s["pos"]), s
         return
     assert 0.15 <= s["in_frame"] <= 0.85, s
     assert s["over8"] >= 0.5, s

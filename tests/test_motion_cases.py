@@ -41,6 +41,81 @@ def test_steered_regimes_through_the_oracle(orc, regime, h, w):
     assert lrs.min() >= 0.0 and lrs.max() <= 1.0
 
 
+@pytest.mark.parametrize("name,regime", mc.WINDOW_ROWS)
+def test_window_cases_through_the_oracle(orc, name, regime):
+    """The regional wiring's rows: FNet sees the top-left LR window only, so the conditions are taken in-window, on the flow of the window crop."""
+    sd, lrs, fvs, warp = mc.window_case(name, regime)
+    (h, w), _, (fh, fw), _, _ = mc.WINDOW_CASES[name]
+    whl, wwl = warp[0] // 8, warp[1] // 8
+    flow = orc.compute_flow(orc.load_numpy_state(sd), T(lrs)[:, :, :, :whl, :wwl])
+    s = mc.flow_stats(flow, whl, wwl)
+    print(f"{name}/{regime} window {whl}x{wwl} of {h}x{w}: {mc.fmt_stats(s)}; frame means "
+          + ", ".join(f"({float(f[0].mean()):.2f}, {float(f[1].mean()):.2f})" for f in flow[0]))
+    mc.assert_regime(s, regime)
+    assert lrs.shape == (1, 3, 3, h, w) and fvs.shape == (1, 3, 3, fh, fw) and lrs.min() >= 0.0 and lrs.max() <= 1.0
+    assert warp[0] % 8 == 0 and warp[1] % 8 == 0 and 64 <= warp[0] <= 8 * h and 64 <= warp[1] <= 8 * w and fh <= 8 * h and fw <= 8 * w
+    if regime == "edge":
+        assert min(whl, wwl) <= 13 and s["absmax"] < 8.0      # what the regime is for: a small window that the +-24 px regimes would empty
+
+
+def test_window_batch_seed_is_in_the_large_regime(orc):
+    """The second clip of the n = 2, y_only GPU test: full-width/large at WINDOW_BATCH_SEED, another clip than the row's own."""
+    sd, lrs, _, warp = mc.window_case("full-width", "large", seed=mc.WINDOW_BATCH_SEED, y_only=True)
+    assert mc.WINDOW_BATCH_SEED != mc.WINDOW_CASES["full-width"][4] and sd["conv_last.weight"].shape[0] == 1
+    whl, wwl = warp[0] // 8, warp[1] // 8
+    s = mc.flow_stats(orc.compute_flow(orc.load_numpy_state(sd), T(lrs)[:, :, :, :whl, :wwl]), whl, wwl)
+    print(f"full-width/large seed {mc.WINDOW_BATCH_SEED}: {mc.fmt_stats(s)}")
+    mc.assert_regime(s, "large")
+
+
+def test_window_rows_are_the_stated_table():
+    assert mc.WINDOW_ROWS == [("inside", "moderate"), ("inside", "large"), ("inside", "saturating"), ("full-width", "moderate"),
+                              ("full-width", "large"), ("full-width", "saturating"), ("whole-ragged", "moderate"), ("whole-ragged", "saturating"),
+                              ("ragged-window", "edge"), ("smallest", "edge")]
+    assert mc.WINDOW_REGIMES == dict(mc.REGIMES, edge=5.0) and "edge" not in mc.REGIMES
+    assert mc.WINDOW_CASES["smallest"][1] == (64, 64)                                   # the smallest legal window
+    (h, w), warp, (fh, fw), _, _ = mc.WINDOW_CASES["ragged-window"]
+    assert fh > warp[0] and fw < warp[1] and fh <= 8 * h                                # the fovea is taller than the window: it crosses its bottom edge
+    with pytest.raises(KeyError):
+        mc.window_case("whole-ragged", "large")
+    with pytest.raises(AssertionError):                                                 # one sign per axis is no edge regime
+        mc.assert_regime({"in_frame": 0.5, "absmax": 3.0, "pos": (1.0, 0.5), "over8": 0.0, "over16": 0.0}, "edge")
+    with pytest.raises(AssertionError):
+        mc.assert_regime({"in_frame": 0.5, "absmax": 2.0, "pos": (0.5, 0.5), "over8": 0.0, "over16": 0.0}, "edge")
+
+
+def test_runtime_oracle_takes_a_flow_and_gives_taps(orc):
+    """``runtime_forward(flows=, taps=)``: its own flow handed back in changes no bit, the taps carry every fetch name with the buffer's
+    shape, a float64 run stays within 1e-5 of the fp32 one, and a wrong flow shape is refused."""
+    from oracle import runtime_oracle as ro
+    sd, lrs, fvs, warp = mc.window_case("smallest")
+    P, L, Fv = orc.load_numpy_state(sd), T(lrs), T(fvs)
+    (h, w), _, (fh, fw), _, _ = mc.WINDOW_CASES["smallest"]
+    flows = orc.compute_flow(P, L[:, :, :, :8, :8])
+    taps = {}
+    plain = ro.runtime_forward(P, L, Fv, warp)
+    assert torch.equal(ro.runtime_forward(P, L, Fv, warp, flows=flows, taps=taps), plain)
+    shapes = {"flow_lr": (2, 2, 8, 8), "x_lr": (3, 32, h, w), "x_hr": (3, 4, fh, fw), "state": (1, 4, 64, 64), "state_w": (1, 4, 64, 64),
+              "prev2": (1, 32, 16, 16), "prev2w": (1, 32, 16, 16), "carry": (1, 24, 16, 16), "carryw": (1, 24, 16, 16), "poff": (1, 4, 64, 64),
+              "al3": (1, 4, 64, 64), "feat2": (1, 4, 8 * h, 8 * w), "flow2": (1, 16, 16, 2), "flow8": (1, 64, 64, 2), "win": (1, 24, 16, 16),
+              "upw": (1, 4, 64, 64), "tttf": (1, 4, fh, fw), "feat_pre": (1, 4, 8 * h, 8 * w)}
+    shapes.update({f"offfeat{k}": (1, 32, 16, 16) for k in range(3)})
+    shapes.update({f"aligned{k}": (1, 32, 16, 16) for k in range(3)})
+    assert {k: tuple(v.shape) for k, v in taps.items()} == shapes
+    assert torch.equal(taps["state"], taps["feat2"][:, :, :64, :64]) and torch.equal(taps["feat2"][:, :, :fh, :fw], taps["tttf"])
+    assert torch.equal(taps["feat2"][:, :, fh:], taps["feat_pre"][:, :, fh:]) and not torch.equal(taps["feat2"], taps["feat_pre"])
+    ref64 = ro.runtime_forward({k: v.double() for k, v in P.items()}, L.double(), Fv.double(), warp, flows=flows)
+    assert ref64.dtype == torch.float64 and float((plain.double() - ref64).abs().max()) < 1e-5
+    moved = ro.runtime_forward(P, L[:, :2], Fv[:, :2], warp, flows=flows[:, :1] * 0)
+    assert float((moved[:, 1] - plain[:, 1]).abs().max()) > 1e-2                          # the flow reaches the output
+    with pytest.raises(ValueError):
+        ro.runtime_forward(P, L, Fv, warp, flows=flows[:, :1])
+    with orc.tapping({}) as outer:                                                        # the oracle's own taps survive the nested use
+        ro.runtime_forward(P, L[:, :2], Fv[:, :2], warp)
+        orc.tap("after", L)
+    assert "after" in outer
+
+
 def test_steered_flow_is_the_stated_function_of_the_frames(orc):
     """flow_x = 256 tanh(g blur(R - G)), flow_y = 256 tanh(g blur(B - R_prev)); only the spynet.* tensors change."""
     from crfp_amd import synth

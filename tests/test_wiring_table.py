@@ -43,7 +43,10 @@ def test_rows_name_the_five_families():
     assert [r.names for r in _lib.FAMILIES.values()] == ["dsv", "cra", "dsv", "dsv", "rt"]
     assert [r.num_params for r in _lib.FAMILIES.values()] == [_lib.NUM_PARAMS, _lib.CRA_NUM_PARAMS, _lib.NUM_PARAMS, _lib.NUM_PARAMS, _lib.RT_NUM_PARAMS]
     assert _lib.FAMILIES["dsv"].ops == DSV_OPS
-    assert _lib.FAMILIES["rt"].ops == {"param_numel", "packed_weight_bytes", "pack_weights", "workspace_bytes", "forward_clip"}
+    assert _lib.FAMILIES["rt"].ops == {"param_numel", "packed_weight_bytes", "pack_weights", "workspace_bytes", "forward_clip", "debug_fetch"}
+    # the regional fetch takes the seven-number geometry: an argument list of its own, not CRFP_DSV's
+    assert _lib.SIGNATURES["crfp_rt_debug_fetch"] != _lib.SIGNATURES["crfp_dsv_debug_fetch"]
+    assert len(_lib.SIGNATURES["crfp_rt_debug_fetch"][1]) == len(_lib.SIGNATURES["crfp_dsv_debug_fetch"][1]) + 4
     for row in _lib.FAMILIES.values():
         assert row.bf16 <= row.ops and "param_numel" not in row.bf16
     assert not _lib.FAMILIES["rt"].bf16
@@ -95,6 +98,12 @@ def test_runtime_handle_reads_its_row():
     assert (e.WIRING, e.MODEL_NAME, e.storage) == ("rt", "MRCF_simple_v18", "f32")
     with pytest.raises(NotImplementedError):
         e._call("forward_batch")
+    e._fns = dict.fromkeys(_lib.FAMILIES["rt"].ops, "bound")
+    for op in _lib.FAMILIES["rt"].ops:
+        assert e._call(op) == "bound"
+    assert _lib.symbol("rt", "debug_fetch") == _lib.symbol("rt", "debug_fetch", "bf16") == "crfp_rt_debug_fetch"
+    with pytest.raises(RuntimeError, match="before any forward"):      # no forward yet: nothing is read, the library is not called
+        e.debug_fetch("state")
     assert engine.RuntimeEngine.WEIGHT_LIMIT_SPLIT == engine.DSVEngine.WEIGHT_LIMIT_SPLIT == 32.0
 
 

@@ -829,6 +829,40 @@ int main() {
         }
         EXPECT(crfp_rt_forward_clip(pk, 0, lrs, fvs, out, 5, 135, 240, 96, 96, 720, 720, wsp, crfp_rt_workspace_bytes(5, 135, 240, 96, 96, 720, 720), stream) == 0);
         EXPECT(crfp_rt_forward_clip(pk, CRFP_DSV_STRICT_F32, lrs, fvs, out, 5, 135, 240, 96, 96, 720, 720, wsp, (size_t)1 << 40, stream) != 0);
+        // the regional debug fetch: every refusal before the first launch, the size query launches nothing, a fetch is one launch or one copy
+        {
+            int c = -1, hh = -1, ww = -1;
+            const long l1 = crfp_stub_launches();
+            EXPECT(crfp_rt_debug_fetch(nullptr, 5, 135, 240, 96, 96, 720, 720, wsp, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+            EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+            EXPECT(crfp_rt_debug_fetch("state", 5, 135, 240, 96, 96, 720, 720, nullptr, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+            EXPECT(crfp_rt_debug_fetch("no_such_buffer", 5, 135, 240, 96, 96, 720, 720, wsp, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+            EXPECT(std::strstr(crfp_last_error_string(), "unknown buffer 'no_such_buffer'") != nullptr);
+            EXPECT(crfp_rt_debug_fetch("", 5, 135, 240, 96, 96, 720, 720, wsp, out, nullptr, nullptr, nullptr, stream) == CRFP_E_BADARG);
+            EXPECT(crfp_rt_debug_fetch("state", 5, 135, 240, 96, 96, 724, 720, wsp, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);    // warp_size no multiple of 8
+            EXPECT(std::strstr(crfp_last_error_string(), "warp_size") != nullptr);
+            EXPECT(crfp_rt_debug_fetch("state", 0, 135, 240, 96, 96, 720, 720, wsp, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+            EXPECT(crfp_rt_debug_fetch("state", 5, 135, 240, 2000, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+            EXPECT(crfp_rt_debug_fetch("state_w", 1, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == CRFP_E_BADARG);  // one frame warps nothing
+            EXPECT(std::strstr(crfp_last_error_string(), "frames >= 1") != nullptr);
+            EXPECT(c == -1 && hh == -1 && ww == -1);                                                                                   // a refusal fills nothing in
+            EXPECT(crfp_rt_debug_fetch("state", 1, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 4 && hh == 720 && ww == 720);
+            EXPECT(crfp_rt_debug_fetch("flow_lr", 5, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 4 && c == 4 && hh == 90 && ww == 90);
+            EXPECT(crfp_rt_debug_fetch("x_lr", 5, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 5 && c == 32 && hh == 135 && ww == 240);
+            EXPECT(crfp_rt_debug_fetch("x_hr", 5, 135, 240, 96, 80, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 5 && c == 4 && hh == 96 && ww == 80);
+            EXPECT(crfp_rt_debug_fetch("carry", 5, 135, 240, 96, 96, 720, 712, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 24 && hh == 180 && ww == 178);
+            EXPECT(crfp_rt_debug_fetch("offfeat1", 5, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 32 && hh == 180 && ww == 180);
+            EXPECT(crfp_rt_debug_fetch("flow8", 5, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 2 && hh == 720 && ww == 720);
+            EXPECT(crfp_rt_debug_fetch("feat2", 5, 135, 240, 96, 96, 720, 720, wsp, nullptr, nullptr, nullptr, nullptr, stream) == 1);
+            EXPECT(crfp_rt_debug_fetch("feat2", 5, 135, 240, 96, 96, 720, 720, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 4 && hh == 1080 && ww == 1920);
+            EXPECT(crfp_stub_launches() == l1);
+            const char* const names[] = {"flow_lr", "x_lr", "x_hr", "state", "state_w", "prev2", "prev2w", "carry", "carryw", "offfeat0", "offfeat1", "offfeat2",
+                                         "aligned0", "aligned1", "aligned2", "poff", "al3", "feat2", "flow2", "flow8", "win", "upw"};
+            for (const char* nm : names)
+                for (int t : {2, 5})
+                    EXPECT(crfp_rt_debug_fetch(nm, t, 135, 240, 96, 96, 720, 720, wsp, out, nullptr, nullptr, nullptr, stream) == 0);
+            EXPECT(crfp_stub_launches() == l1 + 2 * (22 - 5));   // the two flow fields and the three split-fp16 images are copies
+        }
         EXPECT(crfp_fnet_forward(pk, lrs, lrs, out, 2, 180, 320, wsp, crfp_dsv_workspace_bytes(3, 180, 320), stream) == 0);
         EXPECT(crfp_debug_side_tables() >= 1);
         EXPECT(crfp_shutdown() == 0);

@@ -1,6 +1,7 @@
 """Bisect the engine against the oracle: run a 2-frame clip, fetch named workspace intermediates of frame 1
 (crfp_dsv_debug_fetch) and print max / mean |delta| per tensor against the oracle's taps.
-  python tools/bisect_engine.py [--storage bf16] [--h 24 --w 40]"""
+  python tools/bisect_engine.py [--storage bf16] [--h 24 --w 40]
+  python tools/bisect_engine.py --rt [--h 24 --w 40 --fv 64 --warp 128 192]    the regional runtime engine (crfp_rt_debug_fetch)"""
 import argparse
 import os
 import sys
@@ -20,9 +21,43 @@ ap.add_argument("--storage", default="f32")
 ap.add_argument("--h", type=int, default=24)
 ap.add_argument("--w", type=int, default=40)
 ap.add_argument("--fv", type=int, default=64)
+ap.add_argument("--rt", action="store_true", help="the regional runtime engine (crfp_rt_debug_fetch) instead of CRFP_DSV")
+ap.add_argument("--warp", type=int, nargs=2, default=(128, 192), help="--rt: warp_size")
 a = ap.parse_args()
 T = torch.from_numpy
 dev = torch.device("cuda:0")
+
+
+def show(name, got, want):
+    got, want = got.float().cpu(), want.float()
+    if got.shape != want.shape:
+        print(f"{name:24s} SHAPE {tuple(got.shape)} vs {tuple(want.shape)}")
+        return
+    d = (got - want).abs()
+    print(f"{name:24s} max {float(d.max()):.3e} mean {float(d.mean()):.3e}  (|ref| max {float(want.abs().max()):.2e})")
+
+
+if a.rt:   # frame 1 of a 2-frame clip: every fetch name against the fp32 oracle's tap, run with the engine's own flow
+    from crfp_amd.model import MRCF_runtime
+    from oracle import runtime_oracle as ro
+    m = MRCF_runtime.MRCF_simple_v18(dev, mid_channels=32)
+    sd = synth.make_state_dict_like({k: tuple(v.shape) for k, v in m.state_dict().items()}, 3)
+    m.load_state_dict({k: T(v.copy()) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    rs = np.random.RandomState(5)
+    lrs, fvs = T(rs.rand(1, 2, 3, a.h, a.w).astype(np.float32)), T(rs.rand(1, 2, 3, a.fv, a.fv).astype(np.float32))
+    with torch.no_grad():
+        out = m(lrs.to(dev), fvs.to(dev), warp_size=tuple(a.warp)).cpu()
+        eng = m.engine()
+        taps = {}
+        ref = ro.runtime_forward(orc.load_numpy_state(sd), lrs, fvs, tuple(a.warp), flows=eng.debug_fetch("flow_lr")[None, :, :2].cpu(), taps=taps)
+    for n in ("x_lr", "x_hr", "flow2", "flow8", "win", "upw", "state_w", "prev2w", "prev2", "carryw", "offfeat0", "aligned0", "offfeat1", "aligned1",
+              "offfeat2", "aligned2", "poff", "al3", "carry", "feat2", "state"):
+        show(n, eng.debug_fetch(n), taps[n])
+    show("out frame 0", out[:, 0], ref[:, 0])
+    show("out frame 1", out[:, 1], ref[:, 1])
+    sys.exit(0)
+
 sd = synth.make_state_dict(7)
 t, h, w = 2, a.h, a.w
 lrs, fvs, mks = synth.make_clip(3, 1, t, h, w, fv_size=a.fv)
@@ -40,16 +75,6 @@ with torch.no_grad():
         P = orc.bf16_weights(P)
     with ctx, orc.tapping(taps):
         ref = orc.crfp_dsv_forward(P, T(lrs), T(fvs), T(mks))
-
-
-def show(name, got, want):
-    got, want = got.float().cpu(), want.float()
-    if got.shape != want.shape:
-        print(f"{name:24s} SHAPE {tuple(got.shape)} vs {tuple(want.shape)}")
-        return
-    d = (got - want).abs()
-    print(f"{name:24s} max {float(d.max()):.3e} mean {float(d.mean()):.3e}  (|ref| max {float(want.abs().max()):.2e})")
-
 
 f = lambda n: eng.debug_fetch(n, t, h, w)  # noqa: E731
 # frame 1 lives in parity set 1
