@@ -169,16 +169,17 @@ def fnet(P, pre: str, x1: Tensor, x2: Tensor) -> Tensor:
     """FNet.forward (model/CRFP.py:797-814; layers :747-795): flow from x1 to x2, [n,2,h,w]."""
     _, _, h, w = x1.shape
     o = torch.cat([x1, x2], dim=1)
-    for blk in ("encoder1", "encoder2", "encoder3"):
-        o = R(F.relu(conv(P, f"{pre}{blk}.0", o)))
-        o = R(F.relu(conv(P, f"{pre}{blk}.2", o)))
-        o = R(F.avg_pool2d(o, 2, 2))
-    for blk in ("decoder1", "decoder2", "decoder3"):
-        o = R(F.relu(conv(P, f"{pre}{blk}.0", o)))
-        o = R(F.relu(conv(P, f"{pre}{blk}.2", o)))
-        o = R(up_bilinear(o, 2))
-    o = conv(P, pre + "flow.2", R(F.relu(conv(P, pre + "flow.0", o))))     # the flow itself stays fp32
-    o = torch.tanh(o) * 256
+    # taps: the engine's FNet buffers fnet.a0 .. fnet.g1 (conv, conv, pool / resize per block)
+    for blk, (a, b, c) in zip(("encoder1", "encoder2", "encoder3"), (("a0", "a1", "p1"), ("b0", "b1", "p2"), ("c0", "c1", "p3"))):
+        o = tap("fnet." + a, R(F.relu(conv(P, f"{pre}{blk}.0", o))))
+        o = tap("fnet." + b, R(F.relu(conv(P, f"{pre}{blk}.2", o))))
+        o = tap("fnet." + c, R(F.avg_pool2d(o, 2, 2)))
+    for blk, (a, b, c) in zip(("decoder1", "decoder2", "decoder3"), (("d0", "d1", "u1"), ("e0", "e1", "u2"), ("f0", "f1", "u3"))):
+        o = tap("fnet." + a, R(F.relu(conv(P, f"{pre}{blk}.0", o))))
+        o = tap("fnet." + b, R(F.relu(conv(P, f"{pre}{blk}.2", o))))
+        o = tap("fnet." + c, R(up_bilinear(o, 2)))
+    o = conv(P, pre + "flow.2", tap("fnet.g0", R(F.relu(conv(P, pre + "flow.0", o)))))     # the flow itself stays fp32
+    o = tap("fnet.g1", torch.tanh(o) * 256)
     return F.interpolate(o, size=(h, w), mode="bilinear", align_corners=False)
 
 
@@ -236,8 +237,8 @@ def pixel_unshuffle_pack_v2(P, pre: str, x: Tensor, r: int) -> Tensor:
 def resblocks_with_input_conv(P, pre: str, x: Tensor) -> Tensor:
     """ResidualBlocksWithInputConv(in,out,1).forward (model/CRFP.py:516-552 + :433-481):
     conv -> LReLU(0.1) -> one ResidualBlockNoBN (x + conv2(ReLU(conv1(x))), res_scale 1)."""
-    x = R(lrelu(conv(P, pre + "main.0", x)))
-    return R(x + conv(P, pre + "main.2.0.conv2", R(F.relu(conv(P, pre + "main.2.0.conv1", x)))))
+    x = tap(pre + "main0", R(lrelu(conv(P, pre + "main.0", x))))
+    return R(x + conv(P, pre + "main.2.0.conv2", tap(pre + "conv1", R(F.relu(conv(P, pre + "main.2.0.conv1", x))))))
 
 
 def dcn_module(P, pre: str, cur: Tensor, prev: Tensor, prev_warped: Tensor, flow: Tensor,
@@ -309,7 +310,7 @@ def dsv_frame(P, cfg: DSVConfig, st, lr: Tensor, fv: Tensor, mk: Tensor, flow: O
     n, _, h, w = lr.shape
     mkf = mk.float()
     lr8 = up_bilinear(lr, 8)                                                  # :1538
-    x_lr = tap("x_lr", R(lrelu(conv(P, "encoder_lr.slice1.2", R(lrelu(conv(P, "encoder_lr.slice1.0", lr)))))))  # :1540
+    x_lr = tap("x_lr", R(lrelu(conv(P, "encoder_lr.slice1.2", tap("enc_lr0", R(lrelu(conv(P, "encoder_lr.slice1.0", lr))))))))  # :1540
     fvb = fv * mkf + lr8 * (1 - mkf)                                          # :1544
     x_hr = torch.cat((R(fvb), R(lr8)), dim=1)                                 # :1547 (staged as conv input; the head keeps the fp32 lr8)
     tap("xin8", x_hr)
@@ -321,6 +322,7 @@ def dsv_frame(P, cfg: DSVConfig, st, lr: Tensor, fv: Tensor, mk: Tensor, flow: O
         flow8 = up_bilinear(flow, 8) * 8.0                                    # :1566
         prev_hr = st["hr"]                                                    # :1568
         tap("flow2", flow2.permute(0, 2, 3, 1))
+        tap("flow8", flow8.permute(0, 2, 3, 1))
         prev2 = tap("prev2", R(pixel_unshuffle_pack_v2(P, "downsample.", prev_hr, 4)))   # :1569 [n,32,2h,2w]
         prev2_w = tap("prev2w", R(flow_warp(prev2, flow2.permute(0, 2, 3, 1))))          # :1570
         prev_hr_w = tap("prevhrw", R(flow_warp(prev_hr, flow8.permute(0, 2, 3, 1))))     # :1571
@@ -357,6 +359,7 @@ def dsv_frame(P, cfg: DSVConfig, st, lr: Tensor, fv: Tensor, mk: Tensor, flow: O
         up = R(lrelu(pixel_shuffle_pack(P, "upsample_post.", prop, 4)))       # :1664
         feat = resblocks_with_input_conv(P, "forward_resblocks_3.", torch.cat([up, st["hr"]], dim=1))  # :1666-1667
 
+    tap("carry", torch.cat(new_carry, dim=1))                                 # the three carried slices the next frame warps
     fused = conv(P, "conv_tttf", torch.cat([feat, x_hr], dim=1))              # :1672-1673
     feat = tap("state_hr", R(lrelu(mkf * fused + (1 - mkf) * feat)))          # :1674-1675 (the new recurrent state)
     out = conv(P, "conv_last", feat)                                          # :1678
