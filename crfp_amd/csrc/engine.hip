@@ -305,9 +305,6 @@ struct Layout {
     long long gate_b;
     int h1, w1, h2, w2, h3, w3;
     int fnet_cap;   // pairs one FNet pass can hold
-    // FNet's small maps run their convs in K slices (conv_auto_ksplit): the float partial tensors of the layer in flight (the largest layer's ks * cout * H * W
-    // floats per pair)
-    Ten fpart;
 
     Layout(int B_, int t_, int h_, int w_, int wiring = W_DSV) : B(B_), t(t_), h(h_), w(w_), cra(wiring == W_CRA), pq(wiring >= W_SIMPLE ? 8 : 6) {
         flat = (long long)B * t <= kFlatFrames;
@@ -348,17 +345,6 @@ struct Layout {
         fu3 = A.take("fnet.u3", nb, 16, 8 * h3, 8 * w3);
         fg0 = A.take("fnet.g0", nb, 8, 8 * h3, 8 * w3);
         fg1 = A.take("fnet.g1", nb, 1, 8 * h3, 8 * w3, 0, 0, true);
-        {
-            const int lh[7] = {h, h1, h2, h3, 2 * h3, 4 * h3, 8 * h3}, lw[7] = {w, w1, w2, w3, 2 * w3, 4 * w3, 8 * w3};
-            long long most = 0;
-            for (int i = 0; i < 14; ++i) {
-                const int kq = (kConvs[i].cin / 4 + 3) / 4 * 4, H = lh[i / 2], W = lw[i / 2];
-                const int ks = H > 0 && W > 0 ? conv_auto_ksplit(H, W, (kConvs[i].cout + 31) / 32, kq) : 1;
-                if (ks > 1) most = std::max(most, (long long)ks * kConvs[i].cout * H * W);
-            }
-            const long long per = (long long)h * w * 4;
-            fpart = A.take("fnet.part", nb, (int)((most + per - 1) / per), h, w, 0, 0, true);
-        }
         // state-independent per-frame work (fovea blend, encoder_hr, upsample conv, flow upsampling) is
         // produced one or two frames ahead on a side stream -> two buffer sets, indexed by frame parity
         for (int p = 0; p < 2; ++p) {
@@ -633,14 +619,13 @@ struct Runner {
 #else
     static constexpr int chain_mask() { return kActBf16 ? CRFP_NARROW_CHAIN_BF16 : CRFP_NARROW_CHAIN; }
 #endif
-    // which 8x-resolution conv pairs run fused (bit 0: encoder_hr.0->.2, 1: dcn_3 conv_fuse->offset/mask, 2: res3 conv1->conv2,
-    // 3: dcn_3 block.0->.2).  Measured @A fp32, pair vs the two single kernels: res3 47.2 vs 57.8 us (bf16 46.7 vs 56.1);
-    // encoder_hr 71.5 vs 67.6; conv_fuse->offset/mask 80 vs 76.8; dcn_3 block (3 input quads, one workgroup per CU) 126 vs 93.7.
-    // The stencils are bound by 4x4x1-MFMA issue and LDS reads, not by HBM, and the fused form evaluates conv A on 1.16x the
-    // pixels with 9 instead of 4.5 LDS reads per pixel and tap row -- so only the pair whose A has ONE input quad wins.
-    // narrow conv pairs fused into one launch: res3.conv1 -> conv2(+x) wins in the fp32 build; in the bf16 build the
-    // single convs run on the bf16 MFMA and two of them beat the pair kernel (41 vs 47.5 us)
-    static constexpr int pair_mask() { return kActBf16 ? 0 : 4; }
+    // The one 8x-resolution conv pair that runs fused into one launch: res3.conv1 -> conv2(+x), fp32 build only.  Measured @A
+    // fp32, pair vs the two single kernels: res3 47.2 vs 57.8 us (bf16 46.7 vs 56.1).  Three more pairs were measured, lost and have no call
+    // site any more: encoder_hr.0->.2 71.5 vs 67.6; dcn_3 conv_fuse->offset/mask 80 vs 76.8; dcn_3 block.0->.2 (3 input quads, one workgroup
+    // per CU) 126 vs 93.7.  The stencils are bound by 4x4x1-MFMA issue and LDS reads, not by HBM, and the fused form evaluates conv A on
+    // 1.16x the pixels with 9 instead of 4.5 LDS reads per pixel and tap row -- so only the pair whose A has ONE input quad wins.  In the
+    // bf16 build the single convs run on the bf16 MFMA and two of them beat the pair kernel (41 vs 47.5 us).
+    static constexpr bool res3_pair = !kActBf16;
 #ifndef CRFP_STATE_FROM_EPILOGUE
 #define CRFP_STATE_FROM_EPILOGUE 1   // A/B builds: 0 = the separate lrelu pass
 #endif
@@ -693,46 +678,25 @@ struct Runner {
         Q4 g0 = q(L.fg0, 8, 8 * L.h3, 8 * L.w3), g1 = q(L.fg1, 1, 8 * L.h3, 8 * L.w3), fl = q(L.flow_lr, 1, h, w);
         fl.p = flow_out;
         mfma(IT_F0, nb, h, w, {{cur, cur_bs}, {prev, prev_bs}}, {{a0.p, a0.bs(), 0, 8}}, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, group);
-        // Round 6: a layer over a small map runs in K slices (conv_auto_ksplit: the layer's geometry decides, never the number of pairs, so one pair per
-        // call and a clip's pairs compute the same bits); its partial tensors are added by the pool / resize pass behind it -- which reads the layer
-        // anyway -- or by launch_ksplit_reduce.  conv(i, in, out) returns the slices (1: `out` holds the layer as before).
-        KsIn ki;
-        auto conv = [&](int i, const Q4& in, const Q4& out) {
-            const Item& it = M.items[IT_F0 + i];
-            static const bool env_strict = precision_env_strict(0);
-            const int ks = (strict || env_strict || rc) ? 1 : conv_auto_ksplit(in.H, in.W, it.c.ctiles, it.c.kq);
-            if (ks < 2) { mfma_q(IT_F0 + i, nb, in, out); return 1; }
-            const long long pb = out.bs();   // floats of one (pair, slice): the layer's quads
-            ConvArgs a = plan(IT_F0 + i, nb, in.H, in.W, {{in.p, in.bs()}}, {{F(L.fpart), pb, 0, out.nq}});
-            a.ksplit = ks;
-            ki.part = F(L.fpart); ki.pb = pb; ki.ks = ks; ki.act = it.c.act;
-            ki.ovf = ovf(); ki.ovf_div = ovf_div; ki.ovf_add = ovf_add;
-            rc = launch_conv_ksplit(a, it.name, s);
-            return ks;
-        };
-        auto reduce = [&](int ks, const Q4& out) {   // the layer as an ordinary tensor (its reader is another conv)
-            if (ks > 1) RUN(launch_ksplit_reduce(ki.part, ki.pb, ks, out.p, out.bs(), nb, out.nq, out.H, out.W, ki.act, ki.ovf, ki.ovf_div, ki.ovf_add, s));
-        };
-        auto pool = [&](int ks, const Q4& in, const Q4& out) {
-            if (ks > 1) RUN(launch_avgpool2_q4_ks(ki, out.p, out.bs(), nb, in.nq, in.H, in.W, s));
-            else RUN(launch_avgpool2_q4(in.p, in.bs(), out.p, out.bs(), nb, in.nq, in.H, in.W, s));
-        };
-        auto resize2 = [&](int ks, const Q4& in, const Q4& out) {
-            if (ks > 1) RUN(launch_upsample_q4_ks(ki, out.p, out.bs(), nb, in.nq, in.H, in.W, out.H, out.W, 0.5f, 0.5f, 1.0f, s));
-            else RUN(launch_upsample_q4(in.p, in.bs(), out.p, out.bs(), nb, in.nq, in.H, in.W, out.H, out.W, 0.5f, 0.5f, 1.0f, s, 0));
-        };
-        pool(conv(1, a0, a1), a1, p1);
-        reduce(conv(2, p1, b0), b0);
-        pool(conv(3, b0, b1), b1, p2);
-        reduce(conv(4, p2, c0), c0);
-        pool(conv(5, c0, c1), c1, p3);
-        reduce(conv(6, p3, d0), d0);
-        resize2(conv(7, d0, d1), d1, u1);
-        reduce(conv(8, u1, e0), e0);
-        resize2(conv(9, e0, e1), e1, u2);
-        reduce(conv(10, u2, f0), f0);
-        resize2(conv(11, f0, f1), f1, u3);
-        reduce(conv(12, u3, g0), g0);
+        // every layer runs in one piece (K slices over the small maps: measured, lost on a clip's six pairs, removed -- profiles/r06_fnet_ksplit_ab.txt)
+        mfma_q(IT_F0 + 1, nb, a0, a1);
+        RUN(launch_avgpool2_q4(a1.p, a1.bs(), p1.p, p1.bs(), nb, a1.nq, a1.H, a1.W, s));
+        mfma_q(IT_F0 + 2, nb, p1, b0);
+        mfma_q(IT_F0 + 3, nb, b0, b1);
+        RUN(launch_avgpool2_q4(b1.p, b1.bs(), p2.p, p2.bs(), nb, b1.nq, b1.H, b1.W, s));
+        mfma_q(IT_F0 + 4, nb, p2, c0);
+        mfma_q(IT_F0 + 5, nb, c0, c1);
+        RUN(launch_avgpool2_q4(c1.p, c1.bs(), p3.p, p3.bs(), nb, c1.nq, c1.H, c1.W, s));
+        mfma_q(IT_F0 + 6, nb, p3, d0);
+        mfma_q(IT_F0 + 7, nb, d0, d1);
+        RUN(launch_upsample_q4(d1.p, d1.bs(), u1.p, u1.bs(), nb, d1.nq, d1.H, d1.W, u1.H, u1.W, 0.5f, 0.5f, 1.0f, s, 0));
+        mfma_q(IT_F0 + 8, nb, u1, e0);
+        mfma_q(IT_F0 + 9, nb, e0, e1);
+        RUN(launch_upsample_q4(e1.p, e1.bs(), u2.p, u2.bs(), nb, e1.nq, e1.H, e1.W, u2.H, u2.W, 0.5f, 0.5f, 1.0f, s, 0));
+        mfma_q(IT_F0 + 10, nb, u2, f0);
+        mfma_q(IT_F0 + 11, nb, f0, f1);
+        RUN(launch_upsample_q4(f1.p, f1.bs(), u3.p, u3.bs(), nb, f1.nq, f1.H, f1.W, u3.H, u3.W, 0.5f, 0.5f, 1.0f, s, 0));
+        mfma_q(IT_F0 + 12, nb, u3, g0);
         // tanh * 256 flow and its resize to (h, w) stay float in both builds (coordinates)
         mfma(IT_F0 + 13, nb, g0.H, g0.W, {{g0.p, g0.bs()}}, {{g1.p, g1.bs(), 0, g1.nq}}, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 1);
         RUN(crfp::launch_upsample_q4(g1.p, g1.bs(), fl.p, fl.bs(), nb, 1, g1.H, g1.W, h, w, (float)g1.H / (float)h,
@@ -848,16 +812,12 @@ struct Runner {
             // conv_tttf works on the tiles that hold mask pixels and reads x_hr one pixel into their neighbours: encoder_hr's second conv runs on
             // that ring of tiles too, its first conv on two rings, the frame stack on three -- no launch reads a tile nobody wrote.
             // CRFP_DSV_CRA: slice1's output also feeds the three 2x levels, whose reach is wider: only conv_lv3 is gated there.
-            const int gp = (gated && !M.cra && !(pair_mask() & 1)) ? par : -1;
+            const int gp = gated && !M.cra ? par : -1;
             RUN(launch_hr_prep(io.lr, io.fv, io.mk, F(xin), h, w, s, B, io.lr_b, io.fv_b, io.mk_b, xin.bs, gp >= 0 ? gate_ptr(par) : nullptr, L.gate_b));
             // CRFP_DSV_CRA: slice1's output feeds conv_lv3 (-> x_hr, what conv_tttf blends in) and the three 2x levels
             const Ten& s1 = M.cra ? L.c_s1 : L.x_hr[par];
-            if (pair_mask() & 1)
-                narrow_pair(IT_EH0, IT_EH1, "conv_narrow_pair:enc_hr", H8, W8, {{F(xin), xin.bs}, {adv(F(xin), P8q), xin.bs}}, {F(s1), s1.bs});
-            else {
-                narrow(IT_EH0, H8, W8, {{F(xin), xin.bs}, {adv(F(xin), P8q), xin.bs}}, {F(L.eh[par]), L.eh[par].bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 2);
-                narrow(IT_EH1, H8, W8, {{F(L.eh[par]), L.eh[par].bs}}, {F(s1), s1.bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 1);
-            }
+            narrow(IT_EH0, H8, W8, {{F(xin), xin.bs}, {adv(F(xin), P8q), xin.bs}}, {F(L.eh[par]), L.eh[par].bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 2);
+            narrow(IT_EH1, H8, W8, {{F(L.eh[par]), L.eh[par].bs}}, {F(s1), s1.bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 1);
             if (M.cra) {
                 narrow(IT_C_LV3, H8, W8, {{F(s1), s1.bs}}, {F(L.x_hr[par]), L.x_hr[par].bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), par, 1);
                 const Q4 a = q(L.c_a, 4, H2, W2), b = q(L.c_b, 4, H2, W2);
@@ -982,26 +942,19 @@ struct Runner {
                 narrow_chain(IT_D3B0, IT_D3B1, IT_D3FUSE, "conv_narrow_chain:dcn3.block0_block2_fuse", H8, W8, {nb(L.up), nb(L.prevhrw), fl8}, nb(L.poff),
                              nb(L.g2), false);
             else {
-            if (pair_mask() & 8)
-                narrow_pair(IT_D3B0, IT_D3B1, "conv_narrow_pair:dcn3.block", H8, W8, {nb(L.up), nb(L.prevhrw), fl8}, nb(L.g1));
-            else {
                 narrow(IT_D3B0, H8, W8, {nb(L.up), nb(L.prevhrw), fl8}, nb(L.g0));
                 narrow(IT_D3B1, H8, W8, {nb(L.g0)}, nb(L.g1));
-            }
-            if (pair_mask() & 2)
-                narrow_pair(IT_D3FUSE, IT_D3OM, "conv_narrow_pair:dcn3.fuse_offmask", H8, W8, {nb(L.g1), nb(L.poff)}, nb(L.om3), NB(), fl8);
-            else
                 narrow(IT_D3FUSE, H8, W8, {nb(L.g1), nb(L.poff)}, nb(L.g2));
             }
             const Item& d3 = M.items[IT_D3W];
             // dcn_3 with its offset / mask conv inside (gather.hip dcn3_kernel<true>): fp32 build 94.0 vs 73.7 + 37.3 us same-box, bit-identical;
             // the bf16 build keeps two kernels (its stand-alone conv runs on the bf16 MFMA: 84.8 vs 59.8 + 28.4 us, not worth the changed bits)
-            if (!kActBf16 && !(pair_mask() & 2) && dcn_fused_enabled()) {
+            if (!kActBf16 && dcn_fused_enabled()) {
                 const Item& om = M.items[IT_D3OM];
                 RUN(launch_dcn3_fused(F(L.state_hr), L.state_hr.bs, F(L.g2), L.g2.bs, flow8, packed + om.off_w, packed + om.off_b, packed + d3.off_w,
                                       packed + d3.off_b, F(L.al3), L.al3.bs, B, H8, W8, s, f8b));
             } else {
-                if (!(pair_mask() & 2)) narrow(IT_D3OM, H8, W8, {nb(L.g2)}, nb(L.om3), NB(), fl8);
+                narrow(IT_D3OM, H8, W8, {nb(L.g2)}, nb(L.om3), NB(), fl8);
                 RUN(launch_dcn3(F(L.state_hr), L.state_hr.bs, F(L.om3), L.om3.bs, packed + d3.off_w, packed + d3.off_b, F(L.al3), L.al3.bs, B, H8, W8, s));
             }
             if (fg) {           // model/CRFP_test.py:2389
@@ -1028,7 +981,7 @@ struct Runner {
         const NB st2 = mask_gate_enabled() && state_from_epilogue() ? nb(L.state_hr) : NB();
         if (r3_chain)   // main.0 -> conv1 -> conv2 (+ x) in one launch (round 6)
             narrow_chain(first ? IT_R3_0F : IT_R3_0, IT_R3_1, IT_R3_2, "conv_narrow_chain:res3.main0_conv1_conv2_add", H8, W8, r3_srcs, NB(), nb(L.feat), true, st2);
-        else if (pair_mask() & 4)
+        else if (res3_pair)
             narrow_pair(IT_R3_1, IT_R3_2, "conv_narrow_pair:res3.conv1_conv2_add", H8, W8, {nb(L.z0)}, nb(L.feat), nb(L.z0), NB(), st2);
         else {
             narrow(IT_R3_1, H8, W8, {nb(L.z0)}, nb(L.z1));

@@ -13,9 +13,9 @@ Schedules (``SCHEDULES``; the process-wide switches are read once per process, s
                   there this schedule is the product's, and the run only extends the census and the bit comparison to that pairing
 
 Where a row's ``live`` rule comes from is its ``line`` (crfp_amd/csrc/engine.hip).  A buffer is *compared* where it is live and holds a
-tensor; the fp32 build's `offfeat0..2` are live but hold the producer-split S3 image of the tensor (engine.hip:925), so they are compared in the
-bf16 build only; `res3.z1` has no writer in any schedule of either build (fp32: ``pair_mask() & 4`` is a constant, engine.hip:643,1031; bf16:
-``chain_mask()`` is the constant 3, engine.hip:626,634), and the bf16 build never writes `dcn3.g0`, `dcn3.g1`, `res3.z0` for the same reason (the
+tensor; the fp32 build's `offfeat0..2` are live but hold the producer-split S3 image of the tensor (engine.hip:885), so they are compared in the
+bf16 build only; `res3.z1` has no writer in any schedule of either build (fp32: ``res3_pair`` is a constant, engine.hip:628,984; bf16:
+``chain_mask()`` is the constant 3, engine.hip:612,620), and the bf16 build never writes `dcn3.g0`, `dcn3.g1`, `res3.z0` for the same reason (the
 fp32 build does).  ``UNREACHABLE`` lists these with their reasons; ``NOT_MODEL`` lists the fetchable buffers that carry no model tensor.
 
 Frames.  After a t-frame clip the frame-level buffers hold frame t - 1; the parity sets (`xin8`, `enc_hr0`, `x_hr`, `prop0`, `flow2`, `flow8`)
@@ -67,8 +67,8 @@ Flags = collections.namedtuple("Flags", "bf16 pair fused gate chain")
 
 
 def flags(build, sched):
-    """What Runner::frame's switches are under a schedule: pair_convs() at these map sizes (engine.hip:548-558: at most 512 tiles -> both pair
-    sites on), dcn_fused_enabled(), mask_gate_enabled(), chain_mask() (engine.hip:619-635: shipped 2 in the fp32 build, 3 in the bf16 build; only
+    """What Runner::frame's switches are under a schedule: pair_convs() at these map sizes (engine.hip:534-544: at most 512 tiles -> both pair
+    sites on), dcn_fused_enabled(), mask_gate_enabled(), chain_mask() (engine.hip:605-621: shipped 2 in the fp32 build, 3 in the bf16 build; only
     the fp32 objects of the lab library read CRFP_NARROW_CHAIN, its bf16 objects are the product's)."""
     assert build in BUILDS and sched in SCHEDULES, (build, sched)
     bf16 = build == "bf16"
@@ -89,79 +89,79 @@ def _row(key, tap, line, buf=None, sel=None, frames="last", moving=True, gated=0
     return Row(key, buf or key, sel, tap, frames, moving, gated, f32, live, tensor, line, other, state)
 
 
-_FNET = [("a0", 695), ("a1", 724), ("p1", 718), ("b0", 725), ("b1", 726), ("p2", 718), ("c0", 727), ("c1", 728), ("p3", 718), ("d0", 729),
-         ("d1", 730), ("u1", 722), ("e0", 731), ("e1", 732), ("u2", 722), ("f0", 733), ("f1", 734), ("u3", 722), ("g0", 735)]
+_FNET = [("a0", 680), ("a1", 682), ("p1", 683), ("b0", 684), ("b1", 685), ("p2", 686), ("c0", 687), ("c1", 688), ("p3", 689), ("d0", 690),
+         ("d1", 691), ("u1", 692), ("e0", 693), ("e1", 694), ("u2", 695), ("f0", 696), ("f1", 697), ("u3", 698), ("g0", 699)]
 _RGB6 = [0, 1, 2, 4, 5, 6]
 _P24 = slice(0, 24)
 
 ROWS = [
     # ---- clip level
-    _row("flow_lr", "flow_lr", "738", sel=slice(0, 2), frames="pairs", f32=True),
-    _row("enc_lr0", "enc_lr0", "760", frames="clip", moving=False),
-    _row("x_lr", "x_lr", "761", frames="clip", moving=False),
+    _row("flow_lr", "flow_lr", "702", sel=slice(0, 2), frames="pairs", f32=True),
+    _row("enc_lr0", "enc_lr0", "724", frames="clip", moving=False),
+    _row("x_lr", "x_lr", "725", frames="clip", moving=False),
 ] + [_row("fnet." + n, "fnet." + n, str(ln), frames="pairs") for n, ln in _FNET] + [
-    _row("fnet.g1", "fnet.g1", "737", sel=slice(0, 2), frames="pairs", f32=True),
+    _row("fnet.g1", "fnet.g1", "701", sel=slice(0, 2), frames="pairs", f32=True),
     # ---- the two parity sets (state-independent pre-work of a frame, Runner::frame_pre)
-    _row("xin8", "xin8", "852 (gate :851)", sel=_RGB6, frames="set", moving=False, gated=3),
-    _row("enc_hr0", "enc_hr0", "858", frames="set", moving=False, gated=2),
-    _row("x_hr", "x_hr", "859", frames="set", moving=False, gated=1),
-    _row("prop0", "prop0", "876", frames="set", moving=False),
-    _row("flow2", "flow2", "879", frames="set", f32=True),
-    _row("flow8", "flow8", "880", frames="set", f32=True),
+    _row("xin8", "xin8", "816 (gate :815)", sel=_RGB6, frames="set", moving=False, gated=3),
+    _row("enc_hr0", "enc_hr0", "819", frames="set", moving=False, gated=2),
+    _row("x_hr", "x_hr", "820", frames="set", moving=False, gated=1),
+    _row("prop0", "prop0", "836", frames="set", moving=False),
+    _row("flow2", "flow2", "839", frames="set", f32=True),
+    _row("flow8", "flow8", "840", frames="set", f32=True),
     # ---- the recurrent part of the last frame (Runner::frame)
-    _row("prev2", "prev2", "886"),
-    _row("prev2w", "prev2w", "917"),
-    _row("carryw", "carryw", "917"),
-    _row("prevhrw", "prevhrw", "918"),
-    _row("dcn.fa", "dcn_2.block0", "933 (paired: stays in LDS, :929-931)", live=lambda f: not f.pair, other="dcn_1.block0"),
-    _row("dcn.fb", "dcn_2.block2", "931 / 938", other="dcn_1.block2"),
-    _row("offfeat0", "dcn_0.block2", "930-931 / 936 (fp32 build: the S3 image, :925)", tensor=lambda f: f.bf16),
-    _row("offfeat1", "dcn_1.fuse", "941-942 (fp32 build: the S3 image, :925)", tensor=lambda f: f.bf16),
-    _row("offfeat2", "dcn_2.fuse", "941-942 (fp32 build: the S3 image, :925)", tensor=lambda f: f.bf16),
-    _row("offmask:offsets", "dcn_2.offset", "957 (fused: stays in registers, :946-955)", buf="offmask", sel=slice(0, 144), f32=True,
+    _row("prev2", "prev2", "846"),
+    _row("prev2w", "prev2w", "877"),
+    _row("carryw", "carryw", "877"),
+    _row("prevhrw", "prevhrw", "878"),
+    _row("dcn.fa", "dcn_2.block0", "893 (paired: stays in LDS, :889-891)", live=lambda f: not f.pair, other="dcn_1.block0"),
+    _row("dcn.fb", "dcn_2.block2", "891 / 898", other="dcn_1.block2"),
+    _row("offfeat0", "dcn_0.block2", "890-891 / 896 (fp32 build: the S3 image, :885)", tensor=lambda f: f.bf16),
+    _row("offfeat1", "dcn_1.fuse", "901-902 (fp32 build: the S3 image, :885)", tensor=lambda f: f.bf16),
+    _row("offfeat2", "dcn_2.fuse", "901-902 (fp32 build: the S3 image, :885)", tensor=lambda f: f.bf16),
+    _row("offmask:offsets", "dcn_2.offset", "917 (fused: stays in registers, :906-915)", buf="offmask", sel=slice(0, 144), f32=True,
          live=lambda f: not f.fused, other="dcn_1.offset"),
-    _row("offmask:masks", "dcn_2.mask", "957 (fused: stays in registers, :946-955)", buf="offmask", sel=slice(144, 216), f32=True,
+    _row("offmask:masks", "dcn_2.mask", "917 (fused: stays in registers, :906-915)", buf="offmask", sel=slice(144, 216), f32=True,
          live=lambda f: not f.fused, other="dcn_1.mask"),
-    _row("aligned", "dcn_2.aligned", "954 / 959", other="dcn_1.aligned"),
-    _row("res.y0", "forward_resblocks_2.main0", "971", other="forward_resblocks_1.main0"),
-    _row("res.y1", "forward_resblocks_2.conv1", "805 (paired: stays in LDS, :802-803)", live=lambda f: not f.pair, other="forward_resblocks_1.conv1"),
-    _row("prop_a", ("res2", _P24), "799 (level 2: :972-974)", other=("res0", _P24)),
-    _row("prop_b", ("res1", _P24), "799 (level 1: :972-974)"),
-    _row("up", "up", "978"),
-    _row("poff", "dcn_3.pre_offset", "978", state=True),
-    _row("dcn3.g0", "dcn_3.block0", "988 (chained: :981-983)", live=lambda f: not f.chain & 1),
-    _row("dcn3.g1", "dcn_3.block2", "989 (chained: :981-983)", live=lambda f: not f.chain & 1),
-    _row("dcn3.g2", "dcn_3.fuse", "983 / 994"),
-    _row("om3:offset", ("dcn_3.offset", slice(0, 2)), "1004 (fp32 build, fused: inside dcn3_kernel, :999-1002)", buf="om3", sel=slice(0, 2), f32=True,
+    _row("aligned", "dcn_2.aligned", "914 / 919", other="dcn_1.aligned"),
+    _row("res.y0", "forward_resblocks_2.main0", "931", other="forward_resblocks_1.main0"),
+    _row("res.y1", "forward_resblocks_2.conv1", "769 (paired: stays in LDS, :766-767)", live=lambda f: not f.pair, other="forward_resblocks_1.conv1"),
+    _row("prop_a", ("res2", _P24), "763 (level 2: :932-934)", other=("res0", _P24)),
+    _row("prop_b", ("res1", _P24), "763 (level 1: :932-934)"),
+    _row("up", "up", "938"),
+    _row("poff", "dcn_3.pre_offset", "938", state=True),
+    _row("dcn3.g0", "dcn_3.block0", "945 (chained: :941-943)", live=lambda f: not f.chain & 1),
+    _row("dcn3.g1", "dcn_3.block2", "946 (chained: :941-943)", live=lambda f: not f.chain & 1),
+    _row("dcn3.g2", "dcn_3.fuse", "943 / 947"),
+    _row("om3:offset", ("dcn_3.offset", slice(0, 2)), "957 (fp32 build, fused: inside dcn3_kernel, :952-955)", buf="om3", sel=slice(0, 2), f32=True,
          live=lambda f: f.bf16 or not f.fused),
-    _row("om3:mask", ("dcn_3.mask", slice(0, 1)), "1004 (fp32 build, fused: inside dcn3_kernel, :999-1002)", buf="om3", sel=slice(2, 3), f32=True,
+    _row("om3:mask", ("dcn_3.mask", slice(0, 1)), "957 (fp32 build, fused: inside dcn3_kernel, :952-955)", buf="om3", sel=slice(2, 3), f32=True,
          live=lambda f: f.bf16 or not f.fused),
-    _row("aligned3", "dcn_3.aligned", "1002 / 1005"),
-    _row("res3.z0", "forward_resblocks_3.main0", "1014 (chained: :1029-1030)", live=lambda f: not f.chain & 2),
-    _row("res3.z1", "forward_resblocks_3.conv1", "1034 (chained: :1029-1030; fp32 build: paired, :643,1031-1032)", live=lambda f: not f.chain & 2 and f.bf16),
-    _row("feat", "feat", "1030 / 1032 / 1035"),
+    _row("aligned3", "dcn_3.aligned", "955 / 958"),
+    _row("res3.z0", "forward_resblocks_3.main0", "967 (chained: :982-983)", live=lambda f: not f.chain & 2),
+    _row("res3.z1", "forward_resblocks_3.conv1", "987 (chained: :982-983; fp32 build: paired, :628,984-985)", live=lambda f: not f.chain & 2 and f.bf16),
+    _row("feat", "feat", "983 / 985 / 988"),
     # ---- what only the next frame reads
-    _row("state_hr", "state_hr", "1038 (away from the fovea: :1028-1030 / 1037)", moving=False, state=True),
-    _row("carry", "carry", "799 (:972)", moving=False, state=True),
+    _row("state_hr", "state_hr", "991 (away from the fovea: :981-983 / 990)", moving=False, state=True),
+    _row("carry", "carry", "763 (:932)", moving=False, state=True),
 ]
 
 UNREACHABLE = {
-    ("f32", "offfeat0"): "the fp32 build keeps dcn_0's block.2 output as the producer-split S3 image (engine.hip:925); a Q4 tensor only under "
+    ("f32", "offfeat0"): "the fp32 build keeps dcn_0's block.2 output as the producer-split S3 image (engine.hip:885); a Q4 tensor only under "
                          "CRFP_PRECISION=f32, which is none of the schedules here.  Compared in the bf16 build.",
     ("f32", "offfeat1"): "as offfeat0 (dcn_1's conv_fuse output).  Compared in the bf16 build.",
     ("f32", "offfeat2"): "as offfeat0 (dcn_2's conv_fuse output).  Compared in the bf16 build.",
-    ("f32", "res3.z1"): "no schedule of the fp32 build writes it: res3's conv1 -> conv2 pair is a compile-time constant (pair_mask() & 4, "
-                        "engine.hip:643,1031-1032).  Not compared in either build.",
+    ("f32", "res3.z1"): "no schedule of the fp32 build writes it: res3's conv1 -> conv2 pair is a compile-time constant (res3_pair, "
+                        "engine.hip:628,984-985).  Not compared in either build.",
     ("bf16", "res3.z1"): "the bf16 build runs forward_resblocks_3 as one chained launch in every schedule: chain_mask() is the constant 3 in the "
-                         "product objects (engine.hip:626,634), and the lab library links those (csrc/Makefile, LAB_OBJS).  Not compared in either build.",
+                         "product objects (engine.hip:612,620), and the lab library links those (csrc/Makefile, LAB_OBJS).  Not compared in either build.",
     ("bf16", "res3.z0"): "as res3.z1 of the bf16 build (chain bit 1).  Compared in the fp32 build (lab_unfused).",
     ("bf16", "dcn3.g0"): "the bf16 build runs dcn_3's block.0 -> .2 -> conv_fuse as one chained launch in every schedule (chain bit 0, constant: "
-                         "engine.hip:626,634,981-983).  Compared in the fp32 build (every schedule).",
+                         "engine.hip:612,620,941-943).  Compared in the fp32 build (every schedule).",
     ("bf16", "dcn3.g1"): "as dcn3.g0 of the bf16 build.  Compared in the fp32 build (every schedule).",
 }
 # fetchable buffers of Layout (W_DSV, t > 1) that carry no model tensor
 NOT_MODEL = {"status": "status words", "lr_q4": "the LR input frames repacked as quads (fp32 build)", "gate": "mask-gate flag bytes",
-             "gate.1": "mask-gate flag bytes", "fnet.part": "K-slice partial sums (lab library with CRFP_CONV_KSPLIT only)"}
+             "gate.1": "mask-gate flag bytes"}
 
 
 def tap_of(taps, spec):

@@ -88,8 +88,8 @@ def test_every_layout_buffer_is_a_row_or_listed(t, h, w):
     names = sc.fetch_names(t)
     for n in names:
         assert _fetch_shape(n, t, h, w) is not None, n
-    # Layout's frame-level and clip-level names (engine.hip:320-397, W_DSV, t > 1): nothing fetchable is missing from the table
-    layout = ["status", "state_hr", "carry", "flow_lr", "lr_q4", "enc_lr0", "x_lr"] + ["fnet." + n for n, _ in sc._FNET] + ["fnet.g1", "fnet.part"]
+    # Layout's frame-level and clip-level names (engine.hip:317-383, W_DSV, t > 1): nothing fetchable is missing from the table
+    layout = ["status", "state_hr", "carry", "flow_lr", "lr_q4", "enc_lr0", "x_lr"] + ["fnet." + n for n, _ in sc._FNET] + ["fnet.g1"]
     for p in ("", ".1"):
         layout += [b + p for b in ("xin8", "enc_hr0", "x_hr", "prop0", "flow2", "flow8", "gate")]
     layout += ["prop_a", "prop_b", "prev2", "prev2w", "prevhrw", "carryw", "dcn.fa", "dcn.fb", "offfeat0", "offfeat1", "offfeat2", "offmask", "aligned",
@@ -98,7 +98,7 @@ def test_every_layout_buffer_is_a_row_or_listed(t, h, w):
         assert _fetch_shape(n, t, h, w) is not None, n
         assert (n in names) != (n in sc.NOT_MODEL), n
     assert set(names) <= set(layout)
-    for n in ("cra.s1", "fg2", "lr_keep", "no_such_buffer"):        # other wirings' and the one-frame-per-call layout's buffers are not in this Layout
+    for n in ("cra.s1", "fg2", "lr_keep", "fnet.part", "no_such_buffer"):        # other wirings' and the one-frame-per-call layout's buffers are not in this Layout
         assert _fetch_shape(n, t, h, w) is None, n
 
 

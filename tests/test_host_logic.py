@@ -242,6 +242,11 @@ def test_product_library_carries_no_lab_kernels():
         assert name not in blob, name
     assert b"conv3x3_split_kernel" in blob
     assert b"dcn_fused2_kernel" not in blob          # round 5: the role-specialised fused DCN (lost its A/B) is lab-only too
+    # round 6's K slices for FNet's small maps lost their A/B and were removed from both libraries: no sliced conv, no reduce pass, no sliced
+    # instantiation (<true> / <1, true>) of the pool, resize and bf16 conv kernels, no KsIn kernel argument
+    for name in (b"conv3x3_split_ks_kernel", b"ksplit_reduce_kernel", b"upsample_q4_kernelILb1EE", b"avgpool2_q4_kernelILb1EE",
+                 b"conv3x3_bf16_kernelILi1ELb1EE", b"KsIn"):
+        assert name not in blob, name
     assert os.path.getsize(so) < 4 << 20
 
 
