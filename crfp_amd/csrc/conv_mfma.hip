@@ -32,19 +32,10 @@
 namespace CRFP_NS {
 
 constexpr int TW = 64, LW = TW + 2;
-// activation loads of the implicit-GEMM kernels.  -DCRFP_CONV_NT (A/B builds): non-temporal, so that a layer's INPUT does not displace its
-// OUTPUT from the XCD's 4 MB L2 -- with the XCD-banded tile order the next layer's workgroups run on the XCD that wrote their input.
-#ifdef CRFP_CONV_NT
-#define CRFP_LDACT(T, p) __builtin_nontemporal_load(reinterpret_cast<const T*>(p))
-#else
+// activation loads of the implicit-GEMM kernels: plain (the non-temporal form, meant to keep a layer's INPUT from displacing its OUTPUT
+// in the XCD's 4 MB L2, made every conv 4-10 % slower: profiles/README.md, round 4)
 #define CRFP_LDACT(T, p) (*reinterpret_cast<const T*>(p))
-#endif
-#ifndef CRFP_TAP_UNROLL
-#define CRFP_TAP_UNROLL 3
-#endif
-#ifndef CRFP_SPLIT_TAP_UNROLL
-#define CRFP_SPLIT_TAP_UNROLL 9   // default split kernel: full unroll measured +1.4 % frames/s over 3 (168 VGPRs, still 3 waves/SIMD)
-#endif
+constexpr int kTapUnroll = 3;   // tap-loop unroll factor of the fp32-MFMA and lab main loops
 
 // tanh / sigmoid on the hardware exp2 + rcp (v_exp_f32, v_rcp_f32: ~1 ulp each) instead of the libm
 // versions (~30 VALU instructions each): the 216-channel offset/mask epilogue is transcendental-bound
@@ -485,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(const ConvArgs a) 
 #pragma unroll
         for (int kp = 0; kp < KP; ++kp) {
         if (KP * st + kp >= npl) break;   // workgroup-uniform
-#pragma unroll CRFP_TAP_UNROLL
+#pragma unroll kTapUnroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - 3 * ky;
             float4 wa[CT];
@@ -526,6 +517,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_mfma_kernel(const ConvArgs a) 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef CRFP_ACT_BF16   // the split-operand schemes exist for fp32 activations only
+constexpr int kSplitTapUnroll = 9;   // tap loop of the default split kernel: full unroll measured +1.4 % frames/s over 3 (168 VGPRs, still 3 waves/SIMD)
 __device__ __forceinline__ void split_bf16x8(const f32x4& lo, const f32x4& hi, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
     const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
@@ -871,7 +863,7 @@ __device__ __forceinline__ void conv3x3_split_body(const ConvArgs& a, const int 
         SB_STAMP(tB)
         if (ch + 1 < nchunks) CRFP_SPLIT_ISSUE(ch + 1)
         SB_STAMP(tD)   // diagnostic: issue booked under D
-#pragma unroll CRFP_SPLIT_TAP_UNROLL
+#pragma unroll kSplitTapUnroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - 3 * ky;
             bf16x8 wa[CT][NP];
@@ -965,7 +957,7 @@ constexpr int S8_WPC = 9 * 3 * 64;
 #define S8_STAMP_END
 #endif
 
-// NW = 8: two workgroups per CU (the shipped form).  NW = 16 (A/B builds, -DCRFP_S8_NW=16): ONE 16-row workgroup per CU -- the 27.6 KB
+// NW = 8: two workgroups per CU (the only form launched).  NW = 16 was an A/B build: ONE 16-row workgroup per CU -- the 27.6 KB
 // weight stage is loaded once per CU instead of twice and the halo is 18 / 16 instead of 10 / 8 rows: 104 instead of 139 KB of ingest
 // per CU and chunk (profiles/r03_conv_split8_timeline.txt: the prologue is ingest-bound).
 template <int NW>
@@ -975,9 +967,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
     __shared__ bf16x8 tile[2][2][S8_NEL];        // [split part][quad pair][halo pixel]   42.2 KB (NW = 8)
     __shared__ bf16x8 wlds[S8_WPC];              // [(tap, image A/B/C)][lane]            27.6 KB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef CRFP_PRIO47   // A/B builds: static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-    if (wave >= 4) __builtin_amdgcn_s_setprio(CRFP_PRIO47);
-#endif
     const int j = lane & 31, h = lane >> 5;
     const int tiles_x = (a.W + TW - 1) / TW;
     const int ngrp = a.ctiles;
@@ -1543,12 +1532,10 @@ __device__ __forceinline__ void stage_bf16(u32x4_t (&tile)[2][NEL], const cu32x2
     }
 }
 
-#ifndef CRFP_BF16_LB
-#define CRFP_BF16_LB 5   // workgroups per CU the register allocation aims at.  Round 4, same box, 4-clip lock-step batch: 4 -> 5 takes the kernel
-                         // sum per clip 5.67 -> 5.60 ms (32 -> 32 convs 9.4 -> 8.9 us), one-clip calls unchanged; 6 spills (40 B) and loses 6 %
-#endif
+constexpr int kBf16Lb = 5;   // workgroups per CU the register allocation aims at.  Round 4, same box, 4-clip lock-step batch: 4 -> 5 takes the kernel
+                             // sum per clip 5.67 -> 5.60 ms (32 -> 32 convs 9.4 -> 8.9 us), one-clip calls unchanged; 6 spills (40 B) and loses 6 %
 template <int RPW>
-__global__ __launch_bounds__(256, RPW == 1 ? CRFP_BF16_LB : 3) void conv3x3_bf16_kernel(const ConvArgs a) {
+__global__ __launch_bounds__(256, RPW == 1 ? kBf16Lb : 3) void conv3x3_bf16_kernel(const ConvArgs a) {
     constexpr int CT = 1, TH = 4 * RPW, LH = TH + 2, PT = 2 * RPW;
     constexpr int NEL = LH * LW;                 // halo pixels
     constexpr int NIN = (NEL + 255) / 256;       // halo pixels per thread; each carries the chunk's 4 quads
@@ -2084,13 +2071,9 @@ namespace crfp {
 bool precision_env_strict(int family) {
     const char* p = getenv("CRFP_PRECISION");
     if (p && !strcmp(p, "f32")) return true;
-#ifdef CRFP_LAB   // the round-1 per-family knobs (CRFP_CONV_MODE / CRFP_DCN_MODE) live on in the lab library only
-    const char* l = getenv(family == 0 ? "CRFP_CONV_MODE" : "CRFP_DCN_MODE");
+    // the round-1 per-family knobs live on in the lab library only
+    const char* l = family == 0 ? CRFP_LAB_ENV("CRFP_CONV_MODE") : CRFP_LAB_ENV("CRFP_DCN_MODE");
     return l && !strcmp(l, "f32");
-#else
-    (void)family;
-    return false;
-#endif
 }
 }  // namespace crfp
 namespace CRFP_NS {
@@ -2179,11 +2162,10 @@ static bool conv_plan_splits(const ConvArgs& a) {
     return a.wsplit && !(env_strict || a.strict) && (a.kq & 3) == 0 && !nchw_src && a.kq <= CRFP_MAX_KQ;
 }
 
-// The kernel launch_conv_mfma runs for a plan that passed its checks (the lab library's experiments branch off before this is asked, and its
-// cout-tile knob may forbid the two-tile fp32-MFMA kernels: pair_ctiles)
-static ConvKernel select_kernel(const ConvArgs& a, bool pair_ctiles) {
+// The kernel launch_conv_mfma runs for a plan that passed its checks (the lab library's experiments branch off before this is asked)
+ConvKernel conv_select_kernel(const ConvArgs& a) {
     const bool split = conv_plan_splits(a);
-    const bool ct2 = !split && pair_ctiles && a.ctiles % 2 == 0;  // split: <2,1> needs 93 KB of LDS (1 workgroup per CU): slower than 2 x <1,1>
+    const bool ct2 = !split && a.ctiles % 2 == 0;  // split: <2,1> needs 93 KB of LDS (1 workgroup per CU): slower than 2 x <1,1>
     if (split) {
 #ifdef CRFP_ACT_BF16
         // (8-row tiles, conv3x3_bf16_kernel<2>: 1.25 instead of 1.5 ds_read_b128 per MFMA and half the weight staging, but 450
@@ -2205,9 +2187,7 @@ static ConvKernel select_kernel(const ConvArgs& a, bool pair_ctiles) {
         // 8-wave single-accumulator kernel for the convs with one cout tile (the 32-cout layers: one round of 450 workgroups
         // instead of 1.17 rounds of 900; same-box: conv1 26.4 -> 24.6 us, conv2 28.7 -> 26.1, block0 46.0 -> 43.2, main0 40.0 ->
         // 38.0, clip -1.5 %); with several cout tiles the 4-wave kernel stays (offset/mask head 114.0 vs 117.7 us)
-        constexpr int s8_max_wgs = 1 << 30;   // (the lab library's CRFP_F32_S8_MAX_WGS lowers it: launch_conv_lab)
-        if (a.ctiles == 1 && (long long)a.N * ((a.W + TW - 1) / TW) * ((a.H + S8_TH - 1) / S8_TH) <= s8_max_wgs) return CK_SPLIT8;
-        return CK_SPLIT4;
+        return a.ctiles == 1 ? CK_SPLIT8 : CK_SPLIT4;
 #endif
     }
     if (a.src[0].kind == SRC_NCHW_SHIFT) return ct2 ? CK_MFMA_SHIFT_CT2 : CK_MFMA_SHIFT;   // SPyNet's 7x7-as-3x3 convolutions: 18 ... 144 K-quads, two chunks per staging phase
@@ -2217,7 +2197,6 @@ static ConvKernel select_kernel(const ConvArgs& a, bool pair_ctiles) {
     const int tiles = ((a.W + TW - 1) / TW) * ((a.H + 7) / 8);
     return (long long)tiles * a.ctiles * a.N < 512 ? CK_MFMA_ROWS4 : CK_MFMA_ROWS8;
 }
-ConvKernel conv_select_kernel(const ConvArgs& a) { return select_kernel(a, true); }
 
 int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
     if (a.kq & 1 || a.kq < 2 || a.ctiles < 1 || a.nsrc < 1 || a.nsrc > CRFP_MAX_SRC) {
@@ -2240,7 +2219,6 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         }
     }
     static const bool env_strict = precision_env_strict(0);
-    bool ct2 = a.ctiles % 2 == 0;   // the lab library's cout-tile knobs may clear it
     bool s3_src = false;
     for (int i = 0; i < a.nsrc; ++i) s3_src |= a.src[i].kind == SRC_S3;
     const bool split = conv_plan_splits(a);
@@ -2260,14 +2238,14 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
 #ifdef CRFP_LAB
     {
         bool done = false;
-        const int rc = launch_conv_lab(am, name, split, ct2, s, &done);
+        const int rc = launch_conv_lab(am, name, split, s, &done);
         if (rc || done) return rc;
     }
 #endif
     const int tw = (a.W + TW - 1) / TW;
     const int tiles4 = tw * ((a.H + 3) / 4), tiles8 = tw * ((a.H + 7) / 8);   // 4-row / 8-row tiles of 64 columns
     const int nz = a.N * (a.ksplit > 0 ? a.ksplit : 1);
-    switch (select_kernel(a, ct2)) {
+    switch (conv_select_kernel(a)) {
 #ifdef CRFP_ACT_BF16
         case CK_BF16_X8: {
             static_assert(B8_TH == 8, "conv3x3_bf16x8_kernel walks 8-row tiles");
@@ -2277,13 +2255,8 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
         case CK_BF16_4W: conv3x3_bf16_kernel<1><<<dim3(tiles4 * a.ctiles, 1, a.N), 256, 0, s>>>(am); break;
 #else
         case CK_SPLIT8: {
-#ifdef CRFP_S8_NW
-            constexpr int s8nw = CRFP_S8_NW;
-#else
-            constexpr int s8nw = S8_TH;
-#endif
-            const int tiles_s8 = tw * ((a.H + s8nw - 1) / s8nw);
-            conv3x3_split8_kernel<s8nw><<<dim3(tiles_s8 * a.ctiles, 1, a.N), 64 * s8nw, 0, s>>>(am);
+            static_assert(S8_TH == 8, "conv3x3_split8_kernel<8> walks 8-row tiles");
+            conv3x3_split8_kernel<S8_TH><<<dim3(tiles8 * a.ctiles, 1, a.N), 64 * S8_TH, 0, s>>>(am);
             break;
         }
         case CK_SPLIT4: conv3x3_split_kernel<1, 1, 2><<<dim3(tiles4 * a.ctiles, 1, a.N), 256, 0, s>>>(am); break;
@@ -2304,9 +2277,6 @@ int launch_conv_mfma(const ConvArgs& a, const char* name, hipStream_t s) {
 // The decision: CK_SPLIT_DUAL, or CK_NONE for two launches.
 ConvKernel conv_select_dual(const ConvArgs& a0, const ConvArgs& a1) {
 #ifndef CRFP_ACT_BF16
-#ifndef CRFP_CONV_DUAL
-#define CRFP_CONV_DUAL 1   // A/B builds: 0 = always two launches
-#endif
     auto plain_split = [](const ConvArgs& a) {
         bool q4 = true;
         for (int i = 0; i < a.nsrc; ++i) q4 = q4 && (a.src[i].kind == SRC_Q4 || a.src[i].kind == SRC_S3 || a.src[i].kind == SRC_ZERO);
@@ -2317,7 +2287,7 @@ ConvKernel conv_select_dual(const ConvArgs& a0, const ConvArgs& a1) {
 #ifdef CRFP_LAB
     lab = true;   // the lab library keeps its kernel-selection knobs: two launches
 #endif
-    if (CRFP_CONV_DUAL && !lab && plain_split(a0) && plain_split(a1) && a0.N == a1.N && a0.H == a1.H && a0.W == a1.W && a0.ctiles == a1.ctiles &&
+    if (!lab && plain_split(a0) && plain_split(a1) && a0.N == a1.N && a0.H == a1.H && a0.W == a1.W && a0.ctiles == a1.ctiles &&
         conv_s3_supported()) {
         const int tiles = ((a0.W + TW - 1) / TW) * ((a0.H + 3) / 4), w0 = tiles * a0.ctiles;
         if ((w0 & 7) == 0) return CK_SPLIT_DUAL;

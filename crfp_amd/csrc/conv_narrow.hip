@@ -28,29 +28,13 @@ __device__ __forceinline__ float n_act(float v, int act) {
 // Workgroup = 256 threads walks a strided list of 64 x 16 output tiles (persistent).  Per tile the (16+2) x (64+2)
 // halo of every input quad goes global -> registers -> LDS (coalesced 16-B loads); thread (tx, ty) then produces the 4
 // vertically adjacent pixels (tx, 4*ty .. 4*ty+3): 18 halo + 9 weight ds_read_b128 per input quad feed 4 x 9 x 4 fp32
-// MFMAs (v_mfma_f32_4x4x1: the four couts of a pixel per instruction; CRFP_NARROW_MFMA=0 builds the v_fma_f32 form with
-// broadcast weight reads).  The loads of tile t+1 are issued right after tile t reached LDS, so they fly during
+// MFMAs (v_mfma_f32_4x4x1: the four couts of a pixel per instruction).  The loads of tile t+1 are issued right after tile t reached LDS, so they fly during
 // the FMAs and stores of tile t: the one-tile-per-workgroup version spent 7.7-12 k cycles per tile waiting for its
 // loads and 4 k in an epilogue that re-read its arguments (s_memtime stamps), i.e. HBM idled while it computed.
-#ifndef CRFP_NARROW_KY_UNROLL
-#define CRFP_NARROW_KY_UNROLL 3
-#endif
-#ifndef CRFP_NARROW_OCC1
-#ifdef CRFP_ACT_BF16
-#define CRFP_NARROW_OCC1 5   // bf16 build (bf16-MFMA form): 9.5 KB of LDS per input quad, 100 / 140 / 160 VGPRs
-#else
-#define CRFP_NARROW_OCC1 4   // workgroups per CU (launch bound and persistent grid) for KQ = 1
-#endif
-#endif
-#ifndef CRFP_NARROW_OCC2
-#define CRFP_NARROW_OCC2 3   // ... for KQ = 2 (KQ = 3: 2, LDS-bound)
-#endif
-#ifndef CRFP_NARROW_OCC3
-#define CRFP_NARROW_OCC3 2   // (bf16 build: 3 fits at 160 VGPRs but measured slower, dcn3.block0 43.0 -> 45.6 us)
-#endif
-#ifndef CRFP_NARROW_MFMA
-#define CRFP_NARROW_MFMA 1
-#endif
+// workgroups per CU (launch bound and persistent grid) for KQ = 1 / 2 / 3
+constexpr int kNarrowOcc1 = kActBf16 ? 5 : 4;   // bf16 build (bf16-MFMA form): 9.5 KB of LDS per input quad, 100 / 140 / 160 VGPRs
+constexpr int kNarrowOcc2 = 3;
+constexpr int kNarrowOcc3 = 2;   // LDS-bound (bf16 build: 3 fits at 160 VGPRs but measured slower, dcn3.block0 43.0 -> 45.6 us)
 constexpr int NTW = 64, NTH = 16, NLW = NTW + 2, NLH = NTH + 2;
 constexpr int NST = (NLH * NLW + 255) / 256;  // 5 halo elements per thread per quad
 
@@ -113,24 +97,19 @@ __device__ __forceinline__ void narrow_store_state(act_t* d2, long long ppix, cf
 // ST2 (NE_PLAIN, round 6): the launch has a second destination (NarrowArgs::dst2); a template parameter so that every other instantiation keeps
 // the epilogue it had (as a run-time branch it cost the bf16 build's stencils ~1 us each: profiles/r06_headline_ab.txt)
 template <int KQ, int EPI, bool GATE = false, bool ST2 = false>
-__global__ __launch_bounds__(256, KQ == 1 ? CRFP_NARROW_OCC1 : (KQ == 2 ? CRFP_NARROW_OCC2 : CRFP_NARROW_OCC3)) void conv3x3_narrow_kernel(const NarrowArgs a) {
+__global__ __launch_bounds__(256, KQ == 1 ? kNarrowOcc1 : (KQ == 2 ? kNarrowOcc2 : kNarrowOcc3)) void conv3x3_narrow_kernel(const NarrowArgs a) {
 #ifdef CRFP_ACT_BF16
     __shared__ cu32x2 tile[KQ][NLH][NLW];   // bf16 quads as they sit in HBM (8 bytes)
 #else
     __shared__ float4 tile[KQ][NLH][NLW];
-    __shared__ float4 wl[9 * KQ * 4];  // FMA form: [tap][kq][cin comp] -> float4 over cout (broadcast reads)
-                                       // MFMA form: [tap][kq][cout] -> float4 over cin comp (lane reads row cout = lane & 3)
+    __shared__ float4 wl[9 * KQ * 4];  // [tap][kq][cout] -> float4 over cin comp (lane reads row cout = lane & 3)
 #endif
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
 #ifndef CRFP_ACT_BF16
     if (tid < 9 * KQ * 4) {
         const float4 wv = reinterpret_cast<const float4*>(a.wpk)[tid];   // packed: (tap, kq, cin comp) -> 4 couts
-        if (CRFP_NARROW_MFMA) {
-            float* wf = reinterpret_cast<float*>(wl) + (tid >> 2) * 16 + (tid & 3);
-            wf[0] = wv.x; wf[4] = wv.y; wf[8] = wv.z; wf[12] = wv.w;
-        } else {
-            wl[tid] = wv;
-        }
+        float* wf = reinterpret_cast<float*>(wl) + (tid >> 2) * 16 + (tid & 3);
+        wf[0] = wv.x; wf[4] = wv.y; wf[8] = wv.z; wf[12] = wv.w;
     }
 #endif
     const int n = blockIdx.z;
@@ -299,44 +278,31 @@ __global__ __launch_bounds__(256, KQ == 1 ? CRFP_NARROW_OCC1 : (KQ == 2 ? CRFP_N
                                                                      acc[i], 0, 0, 0);
                 }
 #else
-        // The k loop is deliberately NOT unrolled (hipcc otherwise hoists every quad's reads).  ky is: with the MFMA form
-        // a quad needs 18 halo + 9 weight ds_read_b128 (27 instead of 45 when the rows shared by the ky are re-read) and
-        // stays at 108 / 128 / 149 VGPRs for KQ = 1 / 2 / 3 (+0.7 % clip); the FMA form spilled when ky was unrolled.
+        // The k loop is deliberately NOT unrolled (hipcc otherwise hoists every quad's reads).  ky is: a quad needs 18 halo + 9 weight
+        // ds_read_b128 (27 instead of 45 when the rows shared by the ky are re-read) and stays at 108 / 128 / 149 VGPRs for
+        // KQ = 1 / 2 / 3 (+0.7 % clip).
 #pragma unroll 1
         for (int k = 0; k < ((NPROBE & 1) ? 0 : KQ); ++k) {
-#pragma unroll (CRFP_NARROW_KY_UNROLL)
+#pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
-                    const float4* wq = &wl[((ky * 3 + kx) * KQ + k) * 4];
-                    if (CRFP_NARROW_MFMA) {
-                        // v_mfma_f32_4x4x1_16b_f32: 16 blocks of (4 couts x 1) x (1 x 4 pixels); lane l supplies A row l & 3
-                        // (its cout's weight) and B column l & 3 (its own pixel's value) of block l >> 2 and receives the 4
-                        // couts of its own pixel in the 4 result registers -- one 8-cycle MFMA where the FMA form issues four
-                        // 4-cycle v_fma_f32 (packed FP32 would do the same but is off, see Makefile).  fp32 in, fp32 out.
-                        const float4 wv = wq[tx & 3];
-                        f32x4 u[4];
+                    // v_mfma_f32_4x4x1_16b_f32: 16 blocks of (4 couts x 1) x (1 x 4 pixels); lane l supplies A row l & 3
+                    // (its cout's weight) and B column l & 3 (its own pixel's value) of block l >> 2 and receives the 4
+                    // couts of its own pixel in the 4 result registers -- one 8-cycle MFMA where a VALU form issues four
+                    // 4-cycle v_fma_f32 (packed FP32 would do the same but is off, see Makefile).  fp32 in, fp32 out.
+                    const float4 wv = wl[((ky * 3 + kx) * KQ + k) * 4 + (tx & 3)];
+                    f32x4 u[4];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) u[i] = reinterpret_cast<const f32x4&>(tile[k][4 * ty + ky + i][tx + kx]);
+                    for (int i = 0; i < 4; ++i) u[i] = reinterpret_cast<const f32x4&>(tile[k][4 * ty + ky + i][tx + kx]);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.x, u[i].x, acc[i], 0, 0, 0);
+                    for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.x, u[i].x, acc[i], 0, 0, 0);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.y, u[i].y, acc[i], 0, 0, 0);
+                    for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.y, u[i].y, acc[i], 0, 0, 0);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.z, u[i].z, acc[i], 0, 0, 0);
+                    for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.z, u[i].z, acc[i], 0, 0, 0);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.w, u[i].w, acc[i], 0, 0, 0);
-                        continue;
-                    }
-                    const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float4 u = tile[k][4 * ty + ky + i][tx + kx];
-                        acc[i][0] = fmaf(w3.x, u.w, fmaf(w2.x, u.z, fmaf(w1.x, u.y, fmaf(w0.x, u.x, acc[i][0]))));
-                        acc[i][1] = fmaf(w3.y, u.w, fmaf(w2.y, u.z, fmaf(w1.y, u.y, fmaf(w0.y, u.x, acc[i][1]))));
-                        acc[i][2] = fmaf(w3.z, u.w, fmaf(w2.z, u.z, fmaf(w1.z, u.y, fmaf(w0.z, u.x, acc[i][2]))));
-                        acc[i][3] = fmaf(w3.w, u.w, fmaf(w2.w, u.z, fmaf(w1.w, u.y, fmaf(w0.w, u.x, acc[i][3]))));
-                    }
+                    for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.w, u[i].w, acc[i], 0, 0, 0);
                 }
             }
         }
@@ -426,93 +392,7 @@ __global__ __launch_bounds__(256, KQ == 1 ? CRFP_NARROW_OCC1 : (KQ == 2 ? CRFP_N
 #undef CRFP_NARROW_LOAD
 }
 
-#if !defined(CRFP_ACT_BF16) && defined(CRFP_LAB)
-// ---------------------------------------------------------------- round-3 experiment: the same stencil WITHOUT the LDS tile
-// The persistent LDS-tile kernel above spends 9.3 of the 26.6 us of a 4 -> 4 conv with loads, MFMAs and stores all removed
-// (per-tile index arithmetic, LDS staging, two barriers per tile, ramp).  Here a thread owns R vertically adjacent
-// pixels and reads their (R + 2) x 3 neighbourhood straight from global memory (each element is read by ~9 lanes: L1 / L2
-// hits; 4.5-6 x 16 B per pixel and input quad through the texture path = 7-9 us per quad at the L1 rate), zero padding through
-// the buffer range check (an invalid corner gets an out-of-range offset: one v_cndmask on the offset instead of four on the
-// data).  No barrier after the weight table, no persistence, 6 (R = 2) or 4 (R = 4) waves per SIMD.  Same MFMA chains in the
-// same order: bit-identical to conv3x3_narrow_kernel.  NE_PLAIN, Q4 sources only.  Lab: CRFP_NARROW_DIRECT=2|4.
-template <int KQ, int R>
-__global__ __launch_bounds__(256) void conv3x3_narrow_direct_kernel(const NarrowArgs a) {
-    __shared__ float4 wl[9 * KQ * 4];
-    const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
-    if (tid < 9 * KQ * 4) {
-        const float4 wv = reinterpret_cast<const float4*>(a.wpk)[tid];
-        float* wf = reinterpret_cast<float*>(wl) + (tid >> 2) * 16 + (tid & 3);
-        wf[0] = wv.x; wf[4] = wv.y; wf[8] = wv.z; wf[12] = wv.w;
-    }
-    const int n = blockIdx.z, H = a.H, W = a.W;
-    const int x = blockIdx.x * 64 + tx, y0 = (blockIdx.y * 4 + ty) * R;
-    const float4 bias = *reinterpret_cast<const float4*>(a.bpk);
-    f32x4 acc[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) acc[i] = f32x4{bias.x, bias.y, bias.z, bias.w};
-    bool rowok[R + 2], colok[3];
-#pragma unroll
-    for (int r = 0; r < R + 2; ++r) rowok[r] = y0 + r - 1 >= 0 && y0 + r - 1 < H;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) colok[c] = x + c - 1 >= 0 && x + c - 1 < W;
-    __syncthreads();
-#pragma unroll 1
-    for (int k = 0; k < KQ; ++k) {
-        int kql = k, sidx = 0;
-        while (sidx < a.nsrc - 1 && kql >= a.src[sidx].nq) { kql -= a.src[sidx].nq; ++sidx; }
-        const ConvSrc src = a.src[sidx];
-        const int pitch = (W + src.pad) * 16, plane = (H + src.pad) * pitch;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (char*)const_cast<float*>(src.p + (long long)n * src.bstride) + (long long)kql * plane, 0, plane, 0x00020000);
-        const int o00 = (y0 - 1) * pitch + (x - 1) * 16;
-        f32x4 nb[R + 2][3];
-#pragma unroll
-        for (int r = 0; r < R + 2; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int off = rowok[r] && colok[c] ? o00 + r * pitch + c * 16 : 0x7ffffff0;
-                nb[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
-            }
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const float4 wv = wl[((ky * 3 + kx) * KQ + k) * 4 + (tx & 3)];
-#pragma unroll
-                for (int i = 0; i < R; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.x, nb[ky + i][kx].x, acc[i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < R; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.y, nb[ky + i][kx].y, acc[i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < R; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.z, nb[ky + i][kx].z, acc[i], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < R; ++i) acc[i] = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.w, nb[ky + i][kx].w, acc[i], 0, 0, 0);
-            }
-    }
-    if (x >= W) return;
-    const float slope = a.act == CRFP_ACT_RELU ? 0.0f : (a.act == CRFP_ACT_LRELU01 ? 0.1f : 1.0f);
-    const act_t* const resid = a.resid ? as_act(a.resid) + (long long)n * a.resid_bstride : nullptr;
-    act_t* const dsta = as_act(a.dst) + (long long)n * a.dst_bstride;
-    const int dpitch = W + a.dst_pad;
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int y = y0 + i;
-        if (y >= H) break;
-        float v[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) v[o] = o < a.cout ? fmaxf(acc[i][o], slope * acc[i][o]) * a.post_scale : 0.0f;
-        if (resid) {
-            const cf32x4 rv = ldq(resid + ((long long)y * W + x) * 4);
-            v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
-        }
-        stq(dsta + ((long long)y * dpitch + x) * 4, cf32x4{v[0], v[1], v[2], v[3]});
-    }
-}
-#endif
-
 #ifndef CRFP_ACT_BF16
-#ifndef CRFP_SEQ_FAST
-#define CRFP_SEQ_FAST 1   // A/B builds: 0 = the general loader / epilogue for every tile (quad-sequential and chain kernels)
-#endif
 // ---------------------------------------------------------------- quad-sequential form of the multi-quad stencils (round 6, fp32 build)
 // conv3x3_narrow_kernel stages ALL KQ input quads of a tile at once: 57 KB of LDS and 149 VGPRs for KQ = 3 = two workgroups per CU, whose
 // load / MFMA / store phases then add up instead of overlapping (destructive probes, profiles/r06_narrow_probes.txt: dcn3.block0 67.0 us,
@@ -521,7 +401,7 @@ __global__ __launch_bounds__(256) void conv3x3_narrow_direct_kernel(const Narrow
 // flight during this unit's MFMAs -- the resources of the KQ = 1 kernel, four workgroups per CU.  Same products in the same order (k outer,
 // then ky, kx, channel): bit-identical to conv3x3_narrow_kernel<KQ, NE_PLAIN>.
 template <int KQ>
-__global__ __launch_bounds__(256, CRFP_NARROW_OCC1) void conv3x3_narrow_seq_kernel(const NarrowArgs a) {
+__global__ __launch_bounds__(256, kNarrowOcc1) void conv3x3_narrow_seq_kernel(const NarrowArgs a) {
     __shared__ float4 tile[NLH][NLW];
     __shared__ float4 wl[9 * KQ * 4];   // [tap][kq][cout] -> float4 over cin comp (lane reads row cout = lane & 3)
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
@@ -553,14 +433,14 @@ __global__ __launch_bounds__(256, CRFP_NARROW_OCC1) void conv3x3_narrow_seq_kern
     float* const dsta = a.dst + (long long)n * a.dst_bstride;
     const int dpitch = W + a.dst_pad;
     const float* const resid = a.resid ? a.resid + (long long)n * a.resid_bstride : nullptr;
-    const bool plain_out = CRFP_SEQ_FAST && cout == 4 && post == 1.0f;   // (uniform) nothing to mask or scale in the epilogue
+    const bool plain_out = cout == 4 && post == 1.0f;   // (uniform) nothing to mask or scale in the epilogue
 
     f32x4 r[NST];
     bool okr[NST];
     bool r_in = false;   // (uniform) the halo held in r[] lies inside the image as a whole: it goes to LDS without the zero-padding selects
     // this thread's halo elements as byte offsets from the halo's first pixel in a Q4 plane of pitch W -- the same for every tile
     unsigned hoff[NST];
-    bool pitch_w = CRFP_SEQ_FAST != 0;   // (uniform) every source plane has pitch W (no padded source): the fast path's precondition
+    bool pitch_w = true;   // (uniform) every source plane has pitch W (no padded source): the fast path's precondition
 #pragma unroll
     for (int k = 0; k < KQ; ++k) pitch_w = pitch_w && qpitch[k] == W;
 #pragma unroll
@@ -964,7 +844,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_narrow_chain_kernel(const Narr
     bool r_in = false;   // (uniform) the region held in r[] lies inside the image as a whole (see conv3x3_narrow_seq_kernel's fast path)
     // this thread's elements of A's input halo as byte offsets from the halo's first pixel in a Q4 plane of pitch W
     unsigned hoff[KST];
-    bool pitch_w = CRFP_SEQ_FAST != 0;
+    bool pitch_w = true;
 #pragma unroll
     for (int k = 0; k < KQA; ++k) pitch_w = pitch_w && qpitch[k] == W;
 #pragma unroll
@@ -972,7 +852,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_narrow_chain_kernel(const Narr
         const int idx = min(tid + 256 * t, KIH * KIW - 1), rr = idx / KIW;
         hoff[t] = (unsigned)(rr * W + (idx - rr * KIW)) * 16u;
     }
-    const bool plain_out = CRFP_SEQ_FAST && c.cout == 4 && c.post_scale == 1.0f;
+    const bool plain_out = c.cout == 4 && c.post_scale == 1.0f;
     // global quad Q_ over the RW x RH region whose top-left pixel is (x0 - OFF, y0 - OFF) of tile T.  A's quads (OFF == 3) of a tile whose halo
     // lies inside the image: raw buffer loads at scalar tile offset + hoff[]; otherwise unconditional loads at clamped coordinates
 #define CRFP_CHAIN_LOAD(T, Q_, RW, RH, OFF)                                                               \
@@ -1030,7 +910,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_narrow_chain_kernel(const Narr
         const int tyi = t_cur / tiles_x, x0 = (t_cur - tyi * tiles_x) * KCW, y0 = tyi * KCH;
         const int t_next = t_cur + t_step;
         // (uniform) A's 20 x 64 region lies inside the image: no zero padding to apply to A's and B's outputs
-        const bool reg_in = CRFP_SEQ_FAST && x0 >= 2 && y0 >= 2 && x0 - 2 + KAW <= W && y0 - 2 + KAH <= H;
+        const bool reg_in = x0 >= 2 && y0 >= 2 && x0 - 2 + KAW <= W && y0 - 2 + KAH <= H;
         f32x4 acc[5];
         // ---- conv A: its global quads one after the other through buf0
 #pragma unroll
@@ -1500,43 +1380,24 @@ int launch_narrow_pack(const NarrowArgs& a, const float* w, const float* bias, c
 // which of launch_narrow's two kernel families a stencil takes, and its persistent grid: a few workgroups per CU walk the tiles
 NarrowGrid narrow_grid(const NarrowArgs& a) {
     const int ntl = ((a.W + NTW - 1) / NTW) * ((a.H + NTH - 1) / NTH);
-#ifdef CRFP_LAB
-    static const int per_cu_env = getenv("CRFP_NARROW_WGS_PER_CU") ? atoi(getenv("CRFP_NARROW_WGS_PER_CU")) : 0;   // tuning knob
-#else
-    constexpr int per_cu_env = 0;
-#endif
-    const int per_cu = per_cu_env > 0 ? per_cu_env : (a.kq == 1 ? CRFP_NARROW_OCC1 : (a.kq == 2 ? CRFP_NARROW_OCC2 : CRFP_NARROW_OCC3));
+    const int per_cu = a.kq == 1 ? kNarrowOcc1 : (a.kq == 2 ? kNarrowOcc2 : kNarrowOcc3);
 #ifndef CRFP_ACT_BF16
     // Round 6: the plain stencils (dcn_3.dcn_block.0 / .2, dcn_3.conv_fuse; forward_resblocks_3 when its chain is off) in the quad-sequential form.
     // (The bf16 build runs both 8x conv chains as one launch each -- conv3x3_narrow_chain_kernel -- and keeps conv3x3_narrow_kernel for the rest;
     // a bf16 twin of this form measured dcn3.block0 42.1 -> 37.0 us before the chains superseded it: profiles/r06_narrow_seq_ab.txt.)
-#ifndef CRFP_NARROW_SEQ
-#define CRFP_NARROW_SEQ 1
-#endif
-#ifndef CRFP_NARROW_SEQ_MINKQ
-#define CRFP_NARROW_SEQ_MINKQ 1   // the one-quad plain stencils too: the form carries the interior-tile fast path (A/B builds: 2)
-#endif
-#ifdef CRFP_LAB   // lab library: CRFP_NARROW_SEQ=0 at run time keeps conv3x3_narrow_kernel for the plain stencils
-    static const bool seq_on = getenv("CRFP_NARROW_SEQ") ? atoi(getenv("CRFP_NARROW_SEQ")) != 0 : CRFP_NARROW_SEQ != 0;
-#else
-    constexpr bool seq_on = CRFP_NARROW_SEQ != 0;
-#endif
-    if (seq_on && !a.gate && !a.dst2 && a.epi == NE_PLAIN && a.kq >= CRFP_NARROW_SEQ_MINKQ && a.act != CRFP_ACT_TANH && a.act != CRFP_ACT_SIGMOID)
-        return narrow_shares(NK_SEQ, ntl, CRFP_NARROW_OCC1);   // one quad's halo at a time: the resources of the one-quad kernel for every kq
+    // The one-quad plain stencils too: the form carries the interior-tile fast path.  Lab library: CRFP_NARROW_SEQ=0 keeps
+    // conv3x3_narrow_kernel for the plain stencils.
+    const bool seq_on = CRFP_LAB_KNOB("CRFP_NARROW_SEQ", 1) != 0;
+    if (seq_on && !a.gate && !a.dst2 && a.epi == NE_PLAIN && a.act != CRFP_ACT_TANH && a.act != CRFP_ACT_SIGMOID)
+        return narrow_shares(NK_SEQ, ntl, kNarrowOcc1);   // one quad's halo at a time: the resources of the one-quad kernel for every kq
 #endif
     return narrow_shares(NK_NARROW, ntl, per_cu);
 }
 
 int launch_narrow(const NarrowArgs& a_in, const char* name, hipStream_t s) {
     NarrowArgs a = a_in;
-    a.stamps = nullptr;
-#ifdef CRFP_LAB
-    static const char* stamp_name = getenv("CRFP_STAMP_NAME");
-    static long long* stamp_ptr = getenv("CRFP_STAMP_PTR") ? (long long*)strtoull(getenv("CRFP_STAMP_PTR"), nullptr, 0) : nullptr;
-    a.stamps = (stamp_ptr && stamp_name && !strcmp(stamp_name, name)) ? stamp_ptr : nullptr;
-    static const int nprobe = getenv("CRFP_NARROW_PROBE") ? atoi(getenv("CRFP_NARROW_PROBE")) : 0;
-    a.rsv = nprobe;
-#endif
+    a.stamps = lab_stamps(name);
+    a.rsv = CRFP_LAB_KNOB("CRFP_NARROW_PROBE", 0);   // lab timing experiments (conv3x3_narrow_kernel's NPROBE)
     if (a.kq < 1 || a.kq > 3 || a.cout < 1 || a.cout > 4) {
         set_error("conv_narrow %s: unsupported kq=%d cout=%d", name, a.kq, a.cout);
         return CRFP_E_UNSUPPORTED;
@@ -1553,24 +1414,6 @@ int launch_narrow(const NarrowArgs& a_in, const char* name, hipStream_t s) {
     // mask-gated launches touch a data-dependent share of the map: they are booked with no algorithmic bytes / flops (their time still counts)
     const double bytes = a.gate ? 0.0 : px * (in_ch + (a.epi == NE_OFFMASK3 ? 3 : a.cout) + extra) * (double)sizeof(act_t);
     ProfScope prof(name, s, bytes, a.gate ? 0.0 : 2.0 * px * in_ch * a.cout * 9.0);
-#if !defined(CRFP_ACT_BF16) && defined(CRFP_LAB)
-    static const int direct = getenv("CRFP_NARROW_DIRECT") ? atoi(getenv("CRFP_NARROW_DIRECT")) : 0;
-    bool q4only = true;
-    for (int i = 0; i < a.nsrc; ++i) q4only &= a.src[i].kind == SRC_Q4;
-    if (direct && a.epi == NE_PLAIN && q4only && a.act != CRFP_ACT_TANH && a.act != CRFP_ACT_SIGMOID) {
-        const int R = direct == 2 ? 2 : 4;
-        dim3 grid((a.W + 63) / 64, (a.H + 4 * R - 1) / (4 * R), a.N);
-#define CRFP_DIRECT_LAUNCH(KQ_) if (R == 2) conv3x3_narrow_direct_kernel<KQ_, 2><<<grid, 256, 0, s>>>(a); else conv3x3_narrow_direct_kernel<KQ_, 4><<<grid, 256, 0, s>>>(a);
-        switch (a.kq) {
-            case 1: CRFP_DIRECT_LAUNCH(1) break;
-            case 2: CRFP_DIRECT_LAUNCH(2) break;
-            default: CRFP_DIRECT_LAUNCH(3) break;
-        }
-#undef CRFP_DIRECT_LAUNCH
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
     const NarrowGrid g = narrow_grid(a);
     dim3 grid(g.workgroups, 1, a.N);
 #ifndef CRFP_ACT_BF16

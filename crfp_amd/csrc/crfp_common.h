@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
+#include <string.h>
 #include "../../include/crfp_hip.h"
 
 // ------------------------------------------------------------------ storage type of activations in HBM
@@ -33,6 +35,20 @@
 #define CRFP_API(name) name
 #endif
 
+// ------------------------------------------------------------------ lab knobs
+// The switches of the experiments that the lab library keeps (table in profiles/README.md), all read here.  CRFP_LAB_ENV("CRFP_X"): the
+// variable's text or null; CRFP_LAB_KNOB("CRFP_X", d): its integer value, d when it is not set.  Lab build: the environment, read once per
+// process when the site first runs.  Product build: null / d itself, a constant expression where d is one -- macros, so that the name
+// never reaches the product's string table.  d must not depend on the call (it is latched with the value).  The five product switches
+//  keep read-once functions of their own.
+#ifdef CRFP_LAB
+#define CRFP_LAB_ENV(name) ([]() -> const char* { static const char* const v_ = getenv(name); return v_; }())
+#define CRFP_LAB_KNOB(name, dflt) ([]() -> int { static const int v_ = getenv(name) ? atoi(getenv(name)) : (dflt); return v_; }())
+#else
+#define CRFP_LAB_ENV(name) (static_cast<const char*>(nullptr))
+#define CRFP_LAB_KNOB(name, dflt) (dflt)
+#endif
+
 namespace crfp {   // compiled once (runtime.hip): errors, per-kernel timing, environment
 void set_error(const char* fmt, ...);
 struct ProfScope {
@@ -44,6 +60,12 @@ struct ProfScope {
 bool prof_enabled();
 bool precision_env_strict(int family);   // CRFP_PRECISION=f32 in the environment (lab library: or the round-1 knob of family 0 = conv, 1 = DCN)
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// diagnostic builds (tools/stamp_*.py): the s_memtime stamp buffer CRFP_STAMP_PTR when CRFP_STAMP_NAME names this launch site, else null
+static inline long long* lab_stamps(const char* site) {   // (static: the lab library links lab and product objects)
+    const char* const name = CRFP_LAB_ENV("CRFP_STAMP_NAME");
+    const char* const ptr = CRFP_LAB_ENV("CRFP_STAMP_PTR");
+    return name && ptr && !strcmp(name, site) ? (long long*)strtoull(ptr, nullptr, 0) : nullptr;
+}
 // float-tensor helpers of the fp32 build that the bf16 engine borrows for its float tensors (flow fields, masks)
 int launch_upsample_q4(const float* x, long long xb, float* out, long long ob, int N, int nq, int H, int W, int OH,
                        int OW, float sh, float sw, float mul, hipStream_t s, int out_bgroup);
@@ -59,6 +81,7 @@ using crfp::ProfScope;
 using crfp::prof_enabled;
 using crfp::precision_env_strict;
 using crfp::align_up;
+using crfp::lab_stamps;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float cf32x4 __attribute__((ext_vector_type(4)));
@@ -337,9 +360,6 @@ __device__ __forceinline__ unsigned* ovf_word(unsigned* base, int div, int add, 
 // from HBM.  This maps linear workgroup id b of `total` to a tile id such that XCD x walks the contiguous band
 // [x*q + min(x,r), ...) of the tile list (q = total/8, r = total%8): a bijection on [0, total).
 __device__ __forceinline__ int xcd_band_tile(int b, int total) {
-#ifdef CRFP_NO_XCD_BAND
-    return b;   // A/B builds only
-#endif
     const int q = total >> 3, r = total & 7, x = b & 7, i = b >> 3;
     return x * q + min(x, r) + i;
 }

@@ -33,31 +33,12 @@
 
 constexpr int DF_LW = 34;   // halo tile width: 32 pixels + one column either side
 
-// ---- build-time A/B switches (EXTRA of csrc/Makefile, tools/mk_variant.sh); the product builds with the defaults
-#ifndef CRFP_DF_BAND_NP
-#define CRFP_DF_BAND_NP 1   // 0 = the natural tile order of the one-tile form (round 5)
-#endif
-#ifndef CRFP_DF_PS_PROBE   // timing only (results wrong): 1 = the persistent form never requests the next tile's halo tile / weights,
-#define CRFP_DF_PS_PROBE 0 // 2 = ... never writes them to LDS
-#endif
-constexpr int DF_PS_PROBE = CRFP_DF_PS_PROBE;
-// Round 5 (CRFP_DF_LATE_PROLOGUE, default on for the 8-wave form): only what the first MFMA needs -- the halo tile and weight stage 0 -- is
+// Round 5, late prologue (the 8-wave form): only what the first MFMA needs -- the halo tile and weight stage 0 -- is
 // fetched in front of the first barrier.  The DCN weight image (36 KB, first used by the sampler's MFMAs behind stage 1's barrier) and weight
 // stage 1 used to be ingested there too: 153 KB per workgroup before any MFMA, four rounds per launch.  They are now requested BEHIND the
 // first barrier and land during cout tile 0, which has no sampler work to hide anyway (fp32: DF_BEGIN(0, 1); bf16: DF_LATE_FILL).  Same
 // values in the same places before their first use: bit-identical.
 // (PS: the DCN weight image is fetched once per workgroup, in front of the tile loop.)
-#ifndef CRFP_DF_LATE_PROLOGUE
-#define CRFP_DF_LATE_PROLOGUE 1
-#endif
-#ifndef CRFP_DF_PERSIST
-#define CRFP_DF_PERSIST 1   // 0 = no launch takes the persistent form
-#endif
-#if defined(CRFP_LAB) && !defined(CRFP_DF_NO_PREFETCH)
-#define CRFP_DF_NO_PREFETCH   // the lab build carries a run-time probe word in this kernel: with the 16 prefetch registers on top it spills (96 B, 255 us)
-#endif
-// (CRFP_DF_PS_NOBAND, CRFP_PRIO47, CRFP_DF_PROBE_CT: undefined by default, explained where they are read; CRFP_DF_SGB, CRFP_DF_SCHED_R2 and
-// CRFP_DF_SCHED_INC belong to the fp32 build's tap pipeline and schedule table below)
 
 __device__ __forceinline__ void df_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -133,25 +114,19 @@ typedef f32x4 df_tile_t;                             // tile element as loaded: 
 // per tap on a kernel with two waves per SIMD (378 conv MFMAs per wave).  The whole-tile weight stage of the 8-wave form holds both chunks,
 // so the prefetch runs across the chunk boundary; the first tap of a cout tile (behind the stage barrier) loads its own operands.  Same
 // operations on the same values in the same order: bit-identical.
-// Round 5: the scheduling region (sampler item + tap) is laid out as 4 DS reads, then 3 x (1 MFMA, CRFP_DF_SGB vector instructions) with
+// Round 5: the scheduling region (sampler item + tap) is laid out as 4 DS reads, then 3 x (1 MFMA, DF_SGB vector instructions) with
 // sched_group_barrier, so that the sampler's vector work sits INSIDE each MFMA's shadow instead of in front of a burst of three MFMAs
 // (gaps of one instruction between MFMAs: 196 -> 60; same-box 131.2 -> 128.4 us, bit-identical; 10 per MFMA: the same; GAP 3 / 7 / 9 / 12
-// of the generated schedule: 130.0 / 128.8 / 131.8 / 139.4, profiles/r05_dcn_fused_sgb_ab.txt).  -DCRFP_DF_SGB=0: the fenced form.
-#ifndef CRFP_DF_SGB
-#define CRFP_DF_SGB 6
-#endif
-#if CRFP_DF_SGB > 0
-#define DF_TAP_FENCE
+// of the generated schedule: 130.0 / 128.8 / 131.8 / 139.4, profiles/r05_dcn_fused_sgb_ab.txt).
+// The lab build has no operand prefetch: it carries a run-time probe word in this kernel, and with the 16 prefetch registers on top it
+// spills (96 B, 255 us).
+#ifndef CRFP_LAB
+#define DF_SGB 6   // vector instructions per MFMA shadow
 #define DF_TAP_PIPELINE                                                                                   \
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                                                \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, CRFP_DF_SGB, 0); \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, CRFP_DF_SGB, 0); \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, CRFP_DF_SGB, 0);
-#else
-#define DF_TAP_FENCE __builtin_amdgcn_sched_barrier(0);   /* the next tap's reads leave before this tap's MFMAs */
-#define DF_TAP_PIPELINE
-#endif
-#ifndef CRFP_DF_NO_PREFETCH
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, DF_SGB, 0); \
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, DF_SGB, 0); \
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, DF_SGB, 0);
 #define DF_LDOPS(W0, W1, B0, B1, WB, CH_, TAP_)                                                           \
     {                                                                                                     \
         const int ky_ = (TAP_) / 3, kx_ = (TAP_) - 3 * ky_;                                               \
@@ -175,7 +150,6 @@ typedef f32x4 df_tile_t;                             // tile element as loaded: 
         }                                                                                                 \
         else if (tap < 8) DF_LDOPS(pw0, pw1, pb0, pb1, wcur, CH, tap + 1)                                 \
         else if (CPS == 2 && (CH) == 0) DF_LDOPS(pw0, pw1, pb0, pb1, wcur + DF_WCH, 1, 0)                 \
-        DF_TAP_FENCE                                                                                      \
         cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b1, cl, 0, 0, 0);                                 \
         ca = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b0, ca, 0, 0, 0);                                 \
         cl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, b0, cl, 0, 0, 0);                                 \
@@ -292,7 +266,6 @@ typedef cu32x2 df_tile_t;                            // tile element as loaded: 
 // MFMAs MA .. MB-1 of the cout tile's 18 (chunk-major, then taps: the K order of conv3x3_bf16_kernel)
 // Round 5: MFMA m + 1's two operands are read from LDS before MFMA m issues (one register set ahead, +8 VGPRs; the fp32 build's DF_TAPS
 // has the measurement).  The first MFMA of a cout tile (behind the stage barrier) loads its own.  Same operations, same order: bit-identical.
-#ifndef CRFP_DF_NO_PREFETCH
 #define DF_LDOPS(W0, B0, M_)                                                                              \
     {                                                                                                     \
         const int ch_ = (M_) / 9, tap_ = (M_) - 9 * ch_, ky_ = tap_ / 3, kx_ = tap_ - 3 * ky_;            \
@@ -309,16 +282,6 @@ typedef cu32x2 df_tile_t;                            // tile element as loaded: 
         __builtin_amdgcn_sched_barrier(0);                                                                \
         ca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b0, ca, 0, 0, 0);                                \
     }
-#else
-#define DF_M(MA, MB)                                                                                      \
-    _Pragma("unroll") for (int m = (MA); m < (MB); ++m) {                                                 \
-        const int ch = m / 9, tap = m - 9 * ch, ky = tap / 3, kx = tap - 3 * ky;                          \
-        const df_bf16x8 w0 = __builtin_bit_cast(df_bf16x8, wcur[m * 64 + lane]);                           \
-        const int pix = (wave + ky) * DF_LW + j + kx;                                                     \
-        const df_bf16x8 b0 = __builtin_bit_cast(df_bf16x8, *reinterpret_cast<const f32x4*>(&tile[2 * ch + h][pix][0])); \
-        ca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, b0, ca, 0, 0, 0);                                \
-    }
-#endif
 #define DF_CL_ZERO   // one accumulator
 #define DF_RAW(T)                                                                                         \
     {                                                                                                     \
@@ -400,14 +363,14 @@ constexpr double kFusedBytesPerPixel = 8.0 + (32 + 32 + 32) * sizeof(act_t);
     if (PS) {                                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                \
         DF_DECODE(has_next ? t_cur + t_step : t_cur, ntx0, nty0, nn)                                      \
-        if (!(DF_PS_PROBE & 1)) { DF_TLOAD(ntx0, nty0, nn) DF_WLOAD(0) }                                  \
+        DF_TLOAD(ntx0, nty0, nn) DF_WLOAD(0)                                                              \
         __builtin_amdgcn_sched_barrier(0);                                                                \
     }
 #define DF_TAIL_COMMIT                                                                                    \
     if (PS && has_next) {                                                                                 \
         __builtin_amdgcn_sched_barrier(0);                                                                \
         df_lds_barrier();                                                                                 \
-        if (!(DF_PS_PROBE & 2)) { DF_TWRITE(ntx0, nty0) DF_WRITE(0) }                                     \
+        DF_TWRITE(ntx0, nty0) DF_WRITE(0)                                                                 \
         __builtin_amdgcn_sched_barrier(0);                                                                \
     }
 
@@ -433,33 +396,24 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(con
     __shared__ f32x4 wl[36 * 64];
     __shared__ f32x4 bl[DB ? 56 : 1];   // the head's 224 packed biases (NW = 8: LDS has room; NW = 4 keeps them in 4 VGPRs)
     const int tid0 = threadIdx.x;
-#ifdef CRFP_PRIO47   // A/B builds: static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-    if ((tid0 >> 6) >= 4) __builtin_amdgcn_s_setprio(CRFP_PRIO47);
-#endif
     const int H = a.H, W = a.W;
     // the tile list (PS): tile id = (n * tiles_y + ty) * tiles_x + tx; this workgroup takes t_cur, t_cur + t_step, ... below t_end
     const int tiles_x = (W + 31) >> 5, tiles_y = (H + NW - 1) / NW;
     int t_cur = 0, t_end = 0, t_step = 1;
     if (PS) {
         const int total = tiles_x * tiles_y * a.N, G = (int)gridDim.x;
-#ifdef CRFP_DF_PS_NOBAND   // A/B builds: natural order (tile = workgroup id + k * workgroups)
-        t_cur = (int)blockIdx.x; t_end = total; t_step = G;
-#else
         const int q = total >> 3, r = total & 7, x = (int)blockIdx.x & 7;
         const int band0 = x * q + min(x, r);
         t_cur = band0 + ((int)blockIdx.x >> 3); t_end = band0 + q + (x < r ? 1 : 0); t_step = G >> 3;
-#endif
         if (t_cur >= t_end) return;
     }
     int tx0, ty0, n;
     if (PS) DF_DECODE(t_cur, tx0, ty0, n)
-#if CRFP_DF_BAND_NP   // the one-tile form walks the tile list in the XCD-banded order too (xcd_band_tile over the launch's linear workgroup id)
-    else if (DB) {
+    else if (DB) {   // the one-tile form walks the tile list in the XCD-banded order too (xcd_band_tile over the launch's linear workgroup id)
         const int lin_ = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
         const int tb_ = xcd_band_tile(lin_, (int)(gridDim.x * gridDim.y * gridDim.z));
         DF_DECODE(tb_, tx0, ty0, n)
     }
-#endif
     else { tx0 = blockIdx.x * 32; ty0 = blockIdx.y * NW; n = blockIdx.z; }
 
     int ltid = tid0;  // the thread id as the tile loop sees it: re-defined (opaquely) per tile in the persistent form, so that everything derived
@@ -470,7 +424,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(con
     const f32x4* __restrict__ wc = reinterpret_cast<const f32x4*>(a.wconv);
     f32x4 rws[DF_NWS];
     DF_WLOAD(0)
-    constexpr bool LATE = DB && CRFP_DF_LATE_PROLOGUE;
+    constexpr bool LATE = DB;   // the late prologue
     static_assert(!PS || LATE, "the persistent form builds on the late prologue");
     constexpr bool LATE_WL = LATE && !PS;   // the DCN weight image rides in rwl through cout tile 0
     constexpr int DF_NWL = (36 * 64 + NT - 1) / NT;
@@ -516,11 +470,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(con
     const int DF_PROBE = a.probe;   // timing experiments (results wrong), bits: 1 = no sampling, 2 = no conv MFMAs, 4 = no barriers / weight streaming after stage 0, 8 = barriers but no weight streaming, 32 = conv MFMAs without operand reads, 64 = weight reads only
     const float pz = (DF_PROBE & 16) ? 0.0f : 1.0f;   // 16: zero offsets = regular, coalesced sampling positions
 #else
-#ifdef CRFP_DF_PROBE_CT   // A/B builds of the PRODUCT kernel with a compile-time probe (the lab build's run-time probe word costs registers)
-    constexpr int DF_PROBE = CRFP_DF_PROBE_CT;
-#else
     constexpr int DF_PROBE = 0;
-#endif
     constexpr float pz = 1.0f;
 #endif
     float ov[108];   // activated (dy, dx, mask) of position p at 3 p + c; every index below is a compile-time constant
@@ -549,20 +499,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(con
     DF_BEGIN(6) DF_M(0, 3) DF_TRANS(5) DF_SB DF_M(3, 6) DF_SB DF_C(10, Q1) DF_SB DF_M(6, 9) DF_I(13, Q1) DF_SB DF_M(9, 12) DF_SB DF_C(11, Q2) DF_SB
                 DF_M(12, 15) DF_I(14, Q2) DF_SB DF_M(15, 18) DF_SB DF_C(12, Q0) DF_SB DF_I(15, Q0) DF_SB DF_RAW(6)
     DF_TRANS(6) DF_SB DF_C(13, Q1) DF_SB DF_I(16, Q1) DF_SB DF_C(14, Q2) DF_SB DF_I(17, Q2) DF_SB DF_TAIL_REQUEST DF_C(15, Q0) DF_SB DF_C(16, Q1) DF_SB DF_C(17, Q2) DF_TAIL_COMMIT
-#elif defined(CRFP_DF_SCHED_R2)   // A/B builds: the superseded round-2 table (whole pairs between groups of 2-4 taps)
-#define DCN_FUSED_LAB_SCHED_R2
-#include "dcn_fused_lab.inc"
-#undef DCN_FUSED_LAB_SCHED_R2
 #else
     // Round 3: ONE micro-item in front of EVERY tap instead of whole pairs between groups of 2-4 taps (tools/gen/dcn_fused_schedule.py
     // holds the dependency rules and writes the table): <= ~30 vector instructions per 3 MFMAs, the regime in which
     // tools/micro/mfma_valu_overlap2 shows the vector work disappearing in the MFMA gaps.  Same operations on the same values in
-    // the same per-accumulator order: bit-identical to the round-2 table (-DCRFP_DF_SCHED_R2) and to the two-kernel path.
-#ifdef CRFP_DF_SCHED_INC   // A/B builds: another run of the generator
-#include CRFP_DF_SCHED_INC
-#else
+    // the same per-accumulator order: bit-identical to the round-2 table it replaced and to the two-kernel path.
 #include "dcn_fused_schedule.inc"
-#endif
 #endif
     if (valid) {
         DCN_G8_EPILOGUE(a.out, a.ob, a.bdcn, a.ovf, a.ovf_div)
@@ -583,14 +525,10 @@ bool dcn_fused_enabled() {
 }
 
 constexpr int kFusedPersistWgs = 256;   // workgroups of the persistent form = CUs of an MI355X (one 8-wave workgroup per CU: 155 KB of LDS, 250 VGPRs)
-// launches with at least this many tiles take the persistent form (six rounds of one workgroup per CU); -DCRFP_LAB: CRFP_DF_PS_MIN_TILES overrides (tests)
+// launches with at least this many tiles take the persistent form (six rounds of one workgroup per CU); the lab knob overrides (tests)
 static int fused_persist_min_tiles() {
-#ifdef CRFP_LAB
-    static const int v = getenv("CRFP_DF_PS_MIN_TILES") ? atoi(getenv("CRFP_DF_PS_MIN_TILES")) : 6 * kFusedPersistWgs;
+    const int v = CRFP_LAB_KNOB("CRFP_DF_PS_MIN_TILES", 6 * kFusedPersistWgs);
     return v > kFusedPersistWgs ? v : kFusedPersistWgs + 1;
-#else
-    return 6 * kFusedPersistWgs;
-#endif
 }
 
 int launch_dcn_fused(const DcnFuseArgs& args, hipStream_t s) {
@@ -607,7 +545,7 @@ int launch_dcn_fused(const DcnFuseArgs& args, hipStream_t s) {
     // Round 6: both forms walk the tile list in the XCD-banded order (HBM traffic 170 -> 112-116 MB per launch @A).  Launches of six rounds of
     // the chip and more (a lock-step batch, the 4K map) take the persistent form (-1 % there, +1.5 % at 3.5 rounds: profiles/r06_dcn_fused_persistent_ab.txt)
     const int tiles = ((a.W + 31) / 32) * ((a.H + 7) / 8) * a.N;
-    if (CRFP_DF_PERSIST && tiles >= fused_persist_min_tiles()) dcn_fused_kernel<8, true><<<dim3(kFusedPersistWgs, 1, 1), 512, 0, s>>>(a);
+    if (tiles >= fused_persist_min_tiles()) dcn_fused_kernel<8, true><<<dim3(kFusedPersistWgs, 1, 1), 512, 0, s>>>(a);
     else dcn_fused_kernel<8><<<dim3((a.W + 31) / 32, (a.H + 7) / 8, a.N), 512, 0, s>>>(a);
     CRFP_CHECK_LAUNCH();
     return 0;

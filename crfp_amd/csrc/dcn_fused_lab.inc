@@ -1,33 +1,5 @@
-// Lab-only text of dcn_fused.hip (fp32 build), in two parts.  dcn_fused.hip includes this file
-//  * inside dcn_fused_kernel with DCN_FUSED_LAB_SCHED_R2 defined (-DCRFP_DF_SCHED_R2 A/B builds): the superseded round-2 schedule table;
-//  * at namespace scope under CRFP_LAB: dcn_fused2_kernel (lost its A/B in round 5) and the lab library's choice among the kernel forms.
-#ifdef DCN_FUSED_LAB_SCHED_R2
-    // Cout tile T completes the sampling pairs up to (16 T + 10) / 6: 1, 4, 7, 9, 12, 15, 17.  The pairs of tile T are sampled
-    // INSIDE the two stages of tile T + 1, between its taps: the MFMA runs 32 clocks in its own pipe while the wave issues the
-    // sampler's VALU work (coordinates, weights, bilinear FMAs, fp16 split: as many issue clocks per pixel as the MFMAs take),
-    // and a pair's gathers fly under the MFMAs issued before its consumption.  Pair u lives in Q[u & 1]; I(u) follows C(u - 2).
-    DF_BEGIN(0, 0) DF_BIAS(0) DF_TAPS(0, 0, 9)   // (the bias table in LDS is complete behind the first barrier)
-    DF_BEGIN(0, 1) DF_TAPS(1, 0, 9) DF_RAW(0)
-    DF_BIAS(1)
-    DF_BEGIN(1, 0) DF_TAPS(0, 0, 3) DF_TRANS(0) DF_SB DF_TAPS(0, 3, 6) DF_I(0, Q0) DF_SB DF_TAPS(0, 6, 9) DF_I(1, Q1) DF_SB
-    DF_BEGIN(1, 1) DF_TAPS(1, 0, 4) DF_SB DF_C(0, Q0) DF_SB DF_TAPS(1, 4, 9) DF_SB DF_C(1, Q1) DF_SB DF_RAW(1)
-    DF_BIAS(2)
-    DF_BEGIN(2, 0) DF_TAPS(0, 0, 3) DF_TRANS(1) DF_SB DF_TAPS(0, 3, 6) DF_I(2, Q0) DF_SB DF_TAPS(0, 6, 9) DF_I(3, Q1) DF_SB
-    DF_BEGIN(2, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(2, Q0) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(3, Q1) DF_SB DF_TAPS(1, 6, 9) DF_I(4, Q0) DF_SB DF_RAW(2)
-    DF_BIAS(3)
-    DF_BEGIN(3, 0) DF_TAPS(0, 0, 2) DF_TRANS(2) DF_SB DF_TAPS(0, 2, 4) DF_I(5, Q1) DF_SB DF_TAPS(0, 4, 7) DF_SB DF_C(4, Q0) DF_SB DF_TAPS(0, 7, 9) DF_I(6, Q0) DF_SB
-    DF_BEGIN(3, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(5, Q1) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(6, Q0) DF_SB DF_TAPS(1, 6, 9) DF_I(7, Q1) DF_SB DF_RAW(3)
-    DF_BIAS(4)
-    DF_BEGIN(4, 0) DF_TAPS(0, 0, 2) DF_TRANS(3) DF_SB DF_TAPS(0, 2, 4) DF_SB DF_C(7, Q1) DF_SB DF_TAPS(0, 4, 7) DF_I(8, Q0) DF_SB DF_TAPS(0, 7, 9) DF_I(9, Q1) DF_SB
-    DF_BEGIN(4, 1) DF_TAPS(1, 0, 4) DF_SB DF_C(8, Q0) DF_SB DF_TAPS(1, 4, 9) DF_SB DF_C(9, Q1) DF_SB DF_RAW(4)
-    DF_BIAS(5)
-    DF_BEGIN(5, 0) DF_TAPS(0, 0, 3) DF_TRANS(4) DF_SB DF_TAPS(0, 3, 6) DF_I(10, Q0) DF_SB DF_TAPS(0, 6, 9) DF_I(11, Q1) DF_SB
-    DF_BEGIN(5, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(10, Q0) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(11, Q1) DF_SB DF_TAPS(1, 6, 9) DF_I(12, Q0) DF_SB DF_RAW(5)
-    DF_BIAS(6)
-    DF_BEGIN(6, 0) DF_TAPS(0, 0, 2) DF_TRANS(5) DF_SB DF_TAPS(0, 2, 4) DF_I(13, Q1) DF_SB DF_TAPS(0, 4, 7) DF_SB DF_C(12, Q0) DF_SB DF_TAPS(0, 7, 9) DF_I(14, Q0) DF_SB
-    DF_BEGIN(6, 1) DF_TAPS(1, 0, 3) DF_SB DF_C(13, Q1) DF_SB DF_TAPS(1, 3, 6) DF_SB DF_C(14, Q0) DF_SB DF_TAPS(1, 6, 9) DF_I(15, Q1) DF_SB DF_RAW(6)
-    DF_TRANS(6) DF_I(16, Q0) DF_SB DF_C(15, Q1) DF_SB DF_I(17, Q1) DF_SB DF_TAIL_REQUEST DF_C(16, Q0) DF_SB DF_C(17, Q1) DF_TAIL_COMMIT
-#else
+// Lab-only text of dcn_fused.inc (fp32 build), included at namespace scope under CRFP_LAB: dcn_fused2_kernel (lost its A/B in round 5)
+// and the lab library's choice among the kernel forms.
 // ---------------------------------------------------------------- round 3: the same fusion with ROLE-SPECIALISED waves
 // dcn_fused_kernel<8> runs conv taps and sampler items in ONE instruction stream per wave: 246 VGPRs = two waves per SIMD, and
 // whatever stalls the stream (an LDS operand read in front of an MFMA, a gather that has not landed, a barrier) stalls both roles'
@@ -195,23 +167,13 @@ __global__ __launch_bounds__(D2_NT, 1) void dcn_fused2_kernel(const DcnFuseArgs 
 }
 
 // The lab library's choice among the kernel forms (environment, read once): CRFP_DCN_FUSE_PROBE = the probe word of the timing experiments,
-// CRFP_DCN_FUSE_OCC = print the 4-wave form's occupancy, CRFP_DCN_FUSE_V=2 = the role-specialised kernel above, CRFP_DCN_FUSE_NW=4 = the 4-wave
+// CRFP_DCN_FUSE_V=2 = the role-specialised kernel above, CRFP_DCN_FUSE_NW=4 = the 4-wave
 // form (151.6 vs 165.3 us per launch same-box for the 8-wave one).  Returns false when the launch is the product's to make (with b.probe set).
 static bool launch_dcn_fused_lab(DcnFuseArgs& b, hipStream_t s) {
-    static const int probe_env = getenv("CRFP_DCN_FUSE_PROBE") ? atoi(getenv("CRFP_DCN_FUSE_PROBE")) : 0;
-    b.probe = probe_env;
-    static bool once = false;
-    if (!once && getenv("CRFP_DCN_FUSE_OCC")) {
-        once = true;
-        int nb = -1;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dcn_fused_kernel<4>, 256, 0);
-        fprintf(stderr, "dcn_fused_kernel: %d workgroups per CU (hip error %d)\n", nb, (int)e);
-    }
-    static const int nw_lab = getenv("CRFP_DCN_FUSE_NW") ? atoi(getenv("CRFP_DCN_FUSE_NW")) : 8;
-    static const int fuse_v_lab = getenv("CRFP_DCN_FUSE_V") ? atoi(getenv("CRFP_DCN_FUSE_V")) : 1;
+    b.probe = CRFP_LAB_KNOB("CRFP_DCN_FUSE_PROBE", 0);
+    const int nw_lab = CRFP_LAB_KNOB("CRFP_DCN_FUSE_NW", 8), fuse_v_lab = CRFP_LAB_KNOB("CRFP_DCN_FUSE_V", 1);
     if (nw_lab == 8 && fuse_v_lab == 2) dcn_fused2_kernel<<<dim3((b.W + 31) / 32, (b.H + 7) / 8, b.N), D2_NT, 0, s>>>(b);
     else if (nw_lab != 8) dcn_fused_kernel<4><<<dim3((b.W + 31) / 32, (b.H + 3) / 4, b.N), 256, 0, s>>>(b);
     else return false;
     return true;
 }
-#endif

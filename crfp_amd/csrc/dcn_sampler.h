@@ -15,15 +15,13 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // check of a raw buffer load returns 0.  No per-corner validity logic and no 64-bit address math is
 // left on the VALU: one 32-bit byte offset per sample, the other three corners ride on the scalar
 // offset operand (+16, +pitch, +pitch+16).
-#ifndef CRFP_GATHER_AUX
-#define CRFP_GATHER_AUX 0   // cache-policy bits of the gather loads (gfx942+: 1 = sc0, 2 = nt, 16 = sc1)
-#endif
+constexpr int kGatherAux = 0;   // cache-policy bits of the gather loads (gfx942+: 1 = sc0, 2 = nt, 16 = sc1)
 // one pixel quad (16 bytes of fp32 / 8 bytes of bf16) at byte offset voff + soff; out-of-range reads return 0
 __device__ __forceinline__ f32x4 bload(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
 #ifdef CRFP_ACT_BF16
-    return quad_from_bits(__builtin_bit_cast(cu32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, CRFP_GATHER_AUX)));
+    return quad_from_bits(__builtin_bit_cast(cu32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, kGatherAux)));
 #else
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, CRFP_GATHER_AUX));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, kGatherAux));
 #endif
 }
 constexpr int QB = kQuadBytes;   // bytes per pixel quad of a gathered plane
@@ -36,7 +34,7 @@ constexpr int QB = kQuadBytes;   // bytes per pixel quad of a gathered plane
 #ifdef CRFP_ACT_BF16
 typedef u32x4 pairraw_t;
 __device__ __forceinline__ pairraw_t bload_pair(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, CRFP_GATHER_AUX);
+    return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, kGatherAux);
 }
 __device__ __forceinline__ f32x4 pair_lo(const pairraw_t& p) { return quad_from_bits(cu32x2{p.x, p.y}); }
 __device__ __forceinline__ f32x4 pair_hi(const pairraw_t& p) { return quad_from_bits(cu32x2{p.z, p.w}); }
@@ -80,13 +78,8 @@ __device__ __forceinline__ void dcn_issue_one(DcnPair& P, int pi, __amdgpu_buffe
     P.w[pi][0] = a * hx; P.w[pi][1] = a * lx; P.w[pi][2] = b * hx; P.w[pi][3] = b * lx;
     // element index fy * PW + fx in float (exact below 2^24: a 2x-resolution plane has < 2^22 elements), one conversion
     const int vo = (int)__builtin_fmaf(fy, (float)PW, fx) * QB + hbase + gi * plane_b;
-#if defined(CRFP_DF_PROBE_CT) && (CRFP_DF_PROBE_CT & 128)   // A/B builds: coordinates and weights, but no corner gathers (results wrong)
-    P.tp[pi] = pairraw_t{}; P.bt[pi] = pairraw_t{};
-    asm volatile("" ::"v"(vo));
-#else
     P.tp[pi] = bload_pair(rx, vo, 0);
     P.bt[pi] = bload_pair(rx, vo, pitch);
-#endif
 }
 
 __device__ __forceinline__ void dcn_issue_pair(DcnPair& P, __amdgpu_buffer_rsrc_t rx, const DcnOff& O, int hb, int v, float fy0,

@@ -602,23 +602,12 @@ struct Runner {
         c.ovf = ovf(); c.ovf_div = ovf_div; c.ovf_add = ovf_add;
         rc = launch_narrow_chain(a, b, c, res, name, s);
     }
-#ifndef CRFP_NARROW_CHAIN
-// bit 0: dcn_3's dcn_block.0 -> .2 -> conv_fuse, bit 1: forward_resblocks_3's main.0 -> conv1 -> conv2 (+ x).  Shipped: 2.  Same box, fp32 @A
-// (profiles/r06_narrow_chain_ab.txt): the residual chain 87.1 us against 41.1 + 50.8; dcn_3's chain 148.4 us against 59.5 + 28.0 + 42.2 -- its A
-// stage (three input quads on 1.33x the pixels) makes it issue-bound at three workgroups per CU, so it stays three launches.
-#define CRFP_NARROW_CHAIN 2
-#endif
-#ifndef CRFP_NARROW_CHAIN_BF16
-#define CRFP_NARROW_CHAIN_BF16 3   // bf16 build: both chains (its block-diagonal MFMA makes the stages' extra pixels cheap: profiles/r06_narrow_chain_ab.txt)
-#endif
-#ifdef CRFP_LAB   // lab library: CRFP_NARROW_CHAIN=<mask> at run time (tests/test_gpu_round6.py compares the chains with the launches they replace)
-    static int chain_mask() {
-        static const int m = getenv("CRFP_NARROW_CHAIN") ? atoi(getenv("CRFP_NARROW_CHAIN")) : (kActBf16 ? CRFP_NARROW_CHAIN_BF16 : CRFP_NARROW_CHAIN);
-        return m;
-    }
-#else
-    static constexpr int chain_mask() { return kActBf16 ? CRFP_NARROW_CHAIN_BF16 : CRFP_NARROW_CHAIN; }
-#endif
+    // Which 8x conv chains run as one launch.  Bit 0: dcn_3's dcn_block.0 -> .2 -> conv_fuse, bit 1: forward_resblocks_3's main.0 -> conv1 ->
+    // conv2 (+ x).  fp32: 2.  Same box, fp32 @A (profiles/r06_narrow_chain_ab.txt): the residual chain 87.1 us against 41.1 + 50.8; dcn_3's
+    // chain 148.4 us against 59.5 + 28.0 + 42.2 -- its A stage (three input quads on 1.33x the pixels) makes it issue-bound at three
+    // workgroups per CU, so it stays three launches.  bf16 build: both chains (its block-diagonal MFMA makes the stages' extra pixels cheap).
+    // Lab library: CRFP_NARROW_CHAIN=<mask> at run time (tests/test_gpu_round6.py compares the chains with the launches they replace).
+    static int chain_mask() { return CRFP_LAB_KNOB("CRFP_NARROW_CHAIN", kActBf16 ? 3 : 2); }
     // The one 8x-resolution conv pair that runs fused into one launch: res3.conv1 -> conv2(+x), fp32 build only.  Measured @A
     // fp32, pair vs the two single kernels: res3 47.2 vs 57.8 us (bf16 46.7 vs 56.1).  Three more pairs were measured, lost and have no call
     // site any more: encoder_hr.0->.2 71.5 vs 67.6; dcn_3 conv_fuse->offset/mask 80 vs 76.8; dcn_3 block.0->.2 (3 input quads, one workgroup
@@ -626,17 +615,9 @@ struct Runner {
     // 1.16x the pixels with 9 instead of 4.5 LDS reads per pixel and tap row -- so only the pair whose A has ONE input quad wins.  In the
     // bf16 build the single convs run on the bf16 MFMA and two of them beat the pair kernel (41 vs 47.5 us).
     static constexpr bool res3_pair = !kActBf16;
-#ifndef CRFP_STATE_FROM_EPILOGUE
-#define CRFP_STATE_FROM_EPILOGUE 1   // A/B builds: 0 = the separate lrelu pass
-#endif
-#ifdef CRFP_LAB   // lab library: CRFP_STATE_FROM_EPILOGUE=0 at run time keeps the separate lrelu pass
-    static bool state_from_epilogue() {
-        static const bool on = getenv("CRFP_STATE_FROM_EPILOGUE") ? atoi(getenv("CRFP_STATE_FROM_EPILOGUE")) != 0 : CRFP_STATE_FROM_EPILOGUE != 0;
-        return on;
-    }
-#else
-    static constexpr bool state_from_epilogue() { return CRFP_STATE_FROM_EPILOGUE != 0; }
-#endif
+    // the new state away from the fovea comes from the epilogue of forward_resblocks_3's last conv (NarrowArgs::dst2); lab library:
+    // CRFP_STATE_FROM_EPILOGUE=0 at run time keeps the separate lrelu pass
+    static bool state_from_epilogue() { return CRFP_LAB_KNOB("CRFP_STATE_FROM_EPILOGUE", 1) != 0; }
 
     // The fovea blend is a select under the mask (model/CRFP.py:1543-1544,1674-1675): what is computed only to be deselected -- the x8
     // frame stack, encoder_hr and conv_tttf away from the fovea -- is skipped tile by tile, same output bits.  CRFP_MASK_GATE=0: dense launches

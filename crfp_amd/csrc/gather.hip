@@ -143,7 +143,8 @@ __device__ __forceinline__ void warp_quads(__amdgpu_buffer_rsrc_t r, int voff, i
 
 // NW waves = NW rows x 64 pixels per workgroup: with 4-row tiles the source window of a tile (rows + shift + 1 bilinear row) is
 // 1.27x the tile and neighbouring tiles sit on different XCDs (no shared L2): PMC 127.6 MB for 106.9 MB algorithmic (round 2).
-// 8-row tiles (window 1.14x) were measured in round 3 and are no faster (lab: CRFP_WARP_NW=8): the kernel is latency-, not byte-bound.
+// 8-row tiles (window 1.14x) were measured in round 3 and are no faster (26.5 vs 26.0-26.4 us same box): the kernel is latency-, not
+// byte-bound.
 template <int NQA, int NQB, int NW>
 __global__ __launch_bounds__(64 * NW) void flow_warp_p4_dual_kernel(const float* __restrict__ xa, const float* __restrict__ xb_,
                                                                     const float* __restrict__ flow, float* __restrict__ outa,
@@ -185,19 +186,14 @@ __global__ __launch_bounds__(64 * NW) void flow_warp_p4_dual_kernel(const float*
 // (one batch per thread, 57 600 workgroups) reaches 0.70.  Here every thread owns ONE batch: group g of a pixel = GQ quads of prev2 or of
 // the carry, all its gathers in flight at once, (GA + GB) x as many workgroups; flow read and coordinate arithmetic are repeated per
 // group (8 of ~470 bytes per pixel).  Same operations on the same values per output element: bit-identical.
-template <int NQA, int NQB, int GQ, int NW = 4, bool BAND = false>
-__global__ __launch_bounds__(64 * NW) void flow_warp_p4_dual_split_kernel(const float* __restrict__ xa, const float* __restrict__ xb_,
+template <int NQA, int NQB, int GQ>
+__global__ __launch_bounds__(256) void flow_warp_p4_dual_split_kernel(const float* __restrict__ xa, const float* __restrict__ xb_,
                                                                       const float* __restrict__ flow, float* __restrict__ outa,
                                                                       float* __restrict__ outb, int H, int W, const WarpDualStrides bs) {
     constexpr int GA = (NQA + GQ - 1) / GQ, GB = (NQB + GQ - 1) / GQ, NG = GA + GB;
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (BAND) {   // 1-D launch: XCD x walks one contiguous band of the (group, tile row, tile column) list (xcd_band_tile)
-        const int gx = (W + 63) / 64, gy = (H + NW - 1) / NW;
-        const int t = xcd_band_tile(blockIdx.x, gridDim.x);
-        bx = t % gx; by = (t / gx) % gy; bz = t / (gx * gy);
-    }
+    const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     const int px = bx * 64 + (threadIdx.x & 63);
-    const int py = by * NW + (threadIdx.x >> 6);
+    const int py = by * 4 + (threadIdx.x >> 6);
     if (px >= W || py >= H) return;
     const int g = bz % NG;
     const long long n = bz / NG;
@@ -230,43 +226,13 @@ __global__ __launch_bounds__(64 * NW) void flow_warp_p4_dual_split_kernel(const 
     else if (GQ > 3 && cnt == 3) warp_quads<3>(r, voff, pitch, plane_b, w00, w01, w10, w11, os, oplane);
 }
 
-#ifndef CRFP_WARP_SPLIT_DEFAULT
-#define CRFP_WARP_SPLIT_DEFAULT 4
-#endif
 // prev2 (8 quads) + carry (6 quads) by flow2, one launch; zeros padding, P4 sources
 int launch_flow_warp_p4_dual_8_6(const float* xa, const float* xb, const float* flow, float* outa, float* outb, int H, int W,
                                  hipStream_t s, int N, const WarpDualStrides& bs) {
     const double px = (double)N * H * W;
     ProfScope prof("flow_warp_q4_c32+c24", s, px * (2.0 * 14 * 4 * sizeof(act_t) + 8), px * 14 * 4 * 7.0);
-#ifdef CRFP_LAB
-    static const int nw8 = getenv("CRFP_WARP_NW") && atoi(getenv("CRFP_WARP_NW")) == 8;
-    if (nw8) {   // 8-row tiles (window 1.14x instead of 1.27x the tile): 26.5 vs 26.0-26.4 us same box @A -- not the traffic
-        flow_warp_p4_dual_kernel<8, 6, 8><<<dim3((W + 63) / 64, (H + 7) / 8, N), 512, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
-#ifdef CRFP_LAB
-    static const int split = getenv("CRFP_WARP_SPLIT") ? atoi(getenv("CRFP_WARP_SPLIT")) : CRFP_WARP_SPLIT_DEFAULT;   // A/B: 0 = round-2 kernel, 1 / 2 / 4 = quads per group
-#else
-    constexpr int split = CRFP_WARP_SPLIT_DEFAULT;
-#endif
     const dim3 g4((W + 63) / 64, (H + 3) / 4, N);
-#ifdef CRFP_LAB
-    static const int snw = getenv("CRFP_WARP_SNW") ? atoi(getenv("CRFP_WARP_SNW")) : 4;   // A/B: rows per workgroup of the split kernel
-    static const int band = getenv("CRFP_WARP_BAND") ? atoi(getenv("CRFP_WARP_BAND")) : 0;
-    if (split == 4 && band && snw == 4) { flow_warp_p4_dual_split_kernel<8, 6, 4, 4, true><<<dim3(g4.x * g4.y * N * 4, 1, 1), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs); CRFP_CHECK_LAUNCH(); return 0; }
-    if (split == 4 && band && snw == 8) { flow_warp_p4_dual_split_kernel<8, 6, 4, 8, true><<<dim3(g4.x * ((H + 7) / 8) * N * 4, 1, 1), 512, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs); CRFP_CHECK_LAUNCH(); return 0; }
-    if (split == 4 && snw == 8) { flow_warp_p4_dual_split_kernel<8, 6, 4, 8><<<dim3(g4.x, (H + 7) / 8, N * 4), 512, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs); CRFP_CHECK_LAUNCH(); return 0; }
-    if (split == 4 && snw == 16) { flow_warp_p4_dual_split_kernel<8, 6, 4, 16><<<dim3(g4.x, (H + 15) / 16, N * 4), 1024, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs); CRFP_CHECK_LAUNCH(); return 0; }
-    if (split == 2 && snw == 8) { flow_warp_p4_dual_split_kernel<8, 6, 2, 8><<<dim3(g4.x, (H + 7) / 8, N * 7), 512, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs); CRFP_CHECK_LAUNCH(); return 0; }
-    if (split == 4 && snw == 2) { flow_warp_p4_dual_split_kernel<8, 6, 4, 2><<<dim3(g4.x, (H + 1) / 2, N * 4), 128, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs); CRFP_CHECK_LAUNCH(); return 0; }
-#endif
-    if (split == 4 && N * 4 <= 65535) flow_warp_p4_dual_split_kernel<8, 6, 4><<<dim3(g4.x, g4.y, N * 4), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
-    else if (split == 2 && N * 7 <= 65535) flow_warp_p4_dual_split_kernel<8, 6, 2><<<dim3(g4.x, g4.y, N * 7), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
-#ifdef CRFP_LAB
-    else if (split == 1 && N * 14 <= 65535) flow_warp_p4_dual_split_kernel<8, 6, 1><<<dim3(g4.x, g4.y, N * 14), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
-#endif
+    if (N * 4 <= 65535) flow_warp_p4_dual_split_kernel<8, 6, 4><<<dim3(g4.x, g4.y, N * 4), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
     else flow_warp_p4_dual_kernel<8, 6, 4><<<g4, 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
     CRFP_CHECK_LAUNCH();
     return 0;
@@ -358,22 +324,21 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) { return __builtin_nontemp
 
 // x is P4 (see above).  VALU budget per sampling position: position (2), clamp (4), floor/frac (6),
 // modulated bilinear weights (6), byte offset (4), 16 FMAs for the 4-channel sample.
-// F16: the 32x32 GEMM runs on the fp16 MFMA with the exact two-term split of conv_mfma.hip (sample = s0 + 2^-11 s1, weights
-// pre-split; hi / lo accumulators): a pair of sampling positions (2 x 4 channels per lane half) is one K = 16 step = 3 MFMAs of
-// 32 cycles instead of 8 fp32 MFMAs of 64.  The C-ABI op keeps the fp32 MFMA (F16 = false).
+// The 32x32 GEMM on the fp32 MFMA: the C-ABI op and strict fp32.  (The engine's default is dcn_g8_pipe_kernel below, on the fp16 MFMA
+// with the exact two-term split of conv_mfma.hip.)  4 waves = 4 rows per workgroup, sampling positions consumed in pairs.
 #ifndef CRFP_ACT_BF16
-template <int NW, int NP, int MINW, bool F16>
-__global__ __launch_bounds__(64 * NW, MINW) void dcn_g8_kernel(const float* __restrict__ x, long long xb,
+__global__ __launch_bounds__(256, 4) void dcn_g8_kernel(const float* __restrict__ x, long long xb,
                                                         const float* __restrict__ offmask, long long omb,
                                                         const float* __restrict__ wpk, const float* __restrict__ bias,
                                                         float* __restrict__ out, long long ob, int H, int W) {
     // packed DCN weights (36 KB) are shared by the 4 waves of the workgroup through LDS
     __shared__ f32x4 wl[36 * 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < 36 * 64; i += 64 * NW) wl[i] = reinterpret_cast<const f32x4*>(wpk)[i];
+    constexpr int NP = 2;   // sampling positions whose 8 corner loads are issued back to back
+    for (int i = tid; i < 36 * 64; i += 256) wl[i] = reinterpret_cast<const f32x4*>(wpk)[i];
     const int j = lane & 31, h = lane >> 5;
     // (XCD-banded tile order measured here: traffic 316 -> 268 MB but +1.8 % time; the gathers keep the natural order)
-    const int px = blockIdx.x * 32 + j, py = blockIdx.y * NW + wave;
+    const int px = blockIdx.x * 32 + j, py = blockIdx.y * 4 + wave;
     const int n = blockIdx.z;
     const bool valid = px < W && py < H;
     const int cx = min(px, W - 1), cy = min(py, H - 1);
@@ -386,10 +351,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void dcn_g8_kernel(const float* __re
     const float fy0 = (float)(cy - 1), fx0 = (float)(cx - 1), fH = (float)H, fW = (float)W;
     const int hbase = 4 * h * plane_b + guard;
 
-    f32x16 acc, acl;
+    f32x16 acc;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { acc[e] = 0.0f; acl[e] = 0.0f; }
-    static_assert(!F16 || NP == 2, "the f16 path consumes sampling positions in pairs");
+    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
 
     // software pipeline: the (dy,dx) pairs and masks of iteration v+1 are in flight while the 16 corner
     // loads of iteration v (4 sampling positions x 4 corners, issued back to back) are consumed
@@ -430,45 +394,21 @@ __global__ __launch_bounds__(64 * NW, MINW) void dcn_g8_kernel(const float* __re
                 q10[pi] = bload(rx, vo, pitch);
                 q11[pi] = bload(rx, vo, pitch + 16);
             }
-            f32x4 vals[NP];
 #pragma unroll
             for (int pi = 0; pi < NP; ++pi) {
                 f32x4 val = q00[pi] * w00[pi];
                 val = __builtin_elementwise_fma(q01[pi], f32x4{w01[pi], w01[pi], w01[pi], w01[pi]}, val);
                 val = __builtin_elementwise_fma(q10[pi], f32x4{w10[pi], w10[pi], w10[pi], w10[pi]}, val);
                 val = __builtin_elementwise_fma(q11[pi], f32x4{w11[pi], w11[pi], w11[pi], w11[pi]}, val);
-                vals[pi] = val;
-                if (!F16) {
-                    const f32x4 wa = wl[(4 * v + hb + pi) * 64 + lane];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.x, val.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.y, val.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.z, val.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.w, val.w, acc, 0, 0, 0);
-                }
-            }
-            if (F16) {   // positions (4v+hb, 4v+hb+1) = pair u: lane half h supplies their 2 x 4 channels as k = 8h .. 8h+7
-                const float xs[8] = {vals[0].x, vals[0].y, vals[0].z, vals[0].w, vals[NP - 1].x, vals[NP - 1].y, vals[NP - 1].z, vals[NP - 1].w};
-                dcn_f16x8 b0, b1;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const _Float16 hh = (_Float16)xs[i];
-                    b0[i] = hh;
-                    b1[i] = (_Float16)((xs[i] - (float)hh) * 2048.0f);
-                }
-                const int u = (4 * v + hb) >> 1;
-                const dcn_f16x8 w0 = __builtin_bit_cast(dcn_f16x8, wl[(2 * u) * 64 + lane]);
-                const dcn_f16x8 w1 = __builtin_bit_cast(dcn_f16x8, wl[(2 * u + 1) * 64 + lane]);
-                acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b1, acl, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0, b0, acc, 0, 0, 0);
-                acl = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1, b0, acl, 0, 0, 0);
+                const f32x4 wa = wl[(4 * v + hb + pi) * 64 + lane];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.x, val.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.y, val.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.z, val.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa.w, val.w, acc, 0, 0, 0);
             }
         }
     }
     if (!valid) return;
-    if (F16) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] += acl[e] * (1.0f / 2048.0f);
-    }
     float* o = out + (long long)n * ob + ((long long)py * W + px) * 4;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -608,32 +548,9 @@ int launch_dcn_g8(const float* x, long long xb, const float* offmask, long long 
     if ((long long)(H + 1) * (W + 1) >= (1ll << 24)) { set_error("dcn_g8: plane of %d x %d exceeds the sampler's 2^24-element index range", H, W); return CRFP_E_UNSUPPORTED; }
     const double px = (double)N * H * W;
     ProfScope prof("dcnv2_g8_c32", s, px * ((32 + 32) * sizeof(act_t) + (144 + 72) * 4.0) + 32.0 * 32 * 9 * 4, 2.0 * px * 32 * 32 * 9 + px * 288 * 7);
-    int probe = 0;
-#ifdef CRFP_LAB
-    static const int probe_env = getenv("CRFP_DCN_PROBE") ? atoi(getenv("CRFP_DCN_PROBE")) : 0;
-    probe = probe_env;
-#endif
+    const int probe = CRFP_LAB_KNOB("CRFP_DCN_PROBE", 0);
     // measured 89.1 vs 91.7 us for the software-pipelined kernel (and no gain at all until sched_barrier pinned the gathers
     // ahead of the math): mostly bound by the L1 line rate of the 16-B corner gathers and VALU issue
-#if defined(CRFP_LAB) && !defined(CRFP_ACT_BF16)
-    static const int variant = getenv("CRFP_DCN_VARIANT") ? atoi(getenv("CRFP_DCN_VARIANT")) : 3;  // tuning knob (A/B: 3 fastest)
-    static const bool pipe = !(getenv("CRFP_DCN_PIPE") && atoi(getenv("CRFP_DCN_PIPE")) == 0);
-    if (f16 && !pipe) {
-        dcn_g8_kernel<4, 2, 4, true><<<dim3((W + 31) / 32, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W);
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-    if (!f16 && variant != 3) {
-        switch (variant) {
-            case 1: dcn_g8_kernel<8, 2, 6, false><<<dim3((W + 31) / 32, (H + 7) / 8, N), 512, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W); break;
-            case 2: dcn_g8_kernel<8, 4, 4, false><<<dim3((W + 31) / 32, (H + 7) / 8, N), 512, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W); break;
-            case 4: dcn_g8_kernel<8, 1, 8, false><<<dim3((W + 31) / 32, (H + 7) / 8, N), 512, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W); break;
-            default: dcn_g8_kernel<4, 4, 3, false><<<dim3((W + 31) / 32, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W); break;
-        }
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
 #ifdef CRFP_ACT_BF16
     if (!f16) { set_error("dcn_g8: the bf16 build has the split-fp16 GEMM only"); return CRFP_E_UNSUPPORTED; }
     dcn_g8_pipe_kernel<<<dim3((W + 31) / 32, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W, ovf, probe, ovf_div);
@@ -641,280 +558,19 @@ int launch_dcn_g8(const float* x, long long xb, const float* offmask, long long 
     if (f16)
         dcn_g8_pipe_kernel<<<dim3((W + 31) / 32, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W, ovf, probe, ovf_div);
     else
-        dcn_g8_kernel<4, 2, 4, false><<<dim3((W + 31) / 32, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W);
+        dcn_g8_kernel<<<dim3((W + 31) / 32, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask, omb, wpk, bias, out, ob, H, W);
 #endif
     CRFP_CHECK_LAUNCH();
     return 0;
 }
-
-#ifdef CRFP_LAB
-// ---------------------------------------------------------------- round-2 form of the dcn_3 sampler (lab reference for A/B)
-// shared by the 9 taps (dcn_3 of CRFP_DSV at 8x resolution; the reference tiles the 2+1 channels 9x,
-// model/CRFP.py:341-347 -- here they stay compact: offmask3 quad = (dy, dx, mask, -)).
-// HBM-bound: 16 B in (gathered) + 16 B offmask + 16 B out per pixel.
-// lds_max > 0: LDS staging of the reference-feature window (north star).  The workgroup (4 rows x 64 pixels) takes the
-// min / max of its sampling rows and columns (LDS atomics), and when the window [ymin, ymax] x [xmin, xmax] holds at most
-// lds_max elements it is loaded once, coalesced, into LDS and the 16 (36 at clamped borders) corner reads of every pixel come
-// from there instead of going through the texture addresser one lane at a time; a larger window (offsets that scatter the
-// tile's samples) falls back to the direct gathers below.  Same arithmetic either way: bit-identical results.
-#ifdef CRFP_ACT_BF16
-typedef cu32x2 winel_t;
-__device__ __forceinline__ f32x4 win_quad(const winel_t& e) { return quad_from_bits(e); }
-__device__ __forceinline__ winel_t win_load(__amdgpu_buffer_rsrc_t r, int voff) {
-    return __builtin_bit_cast(cu32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, CRFP_GATHER_AUX));
-}
-#else
-typedef f32x4 winel_t;
-__device__ __forceinline__ f32x4 win_quad(const winel_t& e) { return e; }
-__device__ __forceinline__ winel_t win_load(__amdgpu_buffer_rsrc_t r, int voff) { return bload(r, voff, 0); }
-#endif
-constexpr int DCN3_WIN = 40960 / (int)sizeof(winel_t);   // 40 KB window: 2560 fp32 / 5120 bf16 elements
-
-// FUSE: the 4 -> 3 offset / mask conv of dcn_3 (model/CRFP.py:337-347, NE_OFFMASK3 of conv_narrow.hip) runs inside this kernel: `offmask3`
-// is then the conv's INPUT (the dcn_3 offset feature g2, one Q4 quad), staged as a (4+2) x (64+2) fp32 halo tile in LDS; every thread
-// computes its own pixel's (dy, dx, mask) with the narrow kernel's 4x4x1-MFMA form in the same order (fp32 build: bit-identical to the
-// two-kernel path) and samples at once -- the 59 MB offset / mask tensor and one launch per frame disappear.
-template <bool FUSE>
-__global__ __launch_bounds__(256) void dcn3_r2_kernel(const float* __restrict__ x, long long xb,
-                                                   const float* __restrict__ offmask3, long long omb,
-                                                   const float* __restrict__ w, const float* __restrict__ bias,
-                                                   float* __restrict__ out, long long ob, int H, int W, int lds_max,
-                                                   const float* __restrict__ flow, const float* __restrict__ wom,
-                                                   const float* __restrict__ bom) {
-    extern __shared__ __attribute__((aligned(16))) char dcn3_dyn_lds[];   // the window: allocated at launch only when lds_max > 0
-    winel_t* const win = reinterpret_cast<winel_t*>(dcn3_dyn_lds);
-    __shared__ int bnd[4];   // ymin, ymax, xmin, xmax of the tile's corner rows / columns
-    const int px = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int py = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int n = blockIdx.z;
-    const bool live = px < W && py < H;
-    const int cpx = min(px, W - 1), cpy = min(py, H - 1);
-    const long long pix = (long long)cpy * W + cpx;
-    f32x4 om;
-    if constexpr (FUSE) {
-        __shared__ f32x4 gt[6][66];
-        __shared__ f32x4 wlo[36];   // [tap][cout] -> float4 over the 4 input channels
-        const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
-        if (tid < 36) {
-            const float4 wv = reinterpret_cast<const float4*>(wom)[tid];   // packed (tap, comp) -> 4 couts (narrow_pack_kernel, kq = 1)
-            float* wf = reinterpret_cast<float*>(wlo) + (tid >> 2) * 16 + (tid & 3);
-            wf[0] = wv.x; wf[4] = wv.y; wf[8] = wv.z; wf[12] = wv.w;
-        }
-        const act_t* g2 = as_act(offmask3) + (long long)n * omb;
-        const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int idx = tid + 256 * t;
-            if (idx < 6 * 66) {
-                const int r = idx / 66, c = idx - r * 66;
-                const int gy = by0 + r - 1, gx = bx0 + c - 1;
-                const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
-                const cf32x4 v = ldq(g2 + ((long long)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)) * 4);
-                (&gt[0][0])[idx] = ok ? v : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            }
-        }
-        const float2 fl = ldnt2(flow + pix * 2);
-        __syncthreads();
-        const float4 b4 = *reinterpret_cast<const float4*>(bom);
-        f32x4 a4 = f32x4{b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const f32x4 wv = wlo[(ky * 3 + kx) * 4 + (tx & 3)];
-                const f32x4 u = gt[ty + ky][tx + kx];
-                a4 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.x, u.x, a4, 0, 0, 0);
-                a4 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.y, u.y, a4, 0, 0, 0);
-                a4 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.z, u.z, a4, 0, 0, 0);
-                a4 = __builtin_amdgcn_mfma_f32_4x4x1f32(wv.w, u.w, a4, 0, 0, 0);
-            }
-        om = f32x4{tanh10_plus(a4.x, 10.0f + fl.y), tanh10_plus(a4.y, 10.0f + fl.x), fast_sigmoid(a4.z), 0.0f};
-    } else {
-        om = ldg4(offmask3 + (long long)n * omb + pix * 4);   // read once: non-temporal
-    }
-    const int PW = W + 1, pitch = PW * QB, plane_b = (H + 1) * pitch;
-    const int guard = pitch + QB;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)const_cast<act_t*>(as_act(x) + (long long)n * xb) - guard, 0, plane_b + guard, 0x00020000);
-    const float fy0 = (float)(cpy - 1), fx0 = (float)(cpx - 1), fH = (float)H, fW = (float)W;
-    // per-row / per-column sampling coordinates exactly as the reference forms them per tap:
-    // (float)(y - 1 + ky) + dy, clamped into [-1, H] (outside that range the sample is 0 either way)
-    float ly[3], lx[3];
-    int iy[3], ix[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float sy = fminf(fmaxf((fy0 + (float)k) + om.x, -1.0f), fH);
-        const float sx = fminf(fmaxf((fx0 + (float)k) + om.y, -1.0f), fW);
-        const float fy = floorf(sy), fx = floorf(sx);
-        ly[k] = sy - fy; lx[k] = sx - fx;
-        iy[k] = (int)fy; ix[k] = (int)fx;
-    }
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    // The 9 taps share one (dy,dx): away from the borders their integer parts advance by exactly one
-    // per tap, so the 36 bilinear corners are a 4x4 neighbourhood -> 16 loads instead of 36.  The
-    // fractional parts stay per row / column (float rounding of y-1+ky+dy differs per ky).
-    const bool regular = iy[1] == iy[0] + 1 && iy[2] == iy[0] + 2 && ix[1] == ix[0] + 1 && ix[2] == ix[0] + 2;
-    bool use_lds = false;
-    int ymin = 0, xmin = 0, ww = 1;
-    if (lds_max > 0) {   // kernel-uniform
-        if (threadIdx.x == 0) { bnd[0] = 0x7fffffff; bnd[1] = -0x7fffffff; bnd[2] = 0x7fffffff; bnd[3] = -0x7fffffff; }
-        __syncthreads();
-        // wave-level min / max first (one LDS atomic per wave and bound instead of one per lane)
-        int a0 = iy[0], a1 = iy[2] + 1, a2 = ix[0], a3 = ix[2] + 1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            a0 = min(a0, __shfl_xor(a0, o)); a1 = max(a1, __shfl_xor(a1, o));
-            a2 = min(a2, __shfl_xor(a2, o)); a3 = max(a3, __shfl_xor(a3, o));
-        }
-        if ((threadIdx.x & 63) == 0) { atomicMin(&bnd[0], a0); atomicMax(&bnd[1], a1); atomicMin(&bnd[2], a2); atomicMax(&bnd[3], a3); }
-        __syncthreads();
-        ymin = bnd[0]; xmin = bnd[2];
-        const int wh = bnd[1] - ymin + 1;
-        ww = bnd[3] - xmin + 1;
-        use_lds = wh * ww <= min(lds_max, DCN3_WIN);
-        if (use_lds) {
-            const int nel = wh * ww;
-            const float rww = 1.0f / (float)ww;
-            for (int idx = threadIdx.x; idx < nel; idx += 256) {
-                int r = (int)((float)idx * rww);          // idx / ww for idx < 2^13: fix the float estimate by one step
-                r -= (r * ww > idx); r += ((r + 1) * ww <= idx);
-                const int c = idx - r * ww;
-                win[idx] = win_load(rx, ((ymin + r) * PW + (xmin + c)) * QB + guard);
-            }
-            __syncthreads();
-        }
-    }
-    if (use_lds) {
-        if (__all(regular)) {
-            const int base = (iy[0] - ymin) * ww + (ix[0] - xmin);
-            f32x4 nb[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) nb[r][c] = win_quad(win[base + r * ww + c]);
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int tap = ky * 3 + kx;
-                    const float hy = 1.0f - ly[ky], hx = 1.0f - lx[kx];
-                    const f32x4 v = nb[ky][kx] * (hy * hx) + nb[ky][kx + 1] * (hy * lx[kx]) + nb[ky + 1][kx] * (ly[ky] * hx) +
-                                    nb[ky + 1][kx + 1] * (ly[ky] * lx[kx]);
-#pragma unroll
-                    for (int o = 0; o < 4; ++o)
-                        acc[o] = fmaf(w[(o * 4 + 3) * 9 + tap], v.w,
-                                      fmaf(w[(o * 4 + 2) * 9 + tap], v.z,
-                                           fmaf(w[(o * 4 + 1) * 9 + tap], v.y, fmaf(w[(o * 4 + 0) * 9 + tap], v.x, acc[o]))));
-                }
-        } else {
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int tap = ky * 3 + kx;
-                    const float hy = 1.0f - ly[ky], hx = 1.0f - lx[kx];
-                    const int base = (iy[ky] - ymin) * ww + (ix[kx] - xmin);
-                    const f32x4 v = win_quad(win[base]) * (hy * hx) + win_quad(win[base + 1]) * (hy * lx[kx]) +
-                                    win_quad(win[base + ww]) * (ly[ky] * hx) + win_quad(win[base + ww + 1]) * (ly[ky] * lx[kx]);
-#pragma unroll
-                    for (int o = 0; o < 4; ++o)
-                        acc[o] = fmaf(w[(o * 4 + 3) * 9 + tap], v.w,
-                                      fmaf(w[(o * 4 + 2) * 9 + tap], v.z,
-                                           fmaf(w[(o * 4 + 1) * 9 + tap], v.y, fmaf(w[(o * 4 + 0) * 9 + tap], v.x, acc[o]))));
-                }
-        }
-    } else if (__all(regular)) {
-        const int vo = (iy[0] * PW + ix[0]) * QB + guard;
-        pairraw_t nbp[4][2];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) nbp[r][c] = bload_pair(rx, vo, r * pitch + 2 * c * QB);
-        __builtin_amdgcn_sched_barrier(0);   // all gathers in flight together (hipcc otherwise issues and waits row by row)
-        f32x4 nb[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            nb[r][0] = pair_lo(nbp[r][0]); nb[r][1] = pair_hi(nbp[r][0]);
-            nb[r][2] = pair_lo(nbp[r][1]); nb[r][3] = pair_hi(nbp[r][1]);
-        }
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int tap = ky * 3 + kx;
-                const float hy = 1.0f - ly[ky], hx = 1.0f - lx[kx];
-                const f32x4 v = nb[ky][kx] * (hy * hx) + nb[ky][kx + 1] * (hy * lx[kx]) + nb[ky + 1][kx] * (ly[ky] * hx) +
-                                nb[ky + 1][kx + 1] * (ly[ky] * lx[kx]);
-#pragma unroll
-                for (int o = 0; o < 4; ++o)
-                    acc[o] = fmaf(w[(o * 4 + 3) * 9 + tap], v.w,
-                                  fmaf(w[(o * 4 + 2) * 9 + tap], v.z,
-                                       fmaf(w[(o * 4 + 1) * 9 + tap], v.y, fmaf(w[(o * 4 + 0) * 9 + tap], v.x, acc[o]))));
-            }
-    } else {
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int tap = ky * 3 + kx;
-                const float hy = 1.0f - ly[ky], hx = 1.0f - lx[kx];
-                const int vo = (iy[ky] * PW + ix[kx]) * QB + guard;
-                const pairraw_t tp = bload_pair(rx, vo, 0), bt = bload_pair(rx, vo, pitch);
-                const f32x4 v = pair_lo(tp) * (hy * hx) + pair_hi(tp) * (hy * lx[kx]) + pair_lo(bt) * (ly[ky] * hx) + pair_hi(bt) * (ly[ky] * lx[kx]);
-#pragma unroll
-                for (int o = 0; o < 4; ++o)
-                    acc[o] = fmaf(w[(o * 4 + 3) * 9 + tap], v.w,
-                                  fmaf(w[(o * 4 + 2) * 9 + tap], v.z,
-                                       fmaf(w[(o * 4 + 1) * 9 + tap], v.y, fmaf(w[(o * 4 + 0) * 9 + tap], v.x, acc[o]))));
-            }
-    }
-    if (!live) return;
-    stq(as_act(out) + (long long)n * ob + ((long long)py * W + px) * 4,
-        cf32x4{acc[0] * om.z + bias[0], acc[1] * om.z + bias[1], acc[2] * om.z + bias[2], acc[3] * om.z + bias[3]});
-}
-
-static int launch_dcn3_r2(const float* x, long long xb, const float* offmask3, long long omb, const float* w,
-                const float* bias, float* out, long long ob, int N, int H, int W, hipStream_t s) {
-    const double px = (double)N * H * W;
-    // algorithmic bytes reported BOTH ways in DESIGN.md; the profiler record carries the compact
-    // figure (4 in + 2 off + 1 mask + 4 out floats per pixel) that this kernel actually needs
-    ProfScope prof("dcnv2_shared_c4", s, px * ((4 + 4) * sizeof(act_t) + (2 + 1) * 4.0), px * (2.0 * 4 * 4 * 9 + 36 * 7));
-    dim3 grid((W + 63) / 64, (H + 3) / 4, N);
-    // LDS staging of the sampling window (the north star's design) is built in and bit-identical, but it LOSES on MI355X: @A
-    // fp32, stress weights (residuals over the whole +-10 px) 98.7-106 us against 77.7 us for the direct gathers, whatever the
-    // window budget (700 / 1200 / 2560 elements); SURVEY-8d weights (offset_std 0.02, residuals of a few px) 96.3-100.1 against
-    // 73.1 us.  The min / max reduction, two barriers, the staging loop and 40 KB of LDS per workgroup cost more than the 16
-    // per-lane gathers they replace -- the kernel is bound by VALU issue (~400 instructions per pixel: 9 bilinear taps x 4
-    // channels + the 4x4 channel mix), not by the texture path.  Lab library: CRFP_DCN3_LDS=<max window elements>.
-    int lds_max = 0;
-#ifdef CRFP_LAB
-    static const int lds_env = getenv("CRFP_DCN3_LDS") ? atoi(getenv("CRFP_DCN3_LDS")) : 0;
-    lds_max = lds_env;
-#endif
-    dcn3_r2_kernel<false><<<grid, 256, lds_max > 0 ? DCN3_WIN * sizeof(winel_t) : 0, s>>>(x, xb, offmask3, omb, w, bias, out, ob, H, W, lds_max,
-                                                                                        nullptr, nullptr, nullptr);
-    CRFP_CHECK_LAUNCH();
-    return 0;
-}
-
-// dcn_3 with its offset / mask conv inside: g2 = the conv's input (one Q4 quad), wom / bom = its narrow-packed weights and bias
-static int launch_dcn3_fused_r2(const float* x, long long xb, const float* g2, long long gb, const float* flow, const float* wom, const float* bom,
-                      const float* w, const float* bias, float* out, long long ob, int N, int H, int W, hipStream_t s) {
-    const double px = (double)N * H * W;
-    ProfScope prof("dcnv2_shared_c4_fused", s, px * ((4 + 4 + 4) * sizeof(act_t) + 2 * 4.0), px * (2.0 * 4 * 4 * 9 + 36 * 7 + 2.0 * 4 * 3 * 9));
-    dcn3_r2_kernel<true><<<dim3((W + 63) / 64, (H + 3) / 4, N), 256, 0, s>>>(x, xb, g2, gb, w, bias, out, ob, H, W, 0, flow, wom, bom);
-    CRFP_CHECK_LAUNCH();
-    return 0;
-}
-
-#endif  // CRFP_LAB
 
 // ---------------------------------------------------------------- DCNv2 4->4, 1 group, offsets and mask
 // shared by the 9 taps (dcn_3 of CRFP_DSV at 8x resolution; the reference tiles the 2+1 channels 9x,
 // model/CRFP.py:341-347 -- here they stay compact: offmask3 quad = (dy, dx, mask, -)).
 // HBM-bound by bytes: 16 B in (gathered) + 16 B offmask (or, FUSE, the offset feature) + 16 B out per pixel.
 //
-// Round 3 form (the round-2 kernel, incl. its LDS-window experiment, lives on in the lab library as dcn3_r2_kernel):
+// Against the round-2 kernel (one tile per workgroup, 144 v_fma_f32 for the channel mix; its LDS staging of the sampling window lost
+// to the direct gathers, 96-106 against 73-78 us -- DESIGN.md):
 //  * the 4x4 channel mix of the 9 sampled quads runs on v_mfma_f32_4x4x1_16b_f32 like the offset conv above it: lane l
 //    supplies A = the weight row of cout l&3 and B = its own pixel's sampled channel, and receives the 4 couts of its own
 //    pixel -- 36 MFMAs instead of 144 v_fma_f32, same products in the same order (fp32 in, fp32 accumulate: exact);
@@ -946,19 +602,15 @@ __device__ __forceinline__ f32x4 mix4(const f32x4& wv, const f32x4& v, f32x4 a) 
     return a;
 }
 
-#ifdef CRFP_DCN3_WPE   // A/B builds: force the register budget of N waves per SIMD
-#define DCN3_WPE_ATTR __attribute__((amdgpu_waves_per_eu(CRFP_DCN3_WPE, CRFP_DCN3_WPE)))
-#else
-#define DCN3_WPE_ATTR
-#endif
-template <bool FUSE, int NT>
-__global__ __launch_bounds__(256) DCN3_WPE_ATTR void dcn3_kernel(const float* __restrict__ x, long long xb,
+constexpr int DCN3_NT = 3;   // tiles per workgroup strip (12 rows x 64 pixels)
+template <bool FUSE>
+__global__ __launch_bounds__(256) void dcn3_kernel(const float* __restrict__ x, long long xb,
                                                    const float* __restrict__ offmask3, long long omb,
                                                    const float* __restrict__ w, const float* __restrict__ bias,
                                                    float* __restrict__ out, long long ob, int H, int W,
                                                    const float* __restrict__ flow, const float* __restrict__ wom,
                                                    const float* __restrict__ bom, long long fb) {
-    constexpr int TR = 4 * NT;                       // rows of the strip
+    constexpr int NT = DCN3_NT, TR = 4 * NT;         // rows of the strip
     __shared__ f32x4 wmix[36];                       // dcn weight: [tap][cout] -> float4 over the 4 input channels
     __shared__ f32x4 gt[FUSE ? TR + 2 : 1][66];      // FUSE: halo tile of the offset feature
     __shared__ f32x4 wlo[FUSE ? 36 : 1];             // FUSE: offset / mask conv weight, same layout
@@ -1088,30 +740,14 @@ __global__ __launch_bounds__(256) DCN3_WPE_ATTR void dcn3_kernel(const float* __
     }
 }
 
-constexpr int DCN3_NT = 3;   // tiles per workgroup strip (12 rows x 64 pixels)
-#ifdef CRFP_LAB
-static int dcn3_nt_env() { static const int v = getenv("CRFP_DCN3_NT") ? atoi(getenv("CRFP_DCN3_NT")) : DCN3_NT; return v; }
-#endif
-
 int launch_dcn3(const float* x, long long xb, const float* offmask3, long long omb, const float* w,
                 const float* bias, float* out, long long ob, int N, int H, int W, hipStream_t s) {
-#ifdef CRFP_LAB
-    static const bool r2 = getenv("CRFP_DCN3_R2") && atoi(getenv("CRFP_DCN3_R2"));
-    if (r2) return launch_dcn3_r2(x, xb, offmask3, omb, w, bias, out, ob, N, H, W, s);
-#endif
     const double px = (double)N * H * W;
     // algorithmic bytes reported BOTH ways in DESIGN.md; the profiler record carries the compact
     // figure (4 in + 2 off + 1 mask + 4 out floats per pixel) that this kernel actually needs
     ProfScope prof("dcnv2_shared_c4", s, px * ((4 + 4) * sizeof(act_t) + (2 + 1) * 4.0), px * (2.0 * 4 * 4 * 9 + 36 * 7));
-#ifdef CRFP_LAB
-    if (dcn3_nt_env() == 1) {
-        dcn3_kernel<false, 1><<<dim3((W + 63) / 64, (H + 3) / 4, N), 256, 0, s>>>(x, xb, offmask3, omb, w, bias, out, ob, H, W, nullptr, nullptr, nullptr, 0);
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
     dim3 grid((W + 63) / 64, (H + 4 * DCN3_NT - 1) / (4 * DCN3_NT), N);
-    dcn3_kernel<false, DCN3_NT><<<grid, 256, 0, s>>>(x, xb, offmask3, omb, w, bias, out, ob, H, W, nullptr, nullptr, nullptr, 0);
+    dcn3_kernel<false><<<grid, 256, 0, s>>>(x, xb, offmask3, omb, w, bias, out, ob, H, W, nullptr, nullptr, nullptr, 0);
     CRFP_CHECK_LAUNCH();
     return 0;
 }
@@ -1119,24 +755,10 @@ int launch_dcn3(const float* x, long long xb, const float* offmask3, long long o
 // dcn_3 with its offset / mask conv inside: g2 = the conv's input (one Q4 quad), wom / bom = its narrow-packed weights and bias
 int launch_dcn3_fused(const float* x, long long xb, const float* g2, long long gb, const float* flow, const float* wom, const float* bom,
                       const float* w, const float* bias, float* out, long long ob, int N, int H, int W, hipStream_t s, long long fb) {
-#ifdef CRFP_LAB
-    static const bool r2 = getenv("CRFP_DCN3_R2") && atoi(getenv("CRFP_DCN3_R2"));
-    if (r2) return launch_dcn3_fused_r2(x, xb, g2, gb, flow, wom, bom, w, bias, out, ob, N, H, W, s);
-#endif
     const double px = (double)N * H * W;
     ProfScope prof("dcnv2_shared_c4_fused", s, px * ((4 + 4 + 4) * sizeof(act_t) + 2 * 4.0), px * (2.0 * 4 * 4 * 9 + 36 * 7 + 2.0 * 4 * 3 * 9));
-#ifdef CRFP_LAB
-    if (dcn3_nt_env() != DCN3_NT) {
-        const int nt = dcn3_nt_env();
-        if (nt == 1) dcn3_kernel<true, 1><<<dim3((W + 63) / 64, (H + 3) / 4, N), 256, 0, s>>>(x, xb, g2, gb, w, bias, out, ob, H, W, flow, wom, bom, fb);
-        else if (nt == 2) dcn3_kernel<true, 2><<<dim3((W + 63) / 64, (H + 7) / 8, N), 256, 0, s>>>(x, xb, g2, gb, w, bias, out, ob, H, W, flow, wom, bom, fb);
-        else dcn3_kernel<true, 6><<<dim3((W + 63) / 64, (H + 23) / 24, N), 256, 0, s>>>(x, xb, g2, gb, w, bias, out, ob, H, W, flow, wom, bom, fb);
-        CRFP_CHECK_LAUNCH();
-        return 0;
-    }
-#endif
     dim3 grid((W + 63) / 64, (H + 4 * DCN3_NT - 1) / (4 * DCN3_NT), N);
-    dcn3_kernel<true, DCN3_NT><<<grid, 256, 0, s>>>(x, xb, g2, gb, w, bias, out, ob, H, W, flow, wom, bom, fb);
+    dcn3_kernel<true><<<grid, 256, 0, s>>>(x, xb, g2, gb, w, bias, out, ob, H, W, flow, wom, bom, fb);
     CRFP_CHECK_LAUNCH();
     return 0;
 }

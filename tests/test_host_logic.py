@@ -233,6 +233,12 @@ def test_gaze_rig_masks_match_the_reference_loop(tag):
         assert np.array_equal(past, unpack("past", n)), ("past", n)
 
 
+# what the lab library reads from the environment on top of the product's five switches: exactly these
+LAB_KNOBS = {b"CRFP_CONV_MODE", b"CRFP_DCN_MODE", b"CRFP_SPLIT_WS", b"CRFP_SPLIT_IS", b"CRFP_SPLIT_RPW", b"CRFP_SPLIT_PIPE", b"CRFP_CONV_S3",
+             b"CRFP_DCN_FUSE_V", b"CRFP_DCN_FUSE_NW", b"CRFP_NARROW_CHAIN", b"CRFP_NARROW_SEQ", b"CRFP_STATE_FROM_EPILOGUE", b"CRFP_DF_PS_MIN_TILES",
+             b"CRFP_STAMP_NAME", b"CRFP_STAMP_PTR", b"CRFP_DCN_PROBE", b"CRFP_DCN_FUSE_PROBE", b"CRFP_NARROW_PROBE"}
+
+
 def test_product_library_carries_no_lab_kernels():
     """The experiments that lose to the default conv main loop (pipelined / input-stationary / warp-specialised / bf16x6)
     and the s_memtime stamp code are compiled only into the lab library (`make lab`, -DCRFP_LAB)."""
@@ -247,6 +253,14 @@ def test_product_library_carries_no_lab_kernels():
     for name in (b"conv3x3_split_ks_kernel", b"ksplit_reduce_kernel", b"upsample_q4_kernelILb1EE", b"avgpool2_q4_kernelILb1EE",
                  b"conv3x3_bf16_kernelILi1ELb1EE", b"KsIn"):
         assert name not in blob, name
+    # the closed experiments went the same way (ship or bury): the round-2 dcn_3 sampler, the stencil without an LDS tile, the persistent 4-row
+    # f16x3s conv and the split-by-2 warp are in neither library, and dcn_g8_kernel is the one strict-fp32 instantiation (no template arguments)
+    removed = (b"dcn3_r2_kernel", b"conv3x3_narrow_direct_kernel", b"conv3x3_split8p_kernel", b"flow_warp_p4_dual_split_kernelILi8ELi6ELi2E")
+    lab_so = os.path.join(ROOT, "crfp_amd", "libcrfp_hip_lab.so")
+    for blob_ in [blob] + ([open(lab_so, "rb").read()] if os.path.exists(lab_so) else []):
+        for name in removed:
+            assert name not in blob_, name
+    assert len(set(re.findall(rb"_ZN4crfp13dcn_g8_kernel\w*", blob))) == 1
     assert os.path.getsize(so) < 4 << 20
 
 
@@ -262,8 +276,26 @@ def test_product_library_reads_only_the_documented_switches():
     env_like = {n for n in prod if not n.startswith((b"CRFP_E_", b"CRFP_DSV_", b"CRFP_NS", b"CRFP_ACT_"))}
     assert env_like == documented, sorted(env_like ^ documented)
     lab = names(os.path.join(ROOT, "crfp_amd", "libcrfp_hip_lab.so"))
-    for knob in (b"CRFP_CONV_MODE", b"CRFP_DCN_MODE", b"CRFP_DCN_FUSE_V", b"CRFP_DCN_FUSE_NW", b"CRFP_F32_S8_MAX_WGS", b"CRFP_DCN_VARIANT"):
-        assert knob in lab and knob not in prod, knob
+    assert lab - prod == LAB_KNOBS, sorted((lab - prod) ^ LAB_KNOBS)
+    for knob in (b"CRFP_F32_S8_MAX_WGS", b"CRFP_DCN_VARIANT"):   # closed experiments: in neither library
+        assert knob not in lab and knob not in prod, knob
+
+
+def test_every_lab_knob_has_a_user_and_a_line_in_the_table():
+    """A lab knob stays only while a test compares results under it or a tool sets it, and profiles/README.md lists it: the rule that keeps
+    closed experiments from piling up again."""
+    users = b""
+    for top in ("tests", "tools"):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                path = os.path.join(d, f)
+                if f.endswith((".py", ".sh", ".md")) and not os.path.samefile(path, __file__):
+                    users += open(path, "rb").read() + b"\n"
+    readme = open(os.path.join(ROOT, "profiles", "README.md"), "rb").read()
+    table = readme[readme.index(b"## Surviving lab knobs"):]
+    for knob in sorted(LAB_KNOBS):
+        assert re.search(rb"(?<![A-Za-z0-9_])" + knob + rb"(?![A-Za-z0-9_])", users), knob
+        assert re.search(rb"\| `" + knob + rb"` \|", table), knob
 
 
 def test_regional_engine_tables_and_argument_errors(lib):

@@ -6,7 +6,11 @@
 Every variant runs in its own child process (the library reads its switches once), alternating over --rounds so that box
 drift hits all of them alike.  `lib=<path>` inside a variant selects another build of the C-ABI (CRFP_HIP_LIB); `lab`
 is short for the lab library; `AB_RESIDENT=1` sets CRFP_DSV_INPUTS_RESIDENT in --mode stream.  Prints per variant: wall ms per clip (two-stream schedule), kernel-sum ms (single-stream
-instrumented pass) and the avg us of every launch site whose name contains one of --sites, plus a digest of the output."""
+instrumented pass) and the avg us of every launch site whose name contains one of --sites, plus a digest of the output.
+
+The destructive probes (lab library, results wrong by design, the digest shows it) run the same way, one variant per probe word:
+  python tools/ab_sites.py --sites conv_narrow p0=lab p1=CRFP_NARROW_PROBE=1,lab p4=CRFP_NARROW_PROBE=4,lab      (profiles/r06_narrow_probes.txt)
+  python tools/ab_sites.py --sites dcnv2_g8 p0=lab p1=CRFP_DCN_FUSE_PROBE=1,lab nw4=CRFP_DCN_FUSE_NW=4,lab       (the fused offset head + DCN)"""
 import argparse
 import hashlib
 import json
