@@ -88,6 +88,9 @@ SIGNATURES = {
     "crfp_conv3x3_ex_workspace_bytes": (C.c_size_t, [C.c_int] * 9),
     "crfp_conv3x3_ex_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float] + [C.c_int] * 4 +
                             [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "crfp_conv3x3_ex_backward_workspace_bytes": (C.c_size_t, [C.c_int] * 8),
+    "crfp_conv3x3_ex_backward_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_float] +
+                                     [C.c_int] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_conv3x3_packed_bytes": (C.c_size_t, [C.c_int] * 2),
     "crfp_conv3x3_pack_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_conv3x3_packed_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),

@@ -421,6 +421,47 @@ int crfp_conv3x3_ex_f32(const float* x, int cin, const float* x2, int cin2, cons
     return launch_conv_mfma(a, "conv_mfma:api_ex", s);
 }
 
+// ---- conv3x3_ex backward (conv_backward.hip): the forward's combination rules, every argument error before any HIP call
+static int conv3x3_ex_backward_domain(int n, int cin, int cin2, int cout, int h, int w, int act, float post_scale, int unshuffle_r, int shuffle_r) {
+    if (n < 1 || h < 1 || w < 1) { set_error("conv3x3_ex_backward: bad argument (need n, h, w >= 1)"); return CRFP_E_BADARG; }
+    if (!conv_ex_args_ok(cin, cin2, cout, act, unshuffle_r, shuffle_r, false)) return CRFP_E_UNSUPPORTED;
+    if ((act == CRFP_ACT_RELU || act == CRFP_ACT_LRELU01) && !(post_scale > 0.0f)) {
+        set_error("conv3x3_ex_backward: relu / lrelu take their derivative from the sign of out and need post_scale > 0 (got %g)", (double)post_scale);
+        return CRFP_E_UNSUPPORTED;
+    }
+    if ((act == CRFP_ACT_TANH || act == CRFP_ACT_SIGMOID) && !(post_scale < 0.0f || post_scale > 0.0f)) {   // also NaN
+        set_error("conv3x3_ex_backward: tanh / sigmoid take their derivative from out / post_scale and need post_scale != 0 (got %g)", (double)post_scale);
+        return CRFP_E_UNSUPPORTED;
+    }
+    if (cin > 1024 || cin2 > 1024 || !conv3x3_backward_shape_ok(n, cin + cin2, cout, h, w)) {
+        set_error("conv3x3_ex_backward: up to 1024 input and 1024 output channels, 65535 images, 262140 rows, 2^30 columns and 2^58 tensor elements "
+                  "(got cin %d + %d, cout %d, n %d, h %d, w %d)", cin, cin2, cout, n, h, w);
+        return CRFP_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
+size_t crfp_conv3x3_ex_backward_workspace_bytes(int n, int cin, int cin2, int cout, int h, int w, int unshuffle_r, int shuffle_r) {
+    if (conv3x3_ex_backward_domain(n, cin, cin2, cout, h, w, CRFP_ACT_NONE, 1.0f, unshuffle_r, shuffle_r)) return 0;
+    return conv3x3_backward_workspace_bytes(n, cin + cin2, cout, h, w);
+}
+
+int crfp_conv3x3_ex_backward_f32(const float* x, int cin, const float* x2, int cin2, const float* weight, const float* out,
+                                 const float* grad_out, float* grad_x, float* grad_x2, float* grad_weight, float* grad_bias,
+                                 int n, int cout, int h, int w, int act, float post_scale, int unshuffle_r, int shuffle_r,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!grad_x && !grad_x2 && !grad_weight && !grad_bias) { set_error("conv3x3_ex_backward: all four outputs are null (nothing to do)"); return CRFP_E_BADARG; }
+    if (!grad_out) { set_error("conv3x3_ex_backward: null pointer (grad_out is required)"); return CRFP_E_BADARG; }
+    if (const int rc = conv3x3_ex_backward_domain(n, cin, cin2, cout, h, w, act, post_scale, unshuffle_r, shuffle_r)) return rc;
+    if (act != CRFP_ACT_NONE && !out) { set_error("conv3x3_ex_backward: null pointer (out is required with an activation)"); return CRFP_E_BADARG; }
+    if (grad_x2 && cin2 == 0) { set_error("conv3x3_ex_backward: grad_x2 without a second input (cin2 = 0)"); return CRFP_E_BADARG; }
+    if (grad_weight && (!x || (cin2 > 0 && !x2))) { set_error("conv3x3_ex_backward: null pointer (x and x2 are required for grad_weight)"); return CRFP_E_BADARG; }
+    if ((grad_x || grad_x2) && !weight) { set_error("conv3x3_ex_backward: null pointer (weight is required for grad_x / grad_x2)"); return CRFP_E_BADARG; }
+    if (!workspace || workspace_bytes < conv3x3_backward_workspace_bytes(n, cin + cin2, cout, h, w)) { set_error("conv3x3_ex_backward: workspace too small"); return CRFP_E_WORKSPACE; }
+    return launch_conv3x3_backward(x, cin, x2, cin2, weight, out, grad_out, grad_x, grad_x2, grad_weight, grad_bias, n, cout, h, w, act, post_scale,
+                                   unshuffle_r, shuffle_r, workspace, (hipStream_t)stream);
+}
+
 int crfp_upsample_bilinear_f32(const float* x, float* out, int n, int c, int h, int w, int oh, int ow, float scale_h,
                                float scale_w, float mul, void* stream) {
     if (!x || !out || n < 1 || c < 1 || h < 1 || w < 1 || oh < 1 || ow < 1) { set_error("upsample: bad argument"); return CRFP_E_BADARG; }

@@ -516,6 +516,12 @@ int launch_dcn_backward(const float* x, const float* offset, const float* mask, 
 bool flow_warp_backward_shape_ok(int n, int c, int h, int w);
 int launch_flow_warp_backward(const float* x, const float* flow, const float* go, float* gx, float* gflow, int N, int C, int H, int W,
                               int border, int displaced, hipStream_t s);
+// conv_backward.hip (fp32 build only): the gradients of conv3x3_ex (cin_t = cin + cin2); a null output is not computed
+bool conv3x3_backward_shape_ok(int n, int cin_t, int cout, int h, int w);
+size_t conv3x3_backward_workspace_bytes(int n, int cin_t, int cout, int h, int w);     // 0: outside it
+int launch_conv3x3_backward(const float* x, int cin, const float* x2, int cin2, const float* weight, const float* out, const float* go, float* gx,
+                            float* gx2, float* gw, float* gb, int N, int cout, int H, int W, int act, float post_scale, int unshuffle_r,
+                            int shuffle_r, void* workspace, hipStream_t s);
 #endif
 
 }  // namespace CRFP_NS

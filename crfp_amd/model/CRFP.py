@@ -6,7 +6,10 @@ ResidualBlockNoBN :433, ResidualBlocksWithInputConv :516, FNet :743, CRFP_DSV :1
 checkpoints load with ``strict=True`` and ``main.py:34`` / ``trainer.py:318`` call it unchanged.
 The modules only *hold parameters*; all arithmetic runs in the HIP library: ``CRFP_DSV.forward`` is
 one C-ABI call per clip (crfp_amd.engine.DSVEngine), the smaller modules call per-operator entry
-points.  Inference only (no autograd), CUDA/HIP tensors only.
+points.  CUDA/HIP tensors only.  The engines and the model classes' ``forward`` are inference only; the
+smaller modules built on ``ops.conv3x3`` / ``ops.conv3x3_ex`` / ``ops.dcnv2*`` / ``ops.flow_warp`` (DCN_module,
+ResidualBlockNoBN, ResidualBlocksWithInputConv, PixelShufflePack, PixelUnShufflePack_v2) are differentiable
+through those operators' HIP backward passes (first order, fp32).
 """
 import torch
 import torch.nn as nn

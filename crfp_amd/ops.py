@@ -174,8 +174,9 @@ def dcnv2(x, offset, mask, weight, bias, kernel_size=3, padding=1, dilation=1, d
     """Drop-in for ``dcn_v2.DCNv2.forward`` (reference model/CRFP.py:350), forward and backward.  With grad mode on and at least one of
     the five tensors requiring grad the result carries a ``grad_fn`` whose backward is crfp_dcnv2_backward_f32 (fp32, first order only;
     grad_input is an unordered float atomic sum, the other four gradients are bitwise reproducible); otherwise this is the plain
-    forward call.  ``dcnv2_shared`` and ``flow_warp`` have a backward of their own in the same mould; the other wrappers of this module
-    (``dcnv2_g8_packed``, ``conv3x3*``, ``fovea_head``, the resamplers) are forward-only."""
+    forward call.  ``dcnv2_shared``, ``flow_warp``, ``conv3x3`` and ``conv3x3_ex`` have a backward of their own in the same mould; the
+    other wrappers of this module (``dcnv2_g8_packed``, the ``*_packed`` / ``*_unpacked`` convs, ``convkxk``, ``fovea_head``, the
+    resamplers) are forward-only."""
     x, offset, mask = _dev(x, "input"), _dev(offset, "offset"), _dev(mask, "mask")
     weight, bias = _dev(weight, "weight"), _dev(bias, "bias")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, offset, mask, weight, bias)):
@@ -293,12 +294,20 @@ class _DCNv2SharedFunction(torch.autograd.Function):
         return tuple(grads)
 
 
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
 def conv3x3(x, weight, bias=None, act="none", post_scale=1.0):
-    """3x3 stride-1 pad-1 convolution + bias + activation on the fp32 MFMA path (weights repacked by this call)."""
+    """3x3 stride-1 pad-1 convolution + bias + activation on the fp32 MFMA path (weights repacked by this call), forward and backward.
+    With grad mode on and ``x``, ``weight`` or ``bias`` requiring grad the result carries a ``grad_fn`` whose backward is
+    crfp_conv3x3_ex_backward_f32 (see ``conv3x3_ex``); otherwise this is the plain forward call."""
     x, weight = _dev(x, "x"), _dev(weight, "weight")
     if tuple(weight.shape) != (weight.shape[0], x.shape[1], 3, 3):   # nn.Conv2d's own error class and wording (the reference's callers see a RuntimeError)
         raise RuntimeError(f"conv3x3: weight of size {list(weight.shape)}, expected input{list(x.shape)} to have {weight.shape[1]} channels, "
                            f"but got {x.shape[1]} channels instead")
+    if _needs_grad(x, weight, bias):
+        return _Conv3x3ExFunction.apply(x, None, weight, None if bias is None else _dev(bias, "bias"), None, act, float(post_scale), 0, 0, True)
     with _on(x, weight):
         return conv3x3_packed(x, pack_conv3x3(weight, bias), act, post_scale)
 
@@ -306,7 +315,72 @@ def conv3x3(x, weight, bias=None, act="none", post_scale=1.0):
 def conv3x3_ex(x, weight, bias=None, x2=None, residual=None, act="none", post_scale=1.0, unshuffle=0, shuffle=0, out=None, out_c0=0):
     """crfp_conv3x3_ex_f32: conv3x3(cat([x, x2], 1)) + bias -> activation -> * post_scale (+ residual), with the reference's layout steps
     fused: ``unshuffle=4`` reads x [n, c, 4h, 4w] as pixel_unshuffle(x, 4) (model/CRFP.py:28-42), ``shuffle=r`` stores pixel_shuffle(., r)
-    (:184-193), ``out`` / ``out_c0`` write the result into channels [out_c0, out_c0 + cout) of an existing [n, C, h, w] tensor."""
+    (:184-193), ``out`` / ``out_c0`` write the result into channels [out_c0, out_c0 + cout) of an existing [n, C, h, w] tensor.
+    Forward and backward: with grad mode on and at least one of ``x``, ``x2``, ``weight``, ``bias``, ``residual`` requiring grad the result
+    carries a ``grad_fn`` whose backward is crfp_conv3x3_ex_backward_f32 (fp32 on the exact f32-input MFMA, first order only; all gradients
+    bitwise reproducible; the residual's gradient is grad_out itself).  Under grad ``out`` / ``out_c0`` raise RuntimeError (a store into
+    an existing tensor has no graph node) and a residual combined with an activation raises NotImplementedError (no call site, no
+    backward).  Otherwise this is the plain forward call."""
+    if _needs_grad(x, x2, weight, bias, residual):
+        if out is not None or out_c0:
+            raise RuntimeError("conv3x3_ex: `out` / `out_c0` store into an existing tensor, which has no graph node; call it under "
+                               "torch.no_grad() or without them")
+        if residual is not None and act != "none":
+            raise NotImplementedError(f"conv3x3_ex: no backward for a residual combined with an activation (act={act!r})")
+        x, x2, weight, bias, residual = (t if t is None else _dev(t, k) for t, k in zip((x, x2, weight, bias, residual),
+                                                                                        ("x", "x2", "weight", "bias", "residual")))
+        return _Conv3x3ExFunction.apply(x, x2, weight, bias, residual, act, float(post_scale), int(unshuffle), int(shuffle), False)
+    return _conv3x3_ex_forward(x, weight, bias, x2, residual, act, post_scale, unshuffle, shuffle, out, out_c0)
+
+
+class _Conv3x3ExFunction(torch.autograd.Function):
+    """``conv3x3`` / ``conv3x3_ex`` under autograd: forward = the wrapper's own plain call (``packed``: conv3x3's pack + conv3x3_packed
+    route), backward = crfp_conv3x3_ex_backward_f32 with a NULL pointer for every gradient ``ctx.needs_input_grad`` does not ask for."""
+
+    @staticmethod
+    def forward(ctx, x, x2, weight, bias, residual, act, post_scale, unshuffle, shuffle, packed):
+        if packed:
+            with _on(x, weight):
+                out = conv3x3_packed(x, pack_conv3x3(weight, bias), act, post_scale)
+        else:
+            out = _conv3x3_ex_forward(x, weight, bias, x2, residual, act, post_scale, unshuffle, shuffle, None, 0)
+        ctx.save_for_backward(x, x2, weight, out if act != "none" else None)
+        ctx.cfg = (act, post_scale, unshuffle, int(shuffle) if shuffle and shuffle > 1 else 0)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, x2, weight, out = ctx.saved_tensors
+        act, post_scale, unshuffle, r = ctx.cfg
+        grad_out = _dev(grad_out, "grad_out")
+        n = x.shape[0]
+        cin, h, w = (16 * x.shape[1], x.shape[2] // 4, x.shape[3] // 4) if unshuffle == 4 else tuple(x.shape[1:])
+        cin2 = 0 if x2 is None else x2.shape[1]
+        cout = weight.shape[0]
+        need_x, need_x2, need_w, need_b, need_res = ctx.needs_input_grad[:5]
+        need_x2 = need_x2 and x2 is not None
+        gx = gx2 = gw = gb = None
+        if need_x or need_x2 or need_w or need_b:
+            L = _lib.lib()
+            ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+            with _on(x, weight, grad_out):
+                gx = torch.empty_like(x) if need_x else None
+                gx2 = torch.empty_like(x2) if need_x2 else None
+                gw = torch.empty_like(weight) if need_w else None
+                gb = torch.empty(cout, dtype=torch.float32, device=x.device) if need_b else None
+                nb = L.crfp_conv3x3_ex_backward_workspace_bytes(n, cin, cin2, cout, h, w, unshuffle, r)
+                if nb == 0:
+                    _lib.check(-3, "crfp_conv3x3_ex_backward_workspace_bytes")
+                ws = _ws(nb, x.device)
+                _lib.check(L.crfp_conv3x3_ex_backward_f32(x.data_ptr(), cin, ptr(x2), cin2, weight.data_ptr(), ptr(out), grad_out.data_ptr(),
+                                                          ptr(gx), ptr(gx2), ptr(gw), ptr(gb), n, cout, h, w, ACT[act], post_scale, unshuffle, r,
+                                                          ws.data_ptr(), ws.numel(), _stream()), "crfp_conv3x3_ex_backward_f32")
+        return gx, gx2, gw, gb, (grad_out if need_res else None), None, None, None, None, None
+
+
+def _conv3x3_ex_forward(x, weight, bias, x2, residual, act, post_scale, unshuffle, shuffle, out, out_c0):
+    """crfp_conv3x3_ex_f32 (the plain forward call of ``conv3x3_ex``)."""
     x, weight = _dev(x, "x"), _dev(weight, "weight")
     n = x.shape[0]
     if unshuffle == 4:

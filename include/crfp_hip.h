@@ -29,6 +29,7 @@
  *   crfp_dcnv2_forward_f32    model/CRFP.py:6,318-320,350  third-party dcn_v2.DCNv2.forward
  *   crfp_dcnv2_backward_f32   the same extension's backward (autograd of self.dcn(pre_x, offset, mask), model/CRFP.py:350)
  *   crfp_conv3x3_f32          every nn.Conv2d(k=3,s=1,p=1) on the path (e.g. model/CRFP.py:48-50,303-317)
+ *   crfp_conv3x3_ex_backward_f32  autograd of those convs with their activation, cat and pixel (un)shuffle (ATen convolution_backward)
  *   crfp_upsample_bilinear_f32  nn.Upsample / F.interpolate(align_corners=False) (model/CRFP.py:808-812,1471-1478)
  *   crfp_fnet_*               model/CRFP.py:743-814  FNet.forward, :1483-1508 compute_flow
  *   crfp_dsv_*                model/CRFP.py:1387-1706 CRFP_DSV (ctor weights, forward) and the
@@ -175,6 +176,31 @@ size_t crfp_conv3x3_ex_workspace_bytes(int n, int cin, int cin2, int cout, int h
 int crfp_conv3x3_ex_f32(const float* x, int cin, const float* x2, int cin2, const float* weight, const float* bias, const float* residual,
                         float* out, int n, int cout, int h, int w, int act, float post_scale, int unshuffle_r, int shuffle_r,
                         int out_c0, int out_ctotal, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- conv3x3_ex backward: the gradients of crfp_conv3x3_ex_f32's out = act(conv3x3(cat(x, x2)) + bias) * post_scale (+ residual) for a
+ * given grad_out (out's shape: [n,cout,h,w], or [n, cout/r^2, h r, w r] with shuffle_r = r > 1): grad_x (x's shape: [n,cin,h,w], or
+ * [n, cin/16, 4h, 4w] with unshuffle_r = 4), grad_x2 [n,cin2,h,w], grad_weight [cout, cin + cin2, 3, 3], grad_bias [cout].  The
+ * residual's gradient is grad_out itself, so the call takes no residual; a residual combined with an activation has no call site and
+ * no backward.  `out` is the forward's saved output, in out's own (shuffled) layout: the activation's derivative is taken from it
+ * (relu / lrelu: its sign, which needs post_scale > 0; tanh: 1 - (out/s)^2, sigmoid: (out/s)(1 - out/s), which need post_scale != 0;
+ * otherwise CRFP_E_UNSUPPORTED).  The bias is not an input: its gradient is the sum of grad_out * post_scale * act'.
+ * Operands: out may be NULL for CRFP_ACT_NONE; x and x2 may be NULL when grad_weight is NULL; weight may be NULL when grad_x and
+ * grad_x2 are NULL.  Outputs: a NULL output means "not wanted" and its work is skipped (a NULL grad_x or grad_x2 removes its channels
+ * from the input pass, both NULL the pass itself; no weight pass without grad_weight); all four NULL is CRFP_E_BADARG.  Every element of
+ * a wanted output is written by the call with a plain store, and the workspace needs no initialisation.
+ * Domain: the forward's combination rules (unshuffle_r in {0, 1, 4}, shuffle_r in {0, 1, 2, 4}, ...: CRFP_E_UNSUPPORTED otherwise),
+ * cin + cin2 <= 1024, cout <= 1024, n <= 65535, h <= 262140, w <= 2^30, 2^58 tensor elements; beyond it CRFP_E_UNSUPPORTED and the size
+ * query returns 0.  A missing required pointer or a size < 1 is CRFP_E_BADARG, a missing or short workspace CRFP_E_WORKSPACE; every
+ * argument error is returned before any HIP call.  Asynchronous on `stream`, no host synchronisation.
+ * Numbers: fp32 throughout on the exact f32-input MFMA, one rounding per product (no split-fp16: gradients have no bounded range), so
+ * scaling grad_out by a power of two scales every gradient by it bit for bit.  Determinism: all four gradients are bitwise reproducible
+ * from run to run, whichever subset of them is asked for (no atomics; grad_weight / grad_bias through per-workgroup partial slabs in
+ * the workspace added in a fixed order, their count a function of the shape alone). */
+size_t crfp_conv3x3_ex_backward_workspace_bytes(int n, int cin, int cin2, int cout, int h, int w, int unshuffle_r, int shuffle_r);
+int crfp_conv3x3_ex_backward_f32(const float* x, int cin, const float* x2, int cin2, const float* weight, const float* out,
+                                 const float* grad_out, float* grad_x, float* grad_x2, float* grad_weight, float* grad_bias,
+                                 int n, int cout, int h, int w, int act, float post_scale, int unshuffle_r, int shuffle_r,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same two operators with the weight repack hoisted out of the call (pack once per weight update):
  *   crfp_conv3x3_pack_f32 -> crfp_conv3x3_packed_f32           (any cin / cout)

@@ -327,6 +327,69 @@ int main() {
                 }
         EXPECT(crfp_stub_launches() == l0 + launches);
     }
+    // the conv3x3_ex backward: sizing, every refusal before the first launch, the launches each subset of wanted outputs takes
+    {
+        const size_t need = crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 7, 9, 11, 0, 0);
+        EXPECT(need > 0 && crfp_conv3x3_ex_backward_workspace_bytes(1, 66, 0, 32, 360, 640, 0, 0) > 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(1, 4, 4, 4, 1440, 2560, 0, 0) > 0 && crfp_conv3x3_ex_backward_workspace_bytes(1, 128, 32, 288, 180, 320, 0, 0) > 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(1, 32, 0, 9, 5, 7, 4, 0) > 0 && crfp_conv3x3_ex_backward_workspace_bytes(1, 8, 0, 32, 5, 6, 0, 4) > 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(0, 5, 3, 7, 9, 11, 0, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(2, 0, 3, 7, 9, 11, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 5, -1, 7, 9, 11, 0, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 0, 9, 11, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 7, 0, 11, 0, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 7, 9, -4, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 7, 9, 11, 2, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 7, 9, 11, 0, 3) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 24, 0, 7, 9, 11, 4, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(2, 16, 16, 7, 9, 11, 4, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 7, 9, 11, 0, 2) == 0);   // cout % 4
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 1000, 25, 7, 9, 11, 0, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(2, 5, 3, 1025, 9, 11, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(2, 2147483647, 2147483647, 7, 9, 11, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(70000, 5, 3, 7, 9, 11, 0, 0) == 0 && crfp_conv3x3_ex_backward_workspace_bytes(1, 5, 3, 7, 300000, 1, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(1, 5, 3, 7, 9, (1 << 30) + 1, 0, 0) == 0);
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(65535, 1024, 0, 1024, 262140, 1 << 30, 0, 0) == 0);   // element counts beyond 64-bit indexing
+        EXPECT(crfp_conv3x3_ex_backward_workspace_bytes(8, 64, 64, 64, 4320, 7680, 0, 0) > 0 && crfp_conv3x3_ex_backward_workspace_bytes(1, 1, 0, 1, 262140, 100000, 0, 0) > 0);
+        const long l0 = crfp_stub_launches();
+#define CVB(X, X2, W, OUT, GO, GX, GX2, GW, GB, N, CIN, CIN2, COUT, ACT, S, UR, SR, WS, WSB) \
+    crfp_conv3x3_ex_backward_f32(X, CIN, X2, CIN2, W, OUT, GO, GX, GX2, GW, GB, N, COUT, 9, 11, ACT, S, UR, SR, WS, WSB, nullptr)
+        EXPECT(CVB(p16, p16, p16, p16, p16, nullptr, nullptr, nullptr, nullptr, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "nothing to do") != nullptr);
+        EXPECT(CVB(p16, p16, p16, p16, nullptr, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);
+        EXPECT(std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(CVB(p16, p16, p16, nullptr, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);     // out with an activation
+        EXPECT(CVB(nullptr, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);     // x for grad_weight
+        EXPECT(CVB(p16, nullptr, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);     // x2 for grad_weight
+        EXPECT(CVB(p16, p16, nullptr, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);     // weight for grad_x
+        EXPECT(CVB(p16, nullptr, p16, p16, p16, p16, p16, p16, p16, 2, 8, 0, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);     // grad_x2 without x2
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 0, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_BADARG);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 0, 3, 7, 2, 0.5f, 0, 0, p16, need) == CRFP_E_UNSUPPORTED);    // the forward's rules
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 5, 0.5f, 0, 0, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "activation") != nullptr);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 2, 0, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 8, 3, 0.5f, 0, 2, p16, need) == CRFP_E_UNSUPPORTED);    // tanh with a shuffle store
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 1, 0.0f, 0, 0, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "post_scale > 0") != nullptr);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, -1.0f, 0, 0, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 3, 0.0f, 0, 0, p16, need) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "post_scale != 0") != nullptr);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 1025, 0, 1.0f, 0, 0, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 70000, 5, 3, 7, 0, 1.0f, 0, 0, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(std::strstr(crfp_last_error_string(), "65535 images") != nullptr && std::strstr(crfp_last_error_string(), "2^58") != nullptr);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need - 1) == CRFP_E_WORKSPACE);
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, nullptr, need) == CRFP_E_WORKSPACE);
+        EXPECT(crfp_stub_launches() == l0);
+        // gz always; weight transpose + input pass for grad_x / grad_x2; weight pass, bias pass and the slab sum as asked for
+        EXPECT(CVB(p16, p16, p16, p16, p16, p16, p16, p16, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == 0 && crfp_stub_launches() == l0 + 6);
+        EXPECT(CVB(nullptr, nullptr, p16, nullptr, p16, p16, nullptr, nullptr, nullptr, 2, 5, 3, 7, 0, 0.0f, 0, 0, p16, need) == 0 && crfp_stub_launches() == l0 + 9);
+        EXPECT(CVB(nullptr, nullptr, p16, p16, p16, nullptr, p16, nullptr, nullptr, 2, 5, 3, 7, 4, -2.0f, 0, 0, p16, need) == 0 && crfp_stub_launches() == l0 + 12);
+        EXPECT(CVB(p16, p16, nullptr, p16, p16, nullptr, nullptr, p16, nullptr, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == 0 && crfp_stub_launches() == l0 + 15);
+        EXPECT(CVB(nullptr, nullptr, nullptr, p16, p16, nullptr, nullptr, nullptr, p16, 2, 5, 3, 7, 2, 0.5f, 0, 0, p16, need) == 0 && crfp_stub_launches() == l0 + 18);
+#undef CVB
+        for (const auto& g : {std::initializer_list<int>{1, 32, 34, 32, 360, 640, 0, 0}, {1, 4, 4, 4, 1440, 2560, 0, 0}, {3, 128, 32, 288, 1, 1, 0, 0},
+                              {2, 32, 0, 9, 5, 300, 4, 0}, {1, 8, 0, 32, 5, 6, 0, 4}, {1, 16, 0, 12, 7, 10, 0, 2}, {1, 1000, 24, 1024, 3, 70, 0, 0}}) {
+            const int* v = g.begin();
+            const size_t ws = crfp_conv3x3_ex_backward_workspace_bytes(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+            EXPECT(ws > 0 && crfp_conv3x3_ex_backward_f32(p16, v[1], p16, v[2], p16, p16, p16, p16, v[2] ? p16 : nullptr, p16, p16, v[0], v[3], v[4], v[5],
+                                                          1, 1.0f, v[6], v[7], p16, ws, nullptr) == 0);
+        }
+        EXPECT(crfp_stub_launches() == l0 + 18 + 7 * 6);
+    }
     // the DCNv2 backward: sizing, every refusal before the first launch, the launches each subset of wanted outputs takes
     {
         const size_t need = crfp_dcnv2_backward_workspace_bytes(2, 8, 6, 9, 11, 3, 2);
