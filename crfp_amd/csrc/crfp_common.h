@@ -59,6 +59,9 @@ struct ProfScope {
 };
 bool prof_enabled();
 bool precision_env_strict(int family);   // CRFP_PRECISION=f32 in the environment (lab library: or the round-1 knob of family 0 = conv, 1 = DCN)
+// clip calls run a frame's state-independent work in groups of frames (engine.hip, prework_group); lab library: crfp_lab_prework_groups(0) keeps one
+// frame per launch.  Here, and not in the engine, because the lab library's bf16 engine is the product's object: both builds ask this one.
+bool prework_groups();
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // diagnostic builds (tools/stamp_*.py): the s_memtime stamp buffer CRFP_STAMP_PTR when CRFP_STAMP_NAME names this launch site, else null
 static inline long long* lab_stamps(const char* site) {   // (static: the lab library links lab and product objects)
@@ -80,6 +83,7 @@ using crfp::set_error;
 using crfp::ProfScope;
 using crfp::prof_enabled;
 using crfp::precision_env_strict;
+using crfp::prework_groups;
 using crfp::align_up;
 using crfp::lab_stamps;
 

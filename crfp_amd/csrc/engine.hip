@@ -236,7 +236,8 @@ static const Model& model_for(int y_only, bool strict = false, int wiring = W_DS
 }
 
 // ------------------------------------------------------------------ workspace arena
-struct Buf { std::string name; size_t off; int N, nq, H, W, kind, pad; size_t bytes, guard; bool f32; };  // kind 0 = Q4, 1 = NHW2 (always float)
+struct Buf { std::string name; size_t off; int N, nq, H, W, kind, pad; size_t bytes, guard; bool f32; int fslots = 0; };  // kind 0 = Q4, 1 = NHW2 (always float)
+// fslots > 0 (grouped layout): the N items are [clip][fslots frame slots] (crfp_dsv_debug_fetch picks a frame's item)
 // a workspace tensor: byte offset + elements (of the tensor's own type) between two batch items
 struct Ten {
     size_t off = 0;
@@ -258,7 +259,7 @@ struct Arena {
         const size_t guard = pad ? align_up((size_t)(W + 2) * 16, 256) : 0;
         const size_t off = cur + guard;
         cur += guard + align_up(elems * esz, 256);
-        bufs.push_back({name, off, N, nq, H, W, kind, pad, elems * esz, guard, kind != 0 || f32});
+        bufs.push_back({name, off, N, nq, H, W, kind, pad, elems * esz, guard, kind != 0 || f32, 0});
         Ten t;
         t.off = off;
         t.bs = (long long)per;
@@ -282,6 +283,23 @@ struct Q4 {
 // grow with t (BASELINE config 2-5 shapes are all flat; a 100-frame clip takes 13 chunks of 8).
 constexpr int kFlatFrames = 32, kChunkFrames = 8;
 
+// Frames per launch of a clip's state-independent per-frame work (Runner::frame_pre: mask gate, fovea blend, encoder_hr, the upsample conv,
+// the flow up-samplings; W_CRA: the fovea encoder).  None of it depends on the recurrent state, and a clip call holds all its frames, so G
+// consecutive frames of the B clips go into ONE launch per kernel as items (clip, frame) -- where the items have one stride:
+//   B == 1: a clip of up to kGroupFrames frames is one group; a longer one goes in groups of kLongGroupFrames, because two groups' slots are in
+//           flight there and the workspace of a long clip stays bounded (3 GiB at 180 x 320 fp32 whatever t: tests/test_gpu_round4.py);
+//   B  > 1: the whole clips (item k = clip k / t, frame k % t of the contiguous [B, t, ...] tensors) while they are at most kGroupFrames items,
+//           else one frame per launch as before: a lock-step batch has its B items per launch already, and whole clips of 4 x 7 frames in
+//           front of frame 0 measured 0.4 % slower than that.
+// t == 1 (one frame per call) has nothing to group.  The cap: these kernels lose their launch floor by four items per launch,
+// every frame of a group costs a slot of the frame-level buffer sets, and a group may not straddle a chunk of the clip-level
+// stores, whose slots it reads.
+constexpr int kGroupFrames = 8, kLongGroupFrames = 2, kMaxSlots = kGroupFrames;
+static_assert(kChunkFrames % kGroupFrames == 0 && kChunkFrames % kLongGroupFrames == 0 && 2 * kLongGroupFrames <= kMaxSlots, "a pre-work group reads one chunk of x_lr / flow_lr");
+constexpr int prework_group(int B, int t) {
+    return t == 1 ? 1 : B == 1 ? (t <= kGroupFrames ? t : kLongGroupFrames) : ((long long)B * t <= kGroupFrames ? t : 1);
+}
+
 struct Layout {
     Arena A;
     int B, t, h, w;
@@ -294,21 +312,32 @@ struct Layout {
     // FNet
     Ten fa0, fa1, fp1, fb0, fb1, fp2, fc0, fc1, fp3, fd0, fd1, fu1, fe0, fe1, fu2, ff0, ff1, fu3, fg0, fg1;
     // frame-level
-    Ten xin8[2], eh[2], x_hr[2], prop0[2], prop_a, prop_b, flow2[2], flow8[2], prev2, prev2w, prevhrw, carryw, fa, fb, offfeat[3], offmask,
+    Ten xin8[2], eh[2], x_hr[kMaxSlots], prop0[kMaxSlots], prop_a, prop_b, flow2[kMaxSlots], flow8[kMaxSlots], prev2, prev2w, prevhrw, carryw, fa, fb, offfeat[3], offmask,
         aligned, y0, y1, up, poff, g0, g1, g2, om3, al3, z0, z1, feat, fg2, sc_prop, sc_cw, sc_al, sc_up, sc_al3;
     // CRFP_DSV_CRA: slice1's output, the 2x chain's two temporaries, the three fovea levels per buffer set, a level's features and their fused twin
-    Ten c_s1, c_a, c_b, c_lv[2][3], c_y, c_f;
+    Ten c_s1, c_a, c_b, c_lv[kMaxSlots][3], c_y, c_f;
     bool cra;
     int pq;   // quads of the features a level passes on: 6 (CRFP_DSV: 24 + 8 carried beside the level) or 8 (CRFP_simple / CRFP)
     // mask gate of each buffer set: 4 flag bytes per 64 x 16 tile of the 8x map and clip (launch_mask_gate); gate_b = bytes per clip
-    Ten gate[2];
+    Ten gate[kMaxSlots];
     long long gate_b;
+    // Frame slots of the state-independent per-frame tensors (x_hr, prop0, flow2, flow8, gate, W_CRA: c_lv).  G == 1: two sets of B items,
+    // indexed by frame parity.  Grouped (G > 1): every tensor is ONE buffer of [B][slots] items -- a slot per frame of a group, two groups in
+    // flight for a clip longer than one -- so Ten::bs (clip to clip) is slots items and item_bs() is what a group's launch steps by.  xin8 /
+    // enc_hr0 (and W_CRA's c_s1, c_a, c_b) are temporaries of those launches: one group's items, contiguous.
+    int G, slots;
+    bool grouped;
+    int slot_of(int i) const { return grouped ? i % slots : i & 1; }
+    long long item_bs(const Ten& tn) const { return grouped ? tn.bs / slots : tn.bs; }
     int h1, w1, h2, w2, h3, w3;
     int fnet_cap;   // pairs one FNet pass can hold
 
     Layout(int B_, int t_, int h_, int w_, int wiring = W_DSV) : B(B_), t(t_), h(h_), w(w_), cra(wiring == W_CRA), pq(wiring >= W_SIMPLE ? 8 : 6) {
         flat = (long long)B * t <= kFlatFrames;
         TC = flat ? t : kChunkFrames;
+        G = prework_group(B, t);
+        grouped = G > 1;
+        slots = !grouped ? 2 : (t <= G ? t : 2 * G);
         // pairs one FNet pass holds: all of a flat job's (the B - 1 straddling ones included); one per sequence for the one-frame-per-call layout
         const int nb = t == 1 ? B : (flat ? B * t - 1 : TC);
         fnet_cap = nb;
@@ -345,18 +374,30 @@ struct Layout {
         fu3 = A.take("fnet.u3", nb, 16, 8 * h3, 8 * w3);
         fg0 = A.take("fnet.g0", nb, 8, 8 * h3, 8 * w3);
         fg1 = A.take("fnet.g1", nb, 1, 8 * h3, 8 * w3, 0, 0, true);
-        // state-independent per-frame work (fovea blend, encoder_hr, upsample conv, flow upsampling) is
-        // produced one or two frames ahead on a side stream -> two buffer sets, indexed by frame parity
-        for (int p = 0; p < 2; ++p) {
-            xin8[p] = A.take(p ? "xin8.1" : "xin8", B, 2, H8, W8);
-            eh[p] = A.take(p ? "enc_hr0.1" : "enc_hr0", B, 1, H8, W8);
-            x_hr[p] = A.take(p ? "x_hr.1" : "x_hr", B, 1, H8, W8);
-            prop0[p] = A.take(p ? "prop0.1" : "prop0", B, pq, H2, W2);
-            flow2[p] = A.take(p ? "flow2.1" : "flow2", B, 0, H2, W2, 1);
-            flow8[p] = A.take(p ? "flow8.1" : "flow8", B, 0, H8, W8, 1);
-            const int gtiles = ((W8 + 63) / 64) * ((H8 + 15) / 16);
-            gate_b = ((long long)gtiles * 4 + 7) / 8 * 8;
-            gate[p] = A.take(p ? "gate.1" : "gate", B, 0, 1, (int)(gate_b / 8), 1);
+        // state-independent per-frame work (fovea blend, encoder_hr, upsample conv, flow upsampling) is produced ahead of the recurrent
+        // chain on a side stream
+        const int gtiles = ((W8 + 63) / 64) * ((H8 + 15) / 16);
+        gate_b = ((long long)gtiles * 4 + 7) / 8 * 8;
+        if (!grouped) {   // one or two frames ahead -> two buffer sets, indexed by frame parity
+            for (int p = 0; p < 2; ++p) {
+                xin8[p] = A.take(p ? "xin8.1" : "xin8", B, 2, H8, W8);
+                eh[p] = A.take(p ? "enc_hr0.1" : "enc_hr0", B, 1, H8, W8);
+                x_hr[p] = A.take(p ? "x_hr.1" : "x_hr", B, 1, H8, W8);
+                prop0[p] = A.take(p ? "prop0.1" : "prop0", B, pq, H2, W2);
+                flow2[p] = A.take(p ? "flow2.1" : "flow2", B, 0, H2, W2, 1);
+                flow8[p] = A.take(p ? "flow8.1" : "flow8", B, 0, H8, W8, 1);
+                gate[p] = A.take(p ? "gate.1" : "gate", B, 0, 1, (int)(gate_b / 8), 1);
+            }
+        } else {          // a group ahead -> a slot per frame
+            xin8[0] = xin8[1] = A.take("xin8", B * G, 2, H8, W8);
+            A.bufs.back().fslots = G;
+            eh[0] = eh[1] = A.take("enc_hr0", B * G, 1, H8, W8);
+            A.bufs.back().fslots = G;
+            slot_set(x_hr, "x_hr", 1, H8, W8, 0);
+            slot_set(prop0, "prop0", pq, H2, W2, 0);
+            slot_set(flow2, "flow2", 0, H2, W2, 1);
+            slot_set(flow8, "flow8", 0, H8, W8, 1);
+            slot_set(gate, "gate", 0, 1, (int)(gate_b / 8), 1);
         }
         prop_a = A.take("prop_a", B, pq, H2, W2);
         prop_b = A.take("prop_b", B, pq, H2, W2);
@@ -383,11 +424,16 @@ struct Layout {
         feat = A.take("feat", B, 1, H8, W8);
         if (cra) {
             static const char* lvn[2][3] = {{"cra.lv0", "cra.lv1", "cra.lv2"}, {"cra.lv0.1", "cra.lv1.1", "cra.lv2.1"}};
-            c_s1 = A.take("cra.s1", B, 1, H8, W8);
-            c_a = A.take("cra.a", B, 4, H2, W2);
-            c_b = A.take("cra.b", B, 4, H2, W2);
-            for (int p = 0; p < 2; ++p)
+            c_s1 = A.take("cra.s1", B * G, 1, H8, W8);
+            c_a = A.take("cra.a", B * G, 4, H2, W2);
+            c_b = A.take("cra.b", B * G, 4, H2, W2);
+            for (int p = 0; p < 2 && !grouped; ++p)
                 for (int k = 0; k < 3; ++k) c_lv[p][k] = A.take(lvn[p][k], B, 4, H2, W2);
+            for (int k = 0; k < 3 && grouped; ++k) {
+                Ten lv[kMaxSlots];
+                slot_set(lv, lvn[0][k], 4, H2, W2, 0);
+                for (int sl = 0; sl < slots; ++sl) c_lv[sl][k] = lv[sl];
+            }
             c_y = A.take("cra.y", B, 8, H2, W2);
             c_f = A.take("cra.fused", B, 8, H2, W2);
         }
@@ -399,6 +445,17 @@ struct Layout {
             sc_al = A.take("fg.aligned", 1, 8, H2, W2);
             sc_up = A.take("fg.up", 1, 1, H8, W8);
             sc_al3 = A.take("fg.aligned3", 1, 1, H8, W8);
+        }
+    }
+    // grouped layout: one buffer of [B][slots] items; dst[sl] = slot sl of clip 0, clip stride = slots items
+    void slot_set(Ten* dst, const char* name, int nq, int H, int W, int kind) {
+        const Ten b = A.take(name, B * slots, nq, H, W, kind);
+        Buf& buf = A.bufs.back();
+        buf.fslots = slots;
+        const size_t item_bytes = buf.bytes / (size_t)buf.N;
+        for (int sl = 0; sl < slots; ++sl) {
+            dst[sl].off = b.off + (size_t)sl * item_bytes;
+            dst[sl].bs = b.bs * slots;
         }
     }
     size_t bytes() const { return A.cur; }
@@ -557,7 +614,7 @@ struct Runner {
         for (size_t i = 0; i < srcs.size(); ++i) { a.src[i].p = srcs[i].p; a.src[i].bstride = srcs[i].bs; a.src[i].pad = 0; }
         a.src[0].pad = src0_pad;
         a.dst_pad = dst_pad;
-        a.N = L.B; a.H = H; a.W = W;
+        a.N = nitems ? nitems : L.B; a.H = H; a.W = W;
         a.dst = const_cast<float*>(dst.p); a.dst_bstride = dst.bs;
         a.resid = resid.p; a.resid_bstride = resid.bs;
         a.flow = flow.p; a.flow_bstride = flow.bs;
@@ -567,7 +624,7 @@ struct Runner {
         a.bpk = packed + it.off_b;
         a.ovf = ovf(); a.ovf_div = ovf_div; a.ovf_add = ovf_add;
         a.dst2 = const_cast<float*>(dst2.p); a.dst2_bstride = dst2.bs;
-        if (gate_par >= 0 && mask_gate_enabled()) { a.gate = gate_ptr(gate_par); a.gate_bstride = L.gate_b; a.gate_h = gate_h; }
+        if (gate_par >= 0 && mask_gate_enabled()) { a.gate = gate_ptr(gate_par); a.gate_bstride = gate_bs(gate_par); a.gate_h = gate_h; }
         rc = launch_narrow(a, it.name, s);
     }
     // two stencils in one pass: item idA (its output has no other reader) feeding item idB (conv_narrow.hip, launch_narrow_pair)
@@ -627,6 +684,11 @@ struct Runner {
         return on;
     }
     const uint8_t* gate_ptr(int par) const { return reinterpret_cast<const uint8_t*>(ws + L.gate[par]); }
+    // A launch of frame_pre over a group of frames: its item count (0: one frame, an item per clip) -- what narrow() launches instead of L.B
+    // items, stepping through the frame slots (Layout::item_bs) instead of from clip to clip
+    int nitems = 0;
+    long long step(const Ten& tn) const { return nitems ? L.item_bs(tn) : tn.bs; }
+    long long gate_bs(int par) const { return step(L.gate[par]) * (long long)sizeof(float); }   // bytes between two items' flags (one frame: L.gate_b)
 
     // fp32 build: n NCHW LR frames -> Q4 quads in slot s0.. of lr_q4 (see the Model); the bf16 build reads the fp32 frames directly
     // check_div: the frames are the call's own LR input, frame f of clip f / check_div (0: one sequence): values an fp16 operand cannot
@@ -778,47 +840,72 @@ struct Runner {
         f.x_lr = adv(F(L.x_lr), L.slot(0, i) * xq); f.x_b = L.TC * xq;
         return f;
     }
+    // The same for a group launch whose item 0 is frame i of clip 0: every stride is one FRAME.  B == 1: items are frames i, i + 1, ... (within
+    // one chunk of the clip-level stores); B > 1: i == 0 and item k is frame k % t of clip k / t -- the API tensors' own order, and the flat
+    // stores' (TC == t).
+    FrameIO group_io(int i, const float* lrs, const float* fvs, const uint8_t* mks, float* out, int y_only) const {
+        FrameIO f = frame_io(i, lrs, fvs, mks, out, y_only);
+        const long long hr_px = 64LL * L.h * L.w;
+        f.lr_b = 3LL * L.h * L.w; f.fv_b = 3 * hr_px; f.mk_b = hr_px; f.out_b = (long long)(y_only ? 1 : 3) * hr_px;
+        f.flow_b = (long long)L.h * L.w * 4; f.x_b = 8LL * L.h * L.w * 4;
+        return f;
+    }
 
-    // state-independent part of a frame (reference model/CRFP.py:1538-1547,1560,1565-1566): buffer set `par`
+    // state-independent part of a frame (reference model/CRFP.py:1538-1547,1560,1565-1566): buffer set (frame slot) `par`
     // before_ups: event this stream waits for right before the upsample conv, the only consumer of x_lr here (clip
     // schedule: the fovea blend and encoder_hr of frame 0 then run beside encoder_lr instead of behind it)
     // parts: 1 = fovea blend + encoder_hr + upsample conv (need no flow), 2 = the two flow up-samplings (need FNet)
-    void frame_pre(int par, bool first, const FrameIO& io, hipEvent_t before_ups = nullptr, int parts = 3) {
-        const int h = L.h, w = L.w, H2 = 2 * h, W2 = 2 * w, H8 = 8 * h, W8 = 8 * w, B = L.B;
+    // items > 0: ONE launch per kernel over `items` (clip, frame) items (prework_group) -- io: group_io() of item 0's frame, par: its slot; item
+    // k writes the k-th slot from there and raises the status word of ITS clip (B == 1: the call's one word; whole clips: clip k / t)
+    void frame_pre(int par, bool first, const FrameIO& io, hipEvent_t before_ups = nullptr, int parts = 3, int items = 0) {
+        const int h = L.h, w = L.w, H2 = 2 * h, W2 = 2 * w, H8 = 8 * h, W8 = 8 * w, N = items ? items : L.B;
         const long long P8q = (long long)H8 * W8 * 4;
+        struct Restore { Runner& r; int n, d, a; ~Restore() { r.nitems = n; r.ovf_div = d; r.ovf_add = a; } } restore{*this, nitems, ovf_div, ovf_add};
+        nitems = items;
+        if (items) { ovf_div = L.B == 1 ? 0 : L.t; ovf_add = 0; }
         if (parts & 1) {
-            const Ten& xin = L.xin8[par];
+            // the launches' temporaries: a frame's items sit at its place in its group (one clip), so a clip leaves every frame of its last group
+            // behind for crfp_dsv_debug_fetch whatever the steps were
+            const long long t0 = L.grouped && L.B == 1 ? par % L.G : 0;
+            Ten xin = L.xin8[par & 1], eh = L.eh[par & 1];
+            xin.off += (size_t)(t0 * xin.bs) * sizeof(act_t);
+            eh.off += (size_t)(t0 * eh.bs) * sizeof(act_t);
+            const Ten& xhr = L.x_hr[par];
             const bool gated = mask_gate_enabled();
-            if (gated) RUN(launch_mask_gate(io.mk, io.mk_b, const_cast<uint8_t*>(gate_ptr(par)), L.gate_b, B, H8, W8, s));
+            if (gated) RUN(launch_mask_gate(io.mk, io.mk_b, const_cast<uint8_t*>(gate_ptr(par)), gate_bs(par), N, H8, W8, s));
             // conv_tttf works on the tiles that hold mask pixels and reads x_hr one pixel into their neighbours: encoder_hr's second conv runs on
             // that ring of tiles too, its first conv on two rings, the frame stack on three -- no launch reads a tile nobody wrote.
             // CRFP_DSV_CRA: slice1's output also feeds the three 2x levels, whose reach is wider: only conv_lv3 is gated there.
             const int gp = gated && !M.cra ? par : -1;
-            RUN(launch_hr_prep(io.lr, io.fv, io.mk, F(xin), h, w, s, B, io.lr_b, io.fv_b, io.mk_b, xin.bs, gp >= 0 ? gate_ptr(par) : nullptr, L.gate_b));
+            RUN(launch_hr_prep(io.lr, io.fv, io.mk, F(xin), h, w, s, N, io.lr_b, io.fv_b, io.mk_b, xin.bs, gp >= 0 ? gate_ptr(par) : nullptr, gate_bs(par)));
             // CRFP_DSV_CRA: slice1's output feeds conv_lv3 (-> x_hr, what conv_tttf blends in) and the three 2x levels
-            const Ten& s1 = M.cra ? L.c_s1 : L.x_hr[par];
-            narrow(IT_EH0, H8, W8, {{F(xin), xin.bs}, {adv(F(xin), P8q), xin.bs}}, {F(L.eh[par]), L.eh[par].bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 2);
-            narrow(IT_EH1, H8, W8, {{F(L.eh[par]), L.eh[par].bs}}, {F(s1), s1.bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 1);
+            const Ten& s1 = M.cra ? L.c_s1 : xhr;
+            const long long s1b = M.cra ? s1.bs : step(xhr);
+            narrow(IT_EH0, H8, W8, {{F(xin), xin.bs}, {adv(F(xin), P8q), xin.bs}}, {F(eh), eh.bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 2);
+            narrow(IT_EH1, H8, W8, {{F(eh), eh.bs}}, {F(s1), s1b}, NB(), NB(), nullptr, 0, 0, 0, NB(), gp, 1);
             if (M.cra) {
-                narrow(IT_C_LV3, H8, W8, {{F(s1), s1.bs}}, {F(L.x_hr[par]), L.x_hr[par].bs}, NB(), NB(), nullptr, 0, 0, 0, NB(), par, 1);
+                narrow(IT_C_LV3, H8, W8, {{F(s1), s1b}}, {F(xhr), step(xhr)}, NB(), NB(), nullptr, 0, 0, 0, NB(), par, 1);
                 const Q4 a = q(L.c_a, 4, H2, W2), b = q(L.c_b, 4, H2, W2);
-                auto lv = [&](int k) { return q(L.c_lv[par][k], 4, H2, W2); };
-                mfma(IT_C_S2A, B, H2, W2, {{F(s1), s1.bs, 0}}, {{a.p, a.bs(), 0, 4}});
-                mfma_q(IT_C_S2B, B, a, b);
-                mfma_q(IT_C_LV2, B, b, lv(2));
-                mfma_q(IT_C_S3A, B, b, a);
-                mfma_q(IT_C_S3B, B, a, b);
-                mfma_q(IT_C_LV1, B, b, lv(1));
-                mfma_q(IT_C_S4A, B, b, a);
-                mfma_q(IT_C_S4B, B, a, b);
-                mfma_q(IT_C_LV0, B, b, lv(0));
+                auto lv = [&](int id, int k) {   // b -> level k's slot
+                    const Ten& tn = L.c_lv[par][k];
+                    mfma(id, N, H2, W2, {{b.p, b.bs()}}, {{F(tn), step(tn), 0, 4}});
+                };
+                mfma(IT_C_S2A, N, H2, W2, {{F(s1), s1b, 0}}, {{a.p, a.bs(), 0, 4}});
+                mfma_q(IT_C_S2B, N, a, b);
+                lv(IT_C_LV2, 2);
+                mfma_q(IT_C_S3A, N, b, a);
+                mfma_q(IT_C_S3B, N, a, b);
+                lv(IT_C_LV1, 1);
+                mfma_q(IT_C_S4A, N, b, a);
+                mfma_q(IT_C_S4B, N, a, b);
+                lv(IT_C_LV0, 0);
             }
             if (before_ups && !rc && hipStreamWaitEvent(s, before_ups, 0) != hipSuccess) { set_error("dsv: hipStreamWaitEvent failed"); rc = 1; }
-            mfma(IT_UPS, B, h, w, {{io.x_lr, io.x_b}}, {{F(L.prop0[par]), L.prop0[par].bs, 0, L.pq}}, H2, W2);
+            mfma(IT_UPS, N, h, w, {{io.x_lr, io.x_b}}, {{F(L.prop0[par]), step(L.prop0[par]), 0, L.pq}}, H2, W2);
         }
         if (!first && (parts & 2)) {
-            RUN(crfp::launch_upflow(io.flow_lr, io.flow_b, F(L.flow2[par]), L.flow2[par].bs, B, h, w, 2, s));
-            RUN(crfp::launch_upflow(io.flow_lr, io.flow_b, F(L.flow8[par]), L.flow8[par].bs, B, h, w, 8, s));
+            RUN(crfp::launch_upflow(io.flow_lr, io.flow_b, F(L.flow2[par]), step(L.flow2[par]), N, h, w, 2, s));
+            RUN(crfp::launch_upflow(io.flow_lr, io.flow_b, F(L.flow8[par]), step(L.flow8[par]), N, h, w, 8, s));
         }
     }
 
@@ -836,6 +923,7 @@ struct Runner {
         const long long bs6 = L.pq * P2q;   // batch stride of the features a level passes on (prop*): 6 quads, CRFP_simple / CRFP 8
         const bool abl = M.abl(), dense = M.dense();
         float* prop = F(L.prop0[par]);
+        long long pbs = L.prop0[par].bs;   // level 0 reads the frame slot (grouped layout: a clip is `slots` items on), the later levels prop_a / prop_b
         float* prop_next = F(L.prop_a);
         float* prop_other = F(L.prop_b);
         float* carry = F(L.carry);
@@ -865,8 +953,8 @@ struct Runner {
                 float* f = F(L.offfeat[l]);
                 const bool s3 = M.use_s3;   // f holds the SRC_S3 image (same size) instead of fp32 Q4
                 // dcn_block.0's inputs: [features | carried] | warped previous state | flow; CRFP_simple / CRFP: features (32) | warped | flow
-                const std::vector<SrcBind> db0 = abl ? std::vector<SrcBind>{{prop, bs6}, {F(L.prev2w), bs8}, {flow2, f2b}, {nullptr, 0}}
-                                                     : std::vector<SrcBind>{{prop, bs6}, {cw, bs6}, {F(L.prev2w), bs8}, {flow2, f2b}, {nullptr, 0}};
+                const std::vector<SrcBind> db0 = abl ? std::vector<SrcBind>{{prop, pbs}, {F(L.prev2w), bs8}, {flow2, f2b}, {nullptr, 0}}
+                                                     : std::vector<SrcBind>{{prop, pbs}, {cw, bs6}, {F(L.prev2w), bs8}, {flow2, f2b}, {nullptr, 0}};
                 if (pair_convs(PAIR_DCN_BLOCK)) {   // dcn_block.0 -> .2 in one launch, the 32-channel tensor between them stays in LDS
                     if (l == 0 && s3) mfma_pair(it_lvl(l, L_DB0), it_lvl(l, L_DB1), "conv_mfma_pair:dcn.block0_block2", B, H2, W2, db0, {}, nullptr, 0, f, bs8);
                     else mfma_pair(it_lvl(l, L_DB0), it_lvl(l, L_DB1), "conv_mfma_pair:dcn.block0_block2", B, H2, W2, db0, {{l == 0 ? f : F(L.fb), bs8, 0, 8}});
@@ -905,18 +993,19 @@ struct Runner {
                     RUN(launch_scale_q4(F(L.aligned), 0, F(L.sc_al), 8, H2, W2, F(L.fg2), nullptr, s));
                     mfma(it_lvl(l, L_RB0), 1, H2, W2, {{F(L.sc_prop), 0}, {F(L.sc_cw), 0}, {F(L.sc_al), 0}}, {{F(L.y0), 0, 0, 8}});
                 } else if (abl) {   // cat(cur, aligned) (:1034); CRFP: + the warped previous state (:1311)
-                    std::vector<SrcBind> rb = {{prop, bs6}, {F(L.aligned), bs8}};
+                    std::vector<SrcBind> rb = {{prop, pbs}, {F(L.aligned), bs8}};
                     if (dense) rb.push_back({F(L.prev2w), bs8});
                     mfma(it_lvl(l, L_RB0), B, H2, W2, rb, {{F(L.y0), bs8, 0, 8}});
                 } else
-                    mfma(it_lvl(l, L_RB0), B, H2, W2, {{prop, bs6}, {cw, bs6}, {F(L.aligned), bs8}}, {{F(L.y0), bs8, 0, 8}});
+                    mfma(it_lvl(l, L_RB0), B, H2, W2, {{prop, pbs}, {cw, bs6}, {F(L.aligned), bs8}}, {{F(L.y0), bs8, 0, 8}});
                 res_block(l, prop_next, adv(carry, 2 * l * P2qp), H2, W2, par, io.mk, io.mk_b);
                 prop = prop_next;
+                pbs = bs6;
                 std::swap(prop_next, prop_other);
                 offprev = f;
             }
             // the two 32 -> 64 pixel-shuffle convs behind level 2 are independent: one launch (round 6; fp32 build)
-            mfma_dual(IT_UPP, {{prop, bs6}}, {{F(L.up), L.up.bs, 0, 1}}, IT_POFF, {{offprev, bs8}}, {{F(L.poff), L.poff.bs, 0, 1}}, B, H2, W2, H8, W8,
+            mfma_dual(IT_UPP, {{prop, pbs}}, {{F(L.up), L.up.bs, 0, 1}}, IT_POFF, {{offprev, bs8}}, {{F(L.poff), L.poff.bs, 0, 1}}, B, H2, W2, H8, W8,
                       "conv_mfma:upsample_post_ps4+dcn3.preoffset_ps4");
             const NB fl8(flow8, f8b);
             if (chain_mask() & 1)   // dcn_block.0 -> .2 -> conv_fuse in one launch (round 6)
@@ -948,12 +1037,13 @@ struct Runner {
             if (!r3_chain) narrow(IT_R3_0, H8, W8, r3_srcs, nb(L.z0));
         } else {
             for (int l = 0; l < 3; ++l) {
-                mfma(it_lvl(l, L_RB0F), B, H2, W2, {{prop, bs6}, {nullptr, 0}}, {{F(L.y0), bs8, 0, 8}});
+                mfma(it_lvl(l, L_RB0F), B, H2, W2, {{prop, pbs}, {nullptr, 0}}, {{F(L.y0), bs8, 0, 8}});
                 res_block(l, prop_next, adv(carry, 2 * l * P2qp), H2, W2, par, io.mk, io.mk_b);
                 prop = prop_next;
+                pbs = bs6;
                 std::swap(prop_next, prop_other);
             }
-            mfma(IT_UPP, B, H2, W2, {{prop, bs6}}, {{F(L.up), L.up.bs, 0, 1}}, H8, W8);
+            mfma(IT_UPP, B, H2, W2, {{prop, pbs}}, {{F(L.up), L.up.bs, 0, 1}}, H8, W8);
             r3_srcs = {nb(L.up)};
             if (!r3_chain) narrow(IT_R3_0F, H8, W8, r3_srcs, nb(L.z0));
         }
@@ -1054,7 +1144,23 @@ static int forward_batch_impl(int wiring, const void* packed, int flags, const f
     if (!lrs || !fvs || !mks || !out) { set_error("dsv_forward_clip: null tensor"); return CRFP_E_BADARG; }
     Runner R{model_for(y_only, flags & CRFP_DSV_STRICT_F32, wiring), (const float*)packed, (char*)workspace, L, (hipStream_t)stream};
     R.strict = (flags & CRFP_DSV_STRICT_F32) ? 1 : 0;
-    const int TC = L.TC;
+    const int TC = L.TC, G = L.G;
+    // the lab library keeps the per-frame order reachable (crfp_lab_prework_groups(0), runtime.hip: one frame per launch into slots 0 / 1, as before round 25)
+    const bool groups = L.grouped && prework_groups();
+    auto slot = [&](int i) { return groups ? L.slot_of(i) : i & 1; };
+    auto fio = [&](int i) { return R.frame_io(i, lrs, fvs, mks, out, y_only); };
+    // parts 1 / 2 of frames [i0, i1) of every clip (groups only).  One launch per kernel where the items have one stride: one clip's frames,
+    // or whole clips; part 2 has no item for a frame 0, so a lock-step batch keeps its flow up-samplings per frame (B items each).
+    auto pre1 = [&](int i0, int i1, hipEvent_t before_ups) {
+        if (i1 <= i0) return;
+        if (n == 1 && i1 - i0 == 1) R.frame_pre(slot(i0), false, fio(i0), before_ups, 1);
+        else R.frame_pre(slot(i0), false, R.group_io(i0, lrs, fvs, mks, out, y_only), before_ups, 1, n * (i1 - i0));
+    };
+    auto pre2 = [&](int i0, int i1) {
+        if (i0 < 1) i0 = 1;
+        if (n == 1 && i1 - i0 > 1) R.frame_pre(slot(i0), false, R.group_io(i0, lrs, fvs, mks, out, y_only), nullptr, 2, i1 - i0);
+        else for (int i = i0; i < i1; ++i) R.frame_pre(slot(i), false, fio(i), nullptr, 2);
+    };
     SideStream* ssp = side_stream_enabled() && !prof_enabled() && !(flags & CRFP_DSV_SINGLE_STREAM) ? side_stream() : nullptr;
     hipStream_t main_s = (hipStream_t)stream;
     if (!ssp) {
@@ -1067,14 +1173,19 @@ static int forward_batch_impl(int wiring, const void* packed, int flags, const f
                 R.clip_stage(lq, i, i1, 2);
                 R.clip_stage(lq, i, i1, 1);
             }
-            const Runner::FrameIO io = R.frame_io(i, lrs, fvs, mks, out, y_only);
-            R.frame_pre(i & 1, i == 0, io);
-            R.frame(i & 1, i == 0, io);
+            const Runner::FrameIO io = fio(i);
+            if (!groups) R.frame_pre(i & 1, i == 0, io);
+            else if (i % G == 0) {   // a group's pre-work in front of its first frame
+                const int i1 = i + G < t ? i + G : t;
+                pre1(i, i1, nullptr);
+                pre2(i, i1);
+            }
+            R.frame(slot(i), i == 0, io);
         }
         return R.rc;
     }
-    // two-stream schedule: the side stream runs FNet and the state-independent part of every frame up to two
-    // frames ahead of the recurrent chain on the caller's stream
+    // two-stream schedule: the side stream runs FNet and the state-independent part of every frame ahead of the recurrent chain on the
+    // caller's stream
     SideStream& ss = *ssp;
     SideJoin J{ss, main_s, 0, "dsv_forward_clip", nullptr};
     hipEvent_t ev_start = ss.event(0), ev_xlr = ss.event(1);
@@ -1088,6 +1199,66 @@ static int forward_batch_impl(int wiring, const void* packed, int flags, const f
     J.forked = true;
     R.clip_stage(lq, 0, TC < t ? TC : t, 1);   // encoder_lr of the first chunk (flat: of every frame) on the caller's stream, beside frame 0's fovea blend
     if (hipEventRecord(ev_xlr, main_s) != hipSuccess) return J.fail("record");
+    if (groups) {
+        // Per group g: events 2 + kEv g ... = "ready" of its steps, the last one "done" (the recurrent part of its last frame: its slots are free).
+        // The clip start stays as tight as the per-frame order's: frame 0 waits for its own pre-work only (one clip: one item; whole clips: the
+        // clips' one group), frame 1 for FNet, the group's flow up-samplings and its own part 1, and the group's remaining frames go as one
+        // launch per kernel beside frame 1's recurrent part.  W_CRA, whose fovea encoder makes a frame's part 1 a quarter of its recurrent
+        // part: two frames at a time, each step beside the frame in front of it -- five frames in one step made frame 2 wait.
+        // Every later group is one launch per kernel, a whole group ahead of its frames.
+        constexpr int kSteps = kGroupFrames / 2 + 2, kEv = kSteps + 1;
+        for (int i0 = 0; i0 < t && !R.rc; i0 += G) {
+            const int g = i0 / G, i1 = i0 + G < t ? i0 + G : t;
+            auto ready = [&](int k) { return ss.event(2 + kEv * g + k); };
+            hipEvent_t done = ss.event(2 + kEv * g + kSteps);
+            if (!ss.ok) return J.fail("hipEventCreate");
+            // step k: part 1 of frames [p[k - 1], p[k]) (k == 0: from i0), step 1 also FNet and the flow up-samplings; frame f[k] is the first to
+            // wait for step k
+            int p[kSteps] = {i1}, f[kSteps] = {i0}, np = 1;
+            R.s = ss.s;
+            // the slots were last read by group g - 2's frames
+            if (g >= 2 && hipStreamWaitEvent(ss.s, ss.event(2 + kEv * (g - 2) + kSteps), 0) != hipSuccess) return J.fail("wait");
+            if (g == 0) {
+                f[1] = 1;
+                if (n == 1) {   // (grouped: t >= 2)
+                    p[0] = 1; p[1] = 2; np = 2;
+                    const int step = wiring == W_CRA ? 2 : i1;
+                    for (int lo = 2; lo < i1; lo += step, ++np) { f[np] = lo; p[np] = lo + step < i1 ? lo + step : i1; }
+                } else { p[1] = i1; np = 2; }
+                pre1(0, p[0], ev_xlr);
+            } else {
+                // later chunks of a long clip: both clip-level stages on the side stream, in front of the chunk's first group (the stores'
+                // previous contents were last read by this stream's own earlier pre-work)
+                if (i0 % TC == 0) R.clip_stage(lq, i0, i0 + TC < t ? i0 + TC : t, 3);
+                pre1(i0, i1, nullptr);
+                pre2(i0, i1);
+            }
+            if (hipEventRecord(ready(0), ss.s) != hipSuccess) return J.fail("record");
+            for (int i = i0, ph = 0; i < i1 && !R.rc; ++i) {
+                if (i == i0 && hipStreamWaitEvent(main_s, ready(0), 0) != hipSuccess) return J.fail("wait");
+                while (ph + 1 < np && i == f[ph + 1]) {
+                    ++ph;
+                    R.s = ss.s;
+                    if (ph == 1) {
+                        // FNet (all pairs, 0.7 ms) goes BEHIND frame 0's pre-work: frame 0 needs no flow, and with FNet first the caller's
+                        // stream sat idle for FNet + pre(0) at the start of every clip.  It runs beside frame 0's recurrent part.
+                        R.clip_stage(lq, 0, TC < t ? TC : t, 2);
+                        pre2(0, i1);
+                    }
+                    pre1(p[ph - 1], p[ph], nullptr);
+                    if (hipEventRecord(ready(ph), ss.s) != hipSuccess) return J.fail("record");
+                    if (hipStreamWaitEvent(main_s, ready(ph), 0) != hipSuccess) return J.fail("wait");
+                }
+                R.s = main_s;
+                R.frame(slot(i), i == 0, fio(i));
+            }
+            R.s = main_s;
+            if (hipEventRecord(done, main_s) != hipSuccess) return J.fail("record");
+        }
+        if (R.rc) J.join();   // a launch failed mid-clip: the last wait may not have been enqueued
+        return R.rc;
+    }
+    // one frame per launch (a lock-step batch whose items have no single stride; one-frame clips): pre-work up to two frames ahead
     for (int i = 0; i < t && !R.rc; ++i) {
         hipEvent_t pre_done = ss.event(2 + 2 * i), main_done = ss.event(3 + 2 * i);
         if (!ss.ok) return J.fail("hipEventCreate");
@@ -1101,7 +1272,7 @@ static int forward_batch_impl(int wiring, const void* packed, int flags, const f
         // previous contents were last read by this stream's own earlier pre-work)
         if (i > 0 && i % TC == 0) R.clip_stage(lq, i, i + TC < t ? i + TC : t, 3);
         if (i >= 2 && hipStreamWaitEvent(ss.s, ss.event(3 + 2 * (i - 2)), 0) != hipSuccess) return J.fail("wait");
-        const Runner::FrameIO io = R.frame_io(i, lrs, fvs, mks, out, y_only);
+        const Runner::FrameIO io = fio(i);
         R.frame_pre(i & 1, i == 0, io, i == 0 ? ev_xlr : nullptr);
         if (hipEventRecord(pre_done, ss.s) != hipSuccess) return J.fail("record");
         // main: recurrent part of frame i
@@ -1360,10 +1531,20 @@ int CRFP_API(crfp_dsv_debug_fetch)(const char* name, int t, int h, int w, const 
                          int* h_out, int* w_out, void* stream) {
     if (!name || !workspace) return CRFP_E_BADARG;
     Layout L(1, t, h, w);
+    // the frame-slot tensors keep their two fetch names: "x" = the last frame of even index, "x.1" = the last one of odd index -- the parity sets
+    // of the one-frame-per-launch layout, which still has them as two buffers
+    std::string base = name;
+    const bool odd = base.size() > 2 && base.compare(base.size() - 2, 2, ".1") == 0;
+    if (odd) base.resize(base.size() - 2);
     for (auto& b : L.A.bufs)
-        if (b.name == name) {
+        if (b.name == name || (b.fslots && b.name == base)) {
             const float* p = reinterpret_cast<const float*>((const char*)workspace + b.off);
             int bN = b.N;
+            if (b.fslots) {
+                const int f = ((t - 1) & 1) == (odd ? 1 : 0) ? t - 1 : t - 2;   // (grouped: t >= 2); temporaries hold the frame at its place in its group
+                p = reinterpret_cast<const float*>((const char*)workspace + b.off + (size_t)(b.fslots == L.slots ? L.slot_of(f) : f % L.G) * (b.bytes / (size_t)b.N));
+                bN = 1;
+            }
             // the flow of frame i lives in slot i of the store (slot 0 belongs to frame 0, which has none): present frames 1 .. t - 1
             if (b.name == "flow_lr" && t > 1 && L.flat) { p += (size_t)b.H * b.W * 4; bN = t - 1; }
             if (c_out) *c_out = b.kind == 0 ? b.nq * 4 : 2;

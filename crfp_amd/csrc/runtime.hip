@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -32,6 +33,12 @@ static std::vector<ProfEntry> g_entries;
 static std::vector<hipEvent_t> g_free_events;
 
 bool prof_enabled() { return g_prof_on; }
+#ifdef CRFP_LAB
+static std::atomic<int> g_prework_groups{1};
+bool prework_groups() { return g_prework_groups.load() != 0; }
+#else
+bool prework_groups() { return true; }
+#endif
 
 static hipEvent_t get_event() {
     if (!g_free_events.empty()) {
@@ -66,6 +73,13 @@ using namespace crfp;
 extern "C" {
 
 int crfp_version(void) { return CRFP_VERSION; }
+
+#ifdef CRFP_LAB
+// Lab library only (no product symbol, no environment name): on = 0 makes the clip calls of this process run a frame's state-independent work one
+// frame per launch into two buffer sets, the order before round 25, so that tests can hold the two orders equal; returns the previous setting.
+// Not a header entry point: call it while no clip call is in flight.
+int crfp_lab_prework_groups(int on) { return g_prework_groups.exchange(on != 0); }
+#endif
 
 const char* crfp_last_error_string(void) { return g_err; }
 

@@ -377,6 +377,14 @@ size_t crfp_dsv_packed_weight_bytes(int y_only);
 /* repack all parameters into the MFMA / stencil layouts (device -> device, async on stream) */
 int crfp_dsv_pack_weights(const float* const* params, int y_only, void* packed, size_t packed_bytes, void* stream);
 
+/* Workspace of a t-frame clip.  A clip call runs the state-independent work of its frames (mask gate, fovea blend, encoder_hr, the upsample
+ * conv, the flow up-samplings) as one launch per kernel over a GROUP of frames -- the frames of a clip of up to 8 frames (pairs of frames of a longer one), or the whole clips of a
+ * batch while n * t <= 8 -- so the workspace holds one frame slot (x8 frame stack, encoder_hr's two outputs, the upsample conv's output, both
+ * up-sampled flows, the gate flags) per frame of a group instead of two per call: t slots for t <= 8; a longer clip goes in groups of two frames
+ * with two groups in flight, 4 slots of the tensors the recurrent part reads plus 2 of the launches' temporaries, so that its workspace stays bounded.  One slot (from the layout): 289 MB at h x w = 180 x 320 and 651 MB at
+ * 270 x 480 with fp32 storage, 160 MB and 361 MB with bf16 storage; 39 % of it (bf16: 45 %) are the tensors the recurrent part reads.  A 7-frame 180 x 320
+ * fp32 clip therefore takes 1.45 GB more than with two slots (bf16: 0.80 GB), a clip of more than 8 frames 0.22 GB more (bf16: 0.14 GB), whatever
+ * its length.  The one-frame-per-call workspace (t = 1, the streaming entry points) keeps its two sets and its size. */
 size_t crfp_dsv_workspace_bytes(int t, int h, int w);
 
 /* `flags` of the two forward entry points (the round-1 ABI passed y_only in the same slot: 0 / 1 keep their meaning). */

@@ -850,6 +850,19 @@ int main() {
                     EXPECT(crfp_dsv_forward_batch(pk, 0, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_dsv_batch_workspace_bytes(n, t, h, w) - 1, stream) != 0);
                 }
             }
+            // pre-work groups (engine.hip, prework_group): (n, t) around every rule boundary -- two frames, one full group, a tail group, a third
+            // group on the first one's slots, a chunked 40-frame clip; whole clips of a small batch, a batch just past the item cap, a chunked batch
+            const int grouped[][2] = {{1, 2}, {1, 8}, {1, 16}, {1, 17}, {1, 40}, {2, 3}, {2, 4}, {2, 5}, {2, 17}};
+            for (const auto& c : grouped) {
+                const int n = c[0], t = c[1];
+                EXPECT(crfp_dsv_forward_batch(pk, 0, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_dsv_batch_workspace_bytes(n, t, h, w), stream) == 0);
+                EXPECT(crfp_dsv_forward_batch(pk, CRFP_DSV_SINGLE_STREAM, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_dsv_batch_workspace_bytes(n, t, h, w), stream) == 0);
+                EXPECT(crfp_dsv_forward_batch_bf16(pk, 0, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_dsv_batch_workspace_bytes_bf16(n, t, h, w), stream) == 0);
+                EXPECT(crfp_cra_forward_batch(pk, 0, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_cra_batch_workspace_bytes(n, t, h, w), stream) == 0);
+                EXPECT(crfp_cra_forward_batch(pk, CRFP_DSV_SINGLE_STREAM, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_cra_batch_workspace_bytes(n, t, h, w), stream) == 0);
+                EXPECT(crfp_dense_forward_batch_bf16(pk, 0, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_dense_batch_workspace_bytes_bf16(n, t, h, w), stream) == 0);
+                EXPECT(crfp_dsv_forward_batch(pk, 0, lrs, fvs, mks, out, n, t, h, w, wsp, crfp_dsv_batch_workspace_bytes(n, t, h, w) - 1, stream) != 0);
+            }
             // one frame per call: first call, then steady calls with and without the resident-inputs promise, with a regional mask, in a batch
             const size_t sws = crfp_dsv_batch_workspace_bytes(1, 1, h, w);
             EXPECT(crfp_dsv_stream_frame(pk, 0, lrs, nullptr, fvs, mks, nullptr, out, 1, h, w, wsp, sws, stream) == 0);
