@@ -169,16 +169,17 @@ class Family:
 _PACK = frozenset(("param_numel", "packed_weight_bytes", "pack_weights"))
 _CLIP = _PACK | {"batch_workspace_bytes", "batch_status_offset", "forward_batch"}   # clip / lock-step batch forward
 _STREAM = _CLIP | {"stream_batch"}                                                  # + one frame per call
-_DSV = _STREAM | {"fnet_forward", "debug_fetch"}
+_FETCH = _STREAM | {"debug_fetch"}                                                  # + the workspace fetch of the wiring's own Layout
+_DSV = _FETCH | {"fnet_forward"}
 _NUMEL = frozenset(("param_numel",))   # shapes do not depend on the storage type
 # dsv: CRFP_DSV.  cra: CRFP_DSV_CRA, its own parameter table, clip forward and the one-frame-per-call form (MRCF_simple_v18_cra).  simple /
 # dense: the CRFP_simple / CRFP wirings -- CRFP_DSV's parameter names with their own shapes -- clip forward and the one-frame-per-call form
 # (MRCF_simple_v13 / v15).  rt: the regional benchmark wiring, fp32 storage only, with a forward call, a workspace query and a debug fetch of its own.
 FAMILIES = {
     "dsv": Family("crfp_dsv_", "dsv", NUM_PARAMS, "CRFP_DSV", _DSV, _DSV - _NUMEL),
-    "cra": Family("crfp_cra_", "cra", CRA_NUM_PARAMS, "CRFP_DSV_CRA", _STREAM, _STREAM - _NUMEL),
-    "simple": Family("crfp_simple_", "dsv", NUM_PARAMS, "CRFP_simple", _STREAM, _STREAM - _NUMEL),
-    "dense": Family("crfp_dense_", "dsv", NUM_PARAMS, "CRFP", _STREAM, _STREAM - _NUMEL),
+    "cra": Family("crfp_cra_", "cra", CRA_NUM_PARAMS, "CRFP_DSV_CRA", _FETCH, _FETCH - _NUMEL),
+    "simple": Family("crfp_simple_", "dsv", NUM_PARAMS, "CRFP_simple", _FETCH, _FETCH - _NUMEL),
+    "dense": Family("crfp_dense_", "dsv", NUM_PARAMS, "CRFP", _FETCH, _FETCH - _NUMEL),
     "rt": Family("crfp_rt_", "rt", RT_NUM_PARAMS, "MRCF_simple_v18", _PACK | {"workspace_bytes", "forward_clip", "debug_fetch"}, frozenset()),
 }
 

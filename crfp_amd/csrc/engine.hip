@@ -1438,6 +1438,41 @@ static int stream_batch_impl(int wiring, const void* packed, int flags, const fl
     return R.rc;
 }
 
+// crfp_<x>_debug_fetch: a named buffer of the wiring's one-clip Layout as NCHW (diagnosis and tests; no kernel of its own)
+static int debug_fetch_impl(int wiring, const char* name, int t, int h, int w, const void* workspace, float* out_nchw, int* c_out,
+                            int* h_out, int* w_out, void* stream) {
+    if (!name || !workspace) return CRFP_E_BADARG;
+    if (!dims_ok(1, t, h, w)) { set_error("debug_fetch: need t>=1, h,w>=8 (got %d,%d,%d)", t, h, w); return CRFP_E_BADARG; }
+    Layout L(1, t, h, w, wiring);
+    // the frame-slot tensors keep their two fetch names: "x" = the last frame of even index, "x.1" = the last one of odd index -- the parity sets
+    // of the one-frame-per-launch layout, which still has them as two buffers
+    std::string base = name;
+    const bool odd = base.size() > 2 && base.compare(base.size() - 2, 2, ".1") == 0;
+    if (odd) base.resize(base.size() - 2);
+    for (auto& b : L.A.bufs)
+        if (b.name == name || (b.fslots && b.name == base)) {
+            const float* p = reinterpret_cast<const float*>((const char*)workspace + b.off);
+            int bN = b.N;
+            if (b.fslots) {
+                const int f = ((t - 1) & 1) == (odd ? 1 : 0) ? t - 1 : t - 2;   // (grouped: t >= 2); temporaries hold the frame at its place in its group
+                p = reinterpret_cast<const float*>((const char*)workspace + b.off + (size_t)(b.fslots == L.slots ? L.slot_of(f) : f % L.G) * (b.bytes / (size_t)b.N));
+                bN = 1;
+            }
+            // the flow of frame i lives in slot i of the store (slot 0 belongs to frame 0, which has none): present frames 1 .. t - 1
+            if (b.name == "flow_lr" && t > 1 && L.flat) { p += (size_t)b.H * b.W * 4; bN = t - 1; }
+            if (c_out) *c_out = b.kind == 0 ? b.nq * 4 : 2;
+            if (h_out) *h_out = b.H;
+            if (w_out) *w_out = b.W;
+            if (!out_nchw) return bN;
+            if (b.kind == 0 && b.f32) return crfp::launch_q4_to_nchw(p, out_nchw, bN, b.nq * 4, b.H, b.W, b.pad, (hipStream_t)stream);
+            if (b.kind == 0) return launch_q4_to_nchw(p, out_nchw, bN, b.nq * 4, b.H, b.W, b.pad, (hipStream_t)stream);
+            return hipMemcpyAsync(out_nchw, p, (size_t)bN * b.H * b.W * 2 * sizeof(float), hipMemcpyDeviceToDevice,
+                                  (hipStream_t)stream) == hipSuccess ? 0 : 1;
+        }
+    set_error("debug_fetch: unknown buffer '%s'", name);
+    return CRFP_E_BADARG;
+}
+
 // ------------------------------------------------------------------ the C ABI of a wiring
 // One set of entry points per wiring, all over the same implementations: crfp_<x>_packed_weight_bytes / _pack_weights (params: the wiring's
 // parameter table, crfp_<x>_param_name / _param_numel), _batch_workspace_bytes / _batch_status_offset, _forward_batch and _stream_batch.
@@ -1474,6 +1509,10 @@ static int stream_batch_impl(int wiring, const void* packed, int flags, const fl
                                           const uint8_t* fg, float* out, int first, int n, int h, int w, void* workspace, size_t workspace_bytes, \
                                           void* stream) { \
         return stream_batch_impl(WIRING, packed, flags, lr, lr_prev, fv, mk, fg, out, first, n, h, w, workspace, workspace_bytes, stream); \
+    } \
+    int CRFP_API(crfp_##X##_debug_fetch)(const char* name, int t, int h, int w, const void* workspace, float* out_nchw, int* c_out, int* h_out, \
+                                         int* w_out, void* stream) { \
+        return debug_fetch_impl(WIRING, name, t, h, w, workspace, out_nchw, c_out, h_out, w_out, stream); \
     }
 
 extern "C" {
@@ -1525,39 +1564,6 @@ int CRFP_API(crfp_fnet_forward)(const void* packed, const float* cur, const floa
         if (!R.rc) R.rc = crfp::launch_q4_to_nchw(R.F(L.flow_lr), flow + (long long)p0 * 2 * h * w, cnt, 2, h, w, 0, (hipStream_t)stream);
     }
     return R.rc;
-}
-
-int CRFP_API(crfp_dsv_debug_fetch)(const char* name, int t, int h, int w, const void* workspace, float* out_nchw, int* c_out,
-                         int* h_out, int* w_out, void* stream) {
-    if (!name || !workspace) return CRFP_E_BADARG;
-    Layout L(1, t, h, w);
-    // the frame-slot tensors keep their two fetch names: "x" = the last frame of even index, "x.1" = the last one of odd index -- the parity sets
-    // of the one-frame-per-launch layout, which still has them as two buffers
-    std::string base = name;
-    const bool odd = base.size() > 2 && base.compare(base.size() - 2, 2, ".1") == 0;
-    if (odd) base.resize(base.size() - 2);
-    for (auto& b : L.A.bufs)
-        if (b.name == name || (b.fslots && b.name == base)) {
-            const float* p = reinterpret_cast<const float*>((const char*)workspace + b.off);
-            int bN = b.N;
-            if (b.fslots) {
-                const int f = ((t - 1) & 1) == (odd ? 1 : 0) ? t - 1 : t - 2;   // (grouped: t >= 2); temporaries hold the frame at its place in its group
-                p = reinterpret_cast<const float*>((const char*)workspace + b.off + (size_t)(b.fslots == L.slots ? L.slot_of(f) : f % L.G) * (b.bytes / (size_t)b.N));
-                bN = 1;
-            }
-            // the flow of frame i lives in slot i of the store (slot 0 belongs to frame 0, which has none): present frames 1 .. t - 1
-            if (b.name == "flow_lr" && t > 1 && L.flat) { p += (size_t)b.H * b.W * 4; bN = t - 1; }
-            if (c_out) *c_out = b.kind == 0 ? b.nq * 4 : 2;
-            if (h_out) *h_out = b.H;
-            if (w_out) *w_out = b.W;
-            if (!out_nchw) return bN;
-            if (b.kind == 0 && b.f32) return crfp::launch_q4_to_nchw(p, out_nchw, bN, b.nq * 4, b.H, b.W, b.pad, (hipStream_t)stream);
-            if (b.kind == 0) return launch_q4_to_nchw(p, out_nchw, bN, b.nq * 4, b.H, b.W, b.pad, (hipStream_t)stream);
-            return hipMemcpyAsync(out_nchw, p, (size_t)bN * b.H * b.W * 2 * sizeof(float), hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream) == hipSuccess ? 0 : 1;
-        }
-    set_error("debug_fetch: unknown buffer '%s'", name);
-    return CRFP_E_BADARG;
 }
 
 }  // extern "C"

@@ -114,7 +114,7 @@ _REFUSALS = {
     "stream_batch": "a clip handle; the one-frame-per-call schedules are DSVEngine's and, for CRFP_DSV_CRA / CRFP_simple / CRFP, "
                     "CRAStreamEngine's / SimpleStreamEngine's / DenseStreamEngine's",
     "fnet_forward": "use the model's flow network modules ({model}.compute_flow)",
-    "debug_fetch": "debug_fetch reads the CRFP_DSV workspace layout (DSVEngine) or the regional one (RuntimeEngine)",
+    "debug_fetch": "debug_fetch reads a clip engine's workspace layout (each wiring its own) or the regional one (RuntimeEngine)",
 }
 
 
@@ -391,7 +391,8 @@ class DSVEngine(_Handle):
         return flow
 
     def debug_fetch(self, name, t, h, w):
-        """Copy a named workspace intermediate of the last clip forward to an NCHW tensor (tests only)."""
+        """Copy a named workspace intermediate of the last clip forward to an NCHW tensor (tests only).  The subclasses read their own
+        wiring's layout (crfp_cra_ / crfp_simple_ / crfp_dense_debug_fetch)."""
         fetch = self._call("debug_fetch")
         ws = self._workspace(t, h, w)
         c, hh, ww = C.c_int(), C.c_int(), C.c_int()

@@ -566,6 +566,12 @@ int crfp_fnet_forward_bf16(const void* packed, const float* cur, const float* pr
                            void* workspace, size_t workspace_bytes, void* stream);
 int crfp_dsv_debug_fetch_bf16(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
                               int* c_out, int* h_out, int* w_out, void* stream);
+int crfp_cra_debug_fetch_bf16(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
+                              int* c_out, int* h_out, int* w_out, void* stream);
+int crfp_simple_debug_fetch_bf16(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
+                                 int* c_out, int* h_out, int* w_out, void* stream);
+int crfp_dense_debug_fetch_bf16(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
+                                int* c_out, int* h_out, int* w_out, void* stream);
 
 /* FNet alone (compute_flow): pairs cur[n,3,h,w], prev[n,3,h,w] -> flow[n,2,h,w] (NCHW). */
 int crfp_fnet_forward(const void* packed, const float* cur, const float* prev, float* flow, int n, int h, int w,
@@ -589,9 +595,19 @@ int crfp_prof_report(crfp_prof_record* out, int cap);
 int crfp_debug_side_tables(void);
 
 /* debug: copy a named intermediate of the last crfp_dsv_* call out of the workspace (Q4 layout
- * converted to NCHW).  Used by the parity tests to bisect; returns CRFP_E_BADARG for unknown names. */
+ * converted to NCHW).  Used by the parity tests to bisect; returns CRFP_E_BADARG for unknown names.
+ * crfp_cra_ / crfp_simple_ / crfp_dense_debug_fetch read the one-clip workspace of THEIR wiring's forward_batch (each wiring has a
+ * layout of its own: 32-channel prop* for simple / dense, the cra.* buffers for cra) under the same contract: out_nchw == NULL returns
+ * the item count and fills c / h / w_out.  Frame-slot tensors ("x_hr", "prop0", "flow2", "flow8", "cra.lv0..2", ...) answer to "x" (the
+ * last frame of even index) and "x.1" (the last one of odd index). */
 int crfp_dsv_debug_fetch(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
                          int* c_out, int* h_out, int* w_out, void* stream);
+int crfp_cra_debug_fetch(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
+                         int* c_out, int* h_out, int* w_out, void* stream);
+int crfp_simple_debug_fetch(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
+                            int* c_out, int* h_out, int* w_out, void* stream);
+int crfp_dense_debug_fetch(const char* name, int t, int h, int w, const void* workspace, float* out_nchw,
+                           int* c_out, int* h_out, int* w_out, void* stream);
 
 /* ---- Test hook: ONE launch of the engines' own 3x3 conv kernels on caller-supplied tensors (tests/test_gpu_conv_probe.py).  Not a product
  * entry: every call builds the plan as the engines do (same source table, same packers, same launchers), converts the API tensors to the

@@ -381,11 +381,186 @@ def crfp_dsv_forward(P, lrs: Tensor, fvs: Tensor, mks: Tensor, cfg: Optional[DSV
     return torch.stack(outs, dim=1)
 
 
+# ----------------------------------------------------------------------------- the other three wirings of the one-call engine
+class WiringConfig(DSVConfig):
+    """DSVConfig for every wiring the clip engine runs: "dsv" (CRFP_DSV), "cra" (CRFP_DSV_CRA, model/CRFP.py:2314-2664), "simple"
+    (CRFP_simple, :816-1099) and "dense" (CRFP, :1101-1385), hr_dcn and offset_prop on.  simple / dense carry nothing beside a level:
+    all mid_channels travel from level to level (``upsample`` keeps mid_channels, :875-877)."""
+
+    def __init__(self, wiring: str = "dsv", mid_channels: int = 32, y_only: bool = False):
+        if wiring not in ("dsv", "cra", "simple", "dense"):
+            raise ValueError(wiring)
+        super().__init__(mid_channels, y_only)
+        self.wiring = wiring
+        self.cra = wiring == "cra"
+        self.abl = wiring in ("simple", "dense")
+        self.dense = wiring == "dense"
+        if self.abl:
+            self.carry, self.prop = 0, mid_channels
+
+
+def lte_hr_ps(P, pre: str, x6: Tensor):
+    """LTE_simple_hr_ps.forward (model/LTE.py:119-166) on cat(blended fovea, x8 LR): (lv0, lv1, lv2 at 2x resolution with 4 * last channels,
+    lv3 at 8x with last channels).  slice2 opens with PixelUnshuffle(4) (:131; the one-hot grouped conv of :5-19 is F.pixel_unshuffle).
+    Taps: one per buffer the engine keeps -- ``cra.s1`` (slice1), ``cra.lv0..3``, and the six slice convs ``cra.s2a .. cra.s4b`` (the engine
+    ping-pongs them through ``cra.a`` / ``cra.b``)."""
+    s1 = tap("cra.s1", R(lrelu(conv(P, pre + "slice1.2", tap("enc_hr0", R(lrelu(conv(P, pre + "slice1.0", x6))))))))
+    lv3 = tap("cra.lv3", R(lrelu(conv(P, pre + "conv_lv3", s1))))                                    # :158
+    x = F.pixel_unshuffle(s1, 4)
+    x = tap("cra.s2a", R(lrelu(conv(P, pre + "slice2.1", x))))
+    x = tap("cra.s2b", R(lrelu(conv(P, pre + "slice2.3", x))))
+    lv2 = tap("cra.lv2", R(lrelu(conv(P, pre + "conv_lv2", x))))                                     # :160
+    x = tap("cra.s3a", R(lrelu(conv(P, pre + "slice3.0", x))))
+    x = tap("cra.s3b", R(lrelu(conv(P, pre + "slice3.2", x))))
+    lv1 = tap("cra.lv1", R(lrelu(conv(P, pre + "conv_lv1", x))))                                     # :162
+    x = tap("cra.s4a", R(lrelu(conv(P, pre + "slice4.0", x))))
+    x = tap("cra.s4b", R(lrelu(conv(P, pre + "slice4.2", x))))
+    lv0 = tap("cra.lv0", R(lrelu(conv(P, pre + "conv_lv0", x))))                                     # :164
+    return lv0, lv1, lv2, lv3
+
+
+def _head(P, cfg, feat: Tensor, x_hr: Tensor, mkf: Tensor, lr: Tensor, lr8: Tensor):
+    """Fovea fusion and output head, the same lines in every wiring (model/CRFP.py:1065-1076, 1350-1361, 1672-1683, 2631-2642)."""
+    fused = conv(P, "conv_tttf", torch.cat([feat, x_hr], dim=1))
+    feat = tap("state_hr", R(lrelu(mkf * fused + (1 - mkf) * feat)))
+    out = conv(P, "conv_last", feat)
+    return out + (up_bilinear(rgb_to_y(lr), 8) if cfg.y_only else lr8), feat
+
+
+def cra_frame(P, cfg: WiringConfig, st, lr: Tensor, fv: Tensor, mk: Tensor, flow: Optional[Tensor], mk2_mode: str = "bilinear"):
+    """One iteration of CRFP_DSV_CRA.forward (model/CRFP.py:2492-2643) with the per-frame share of the up-front encoders (:2467-2478).
+    CRFP_DSV's recurrence with the four-level fovea encoder and, behind each 2x level's residual block, the cross-resolution fusion
+    ``mk2 * conv_tttf_k(cat(y, fovea level k)) + (1 - mk2) * y`` (:2533-2535, 2549-2551, 2565-2567; first frame :2589-2591 ...), mk2 =
+    img_downsample_4x(mk.float()) (:2501; nn.Upsample(0.25, bilinear), :2402).  ``mk2_mode="nearest"`` is a deliberately wrong mask for the
+    tests' guard."""
+    n, _, h, w = lr.shape
+    mkf = mk.to(lr.dtype)
+    lr8 = up_bilinear(lr, 8)                                                  # :2469
+    x_lr = tap("x_lr", R(lrelu(conv(P, "encoder_lr.slice1.2", tap("enc_lr0", R(lrelu(conv(P, "encoder_lr.slice1.0", lr))))))))  # :2471
+    fvb = fv * mkf + lr8 * (1 - mkf)                                          # :2475
+    x6 = tap("xin8", torch.cat((R(fvb), R(lr8)), dim=1))                      # :2478
+    lvs = lte_hr_ps(P, "encoder_hr.", x6)
+    x_hr = tap("x_hr", lvs[3])
+    mk2 = F.interpolate(mk.to(lr.dtype), scale_factor=0.25, mode=mk2_mode, **({"align_corners": False} if mk2_mode == "bilinear" else {}))  # :2501
+    tap("mk2", mk2)
+
+    def fuse(lvl, y):   # :2533-2540
+        tap(f"cra.y{lvl}", y)
+        fz = tap(f"cra.fused{lvl}", R(conv(P, f"conv_tttf_{lvl}", torch.cat([y, lvs[lvl]], dim=1))))
+        y = tap(f"res{lvl}", R(mk2 * fz + (1 - mk2) * y))
+        return y[:, :cfg.prop], y[:, cfg.prop:]
+
+    prop = tap("prop0", R(pixel_shuffle_pack(P, "upsample.", x_lr, 2)))       # :2500
+    new_carry = []
+    if flow is not None:
+        flow2 = up_bilinear(flow, 2) * 2.0                                    # :2506
+        flow8 = up_bilinear(flow, 8) * 8.0                                    # :2507
+        prev_hr = st["hr"]
+        tap("flow2", flow2.permute(0, 2, 3, 1))
+        tap("flow8", flow8.permute(0, 2, 3, 1))
+        prev2 = tap("prev2", R(pixel_unshuffle_pack_v2(P, "downsample.", prev_hr, 4)))   # :2510
+        prev2_w = tap("prev2w", R(flow_warp(prev2, flow2.permute(0, 2, 3, 1))))          # :2511
+        prev_hr_w = tap("prevhrw", R(flow_warp(prev_hr, flow8.permute(0, 2, 3, 1))))     # :2512
+        carry = torch.chunk(tap("carryw", R(flow_warp(torch.cat(st["carry"], dim=1), flow2.permute(0, 2, 3, 1)))), 3, dim=1)  # :2514-2523
+        off_feat = None
+        for lvl in range(3):                                                  # :2527-2572
+            cur = torch.cat((prop, carry[lvl]), dim=1)
+            aligned, off_feat = dcn_module(P, f"dcn_{lvl}.", cur, prev2, prev2_w, flow2, off_feat, dg=cfg.dg, repeat=False, interpolate="none")
+            prop, c_new = fuse(lvl, resblocks_with_input_conv(P, f"forward_resblocks_{lvl}.", torch.cat([cur, aligned], dim=1)))
+            new_carry.append(c_new)
+        up = tap("up", R(lrelu(pixel_shuffle_pack(P, "upsample_post.", prop, 4))))       # :2575
+        aligned, _ = dcn_module(P, "dcn_3.", up, prev_hr, prev_hr_w, flow8, off_feat, dg=1, repeat=True, interpolate="pixelshuffle",
+                                flow_is_mfma_operand=False)                   # :2576
+        feat = tap("feat", resblocks_with_input_conv(P, "forward_resblocks_3.", torch.cat([up, aligned], dim=1)))   # :2579-2580
+    else:
+        zeros2 = lr.new_zeros(n, cfg.mid, 2 * h, 2 * w)
+        for lvl in range(3):                                                  # :2587-2620
+            prop, c_new = fuse(lvl, resblocks_with_input_conv(P, f"forward_resblocks_{lvl}.", torch.cat([prop, zeros2, st["carry"][lvl]], dim=1)))
+            new_carry.append(c_new)
+        up = tap("up", R(lrelu(pixel_shuffle_pack(P, "upsample_post.", prop, 4))))       # :2623
+        feat = tap("feat", resblocks_with_input_conv(P, "forward_resblocks_3.", torch.cat([up, st["hr"]], dim=1)))  # :2625-2626
+    tap("carry", torch.cat(new_carry, dim=1))
+    out, feat = _head(P, cfg, feat, x_hr, mkf, lr, lr8)                       # :2631-2642
+    return out, {"hr": feat, "carry": new_carry, "first": False}
+
+
+def ablation_frame(P, cfg: WiringConfig, st, lr: Tensor, fv: Tensor, mk: Tensor, flow: Optional[Tensor], drop_third: bool = False):
+    """One iteration of CRFP_simple.forward (model/CRFP.py:979-1077) or, with ``cfg.dense``, of CRFP.forward (:1264-1362), hr_dcn and
+    offset_prop on.  Against CRFP_DSV: all mid_channels pass from level to level and nothing is carried beside them; the previous state is
+    warped at 8x FIRST and both versions are brought to 2x by ``downsample`` (:999-1002); the dense variant hands every residual block
+    the warped previous state as a third input (:1311, 1316, 1321, and the 8x one :1333).  ``drop_third`` zeroes that third input (the
+    tests' guard: dense then equals simple on weights whose third block is ignored)."""
+    n, _, h, w = lr.shape
+    mkf = mk.to(lr.dtype)
+    lr8 = up_bilinear(lr, 8)                                                  # :962
+    x_lr = tap("x_lr", R(lrelu(conv(P, "encoder_lr.slice1.2", tap("enc_lr0", R(lrelu(conv(P, "encoder_lr.slice1.0", lr))))))))  # :964
+    fvb = fv * mkf + lr8 * (1 - mkf)                                          # :968
+    x6 = tap("xin8", torch.cat((R(fvb), R(lr8)), dim=1))                      # :971
+    x_hr = tap("x_hr", R(lrelu(conv(P, "encoder_hr.slice1.2", tap("enc_hr0", R(lrelu(conv(P, "encoder_hr.slice1.0", x6))))))))
+    third = (lambda x: [x * 0 if drop_third else x]) if cfg.dense else (lambda x: [])
+    prop = tap("prop0", R(pixel_shuffle_pack(P, "upsample.", x_lr, 2)))       # :984  [n, mid, 2h, 2w]
+    if flow is not None:
+        flow2 = up_bilinear(flow, 2) * 2.0                                    # :989
+        flow8 = up_bilinear(flow, 8) * 8.0                                    # :991
+        prev_hr = st["hr"]
+        tap("flow2", flow2.permute(0, 2, 3, 1))
+        tap("flow8", flow8.permute(0, 2, 3, 1))
+        prev_hr_w = tap("prevhrw", R(flow_warp(prev_hr, flow8.permute(0, 2, 3, 1))))     # :1000
+        prev2_w = tap("prev2w", R(pixel_unshuffle_pack_v2(P, "downsample.", prev_hr_w, 4)))   # :1001
+        prev2 = tap("prev2", R(pixel_unshuffle_pack_v2(P, "downsample.", prev_hr, 4)))        # :1002
+        off_feat = None
+        for lvl in range(3):                                                  # :1009-1030
+            aligned, off_feat = dcn_module(P, f"dcn_{lvl}.", prop, prev2, prev2_w, flow2, off_feat, dg=cfg.dg, repeat=False, interpolate="none")
+            prop = tap(f"res{lvl}", resblocks_with_input_conv(P, f"forward_resblocks_{lvl}.", torch.cat([prop, aligned] + third(prev2_w), dim=1)))
+        up = tap("up", R(lrelu(pixel_shuffle_pack(P, "upsample_post.", prop, 4))))       # :1034
+        aligned, _ = dcn_module(P, "dcn_3.", up, prev_hr, prev_hr_w, flow8, off_feat, dg=1, repeat=True, interpolate="pixelshuffle",
+                                flow_is_mfma_operand=False)                   # :1035
+        feat = tap("feat", resblocks_with_input_conv(P, "forward_resblocks_3.", torch.cat([up, aligned] + third(prev_hr_w), dim=1)))   # :1039-1040
+    else:
+        zeros2, zeros8 = lr.new_zeros(n, cfg.mid, 2 * h, 2 * w), st["hr"]     # the zero state of :957-958
+        for lvl in range(3):                                                  # :1044-1053
+            prop = tap(f"res{lvl}", resblocks_with_input_conv(P, f"forward_resblocks_{lvl}.", torch.cat([prop, zeros2] + third(zeros2), dim=1)))
+        up = tap("up", R(lrelu(pixel_shuffle_pack(P, "upsample_post.", prop, 4))))       # :1057
+        feat = tap("feat", resblocks_with_input_conv(P, "forward_resblocks_3.", torch.cat([up, zeros8] + third(zeros8), dim=1)))      # :1058-1061
+    out, feat = _head(P, cfg, feat, x_hr, mkf, lr, lr8)                       # :1065-1076
+    return out, {"hr": feat, "carry": [], "first": False}
+
+
+def frame_fn(cfg):
+    """The frame function of a config's wiring: (P, cfg, st, lr, fv, mk, flow) -> (out, state)."""
+    wiring = getattr(cfg, "wiring", "dsv")
+    return cra_frame if wiring == "cra" else ablation_frame if wiring in ("simple", "dense") else dsv_frame
+
+
+def wiring_new_state(cfg, n: int, h: int, w: int, like: Tensor):
+    """Zero recurrent state of any wiring (simple / dense: the 8x feature alone, model/CRFP.py:957-958)."""
+    if getattr(cfg, "abl", False):
+        return {"hr": like.new_zeros(n, cfg.last, 8 * h, 8 * w), "carry": [], "first": True}
+    return new_state(cfg, n, h, w, like)
+
+
+def wiring_forward(P, lrs: Tensor, fvs: Tensor, mks: Tensor, cfg: WiringConfig, flows: Optional[Tensor] = None) -> Tensor:
+    """Clip forward of any wiring: lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], bool mks[n,t,1,8h,8w] -> [n,t,3|1,8h,8w].  flows [n,t-1,2,h,w]:
+    the flow to use instead of the oracle's own FNet (every wiring computes FNet(frame i, frame i - 1), :1483-1508)."""
+    n, t, c, h, w = lrs.shape
+    if flows is None and t > 1:
+        flows = compute_flow(P, lrs)
+    st = wiring_new_state(cfg, n, h, w, lrs)
+    step, outs = frame_fn(cfg), []
+    for i in range(t):
+        out, st = step(P, cfg, st, lrs[:, i], fvs[:, i], mks[:, i], flows[:, i - 1] if i > 0 else None)
+        outs.append(out)
+    return torch.stack(outs, dim=1)
+
+
 class StreamOracle:
     """One-frame-per-call variant (model/CRFP_test.py:2114-2478, MRCF_simple_v18): recurrent state and
     the previous LR frame persist between calls; ``clear_states`` (:2473-2478) starts a new sequence.
     Flow of the first frame of a sequence is FNet(frame, last frame of the same call) (:2234-2239) but
-    unused, because that frame takes the state-less branch (:2309 ``torch.is_tensor(self.feat_prop_lv3)``)."""
+    unused, because that frame takes the state-less branch (:2309 ``torch.is_tensor(self.feat_prop_lv3)``).
+    With a ``WiringConfig`` it is MRCF_simple_v13 / v15 / v18_cra (:1184-1486, 1805-2113, 2480-2861): the same carry of state and
+    previous frame around ``ablation_frame`` / ``cra_frame``; these three never read ``fgs`` (v13 / v15 resample it and drop the
+    result, :1357-1359, 1978-1980)."""
 
     def __init__(self, P, cfg: Optional[DSVConfig] = None):
         self.P, self.cfg = P, cfg or DSVConfig()
@@ -398,15 +573,19 @@ class StreamOracle:
     def __call__(self, lrs: Tensor, fvs: Tensor, mks: Tensor, fgs: Optional[Tensor] = None) -> Tensor:
         n, t, c, h, w = lrs.shape
         if self.st is None:
-            self.st = new_state(self.cfg, n, h, w, lrs)
+            self.st = wiring_new_state(self.cfg, n, h, w, lrs)
+        step = frame_fn(self.cfg)
         outs = []
         for i in range(t):
             lr = lrs[:, i]
             flow = None
             if not self.st["first"]:
                 flow = fnet(self.P, "spynet.", lr, self.prev_lr)
-            out, self.st = dsv_frame(self.P, self.cfg, self.st, lr, fvs[:, i], mks[:, i], flow,
-                                     None if fgs is None else fgs[:, i])
+            if step is dsv_frame:
+                out, self.st = dsv_frame(self.P, self.cfg, self.st, lr, fvs[:, i], mks[:, i], flow,
+                                         None if fgs is None else fgs[:, i])
+            else:
+                out, self.st = step(self.P, self.cfg, self.st, lr, fvs[:, i], mks[:, i], flow)
             self.prev_lr = lr
             outs.append(out)
         return torch.stack(outs, dim=1)

@@ -85,5 +85,9 @@ def test_stream_engines_keep_the_clip_engines_refusals():
     e = object.__new__(engine.DenseStreamEngine)
     e.storage = "bf16"
     with pytest.raises(NotImplementedError):
-        e._call("debug_fetch")
+        e._call("fnet_forward")
+    # the workspace fetch reads the wiring's own Layout through the wiring's own symbol
+    from crfp_amd import _lib
+    assert _lib.symbol("dense", "debug_fetch", "bf16") == "crfp_dense_debug_fetch_bf16" and _lib.symbol("simple", "debug_fetch") == "crfp_simple_debug_fetch"
+    assert engine.DenseStreamEngine.debug_fetch is engine.DSVEngine.debug_fetch
 

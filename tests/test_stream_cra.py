@@ -29,6 +29,11 @@ def _table(m):
     return [f"{k}:{','.join(map(str, v.shape))}" for k, v in m.state_dict().items()]
 
 
+def _lib_row(key):
+    from crfp_amd import _lib
+    return _lib.FAMILIES[key]
+
+
 def test_cra_row_carries_stream_batch_for_both_storages():
     from crfp_amd import _lib
     row = _lib.FAMILIES["cra"]
@@ -72,9 +77,11 @@ def test_stream_handle_offers_what_the_clip_handle_withholds(storage):
         c.stream_frame(None, None, None)
     for e in (s, c):
         assert e._call("forward_batch") == "bound"
-        for op in ("fnet_forward", "debug_fetch"):
-            with pytest.raises(NotImplementedError, match="CRFP_DSV_CRA"):
-                e._call(op)
+        with pytest.raises(NotImplementedError, match="CRFP_DSV_CRA"):
+            e._call("fnet_forward")
+        with pytest.raises(KeyError):      # debug_fetch is in the row (crfp_cra_debug_fetch); this hand-made table of bound functions lacks it
+            e._call("debug_fetch")
+        assert "debug_fetch" in _lib_row("cra").ops and type(e).debug_fetch is engine.DSVEngine.debug_fetch
     assert issubclass(engine.CRAStreamEngine, engine.CRAEngine) and engine.CRAStreamEngine._withheld == frozenset()
     assert engine.CRAStreamEngine.stream_frame is engine.DSVEngine.stream_frame
     assert engine.CRAStreamEngine.clear_states is engine.DSVEngine.clear_states

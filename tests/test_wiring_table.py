@@ -15,7 +15,7 @@ from crfp_amd import _lib, engine
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the C-ABI's n = 1 conveniences (crfp_dsv_forward_clip = crfp_dsv_forward_batch with n = 1, and so on): exported and bound, used by no handle
 N1_CONVENIENCES = {f"crfp_dsv_{n}{s}" for n in ("forward_clip", "stream_frame", "workspace_bytes", "status_offset") for s in ("", "_bf16")}
-CLIP_REFUSED = {"stream_batch", "fnet_forward", "debug_fetch"}
+CLIP_REFUSED = {"stream_batch", "fnet_forward"}      # every wiring has a debug_fetch of its own Layout
 REFUSED = {"DSVEngine": set(), "CRAEngine": CLIP_REFUSED, "SimpleEngine": CLIP_REFUSED, "DenseEngine": CLIP_REFUSED,
            "SimpleStreamEngine": CLIP_REFUSED - {"stream_batch"}, "DenseStreamEngine": CLIP_REFUSED - {"stream_batch"}}
 DSV_OPS = {"param_numel", "packed_weight_bytes", "pack_weights", "batch_workspace_bytes", "batch_status_offset", "forward_batch",
@@ -43,6 +43,10 @@ def test_rows_name_the_five_families():
     assert [r.names for r in _lib.FAMILIES.values()] == ["dsv", "cra", "dsv", "dsv", "rt"]
     assert [r.num_params for r in _lib.FAMILIES.values()] == [_lib.NUM_PARAMS, _lib.CRA_NUM_PARAMS, _lib.NUM_PARAMS, _lib.NUM_PARAMS, _lib.RT_NUM_PARAMS]
     assert _lib.FAMILIES["dsv"].ops == DSV_OPS
+    for key in ("cra", "simple", "dense"):      # everything CRFP_DSV has but the stand-alone flow network call, the fetch in both storage types
+        assert _lib.FAMILIES[key].ops == DSV_OPS - {"fnet_forward"} and "debug_fetch" in _lib.FAMILIES[key].bf16
+        assert _lib.symbol(key, "debug_fetch", "bf16") == f"crfp_{key}_debug_fetch_bf16"
+        assert _lib.SIGNATURES[f"crfp_{key}_debug_fetch"] == _lib.SIGNATURES["crfp_dsv_debug_fetch"]
     assert _lib.FAMILIES["rt"].ops == {"param_numel", "packed_weight_bytes", "pack_weights", "workspace_bytes", "forward_clip", "debug_fetch"}
     # the regional fetch takes the seven-number geometry: an argument list of its own, not CRFP_DSV's
     assert _lib.SIGNATURES["crfp_rt_debug_fetch"] != _lib.SIGNATURES["crfp_dsv_debug_fetch"]

@@ -939,6 +939,46 @@ int main() {
                     EXPECT(crfp_rt_debug_fetch(nm, t, 135, 240, 96, 96, 720, 720, wsp, out, nullptr, nullptr, nullptr, stream) == 0);
             EXPECT(crfp_stub_launches() == l1 + 2 * (22 - 5));   // the two flow fields and the three split-fp16 images are copies
         }
+        // the clip wirings' debug fetch: each reads its own Layout (cra.* exists for cra only, prop0 is 32 channels wide for simple / dense),
+        // refusals and size queries launch nothing, frame-slot names answer with and without ".1"
+        {
+            typedef int (*fetch_fn)(const char*, int, int, int, const void*, float*, int*, int*, int*, void*);
+            const fetch_fn fetch[8] = {crfp_dsv_debug_fetch, crfp_cra_debug_fetch, crfp_simple_debug_fetch, crfp_dense_debug_fetch,
+                                       crfp_dsv_debug_fetch_bf16, crfp_cra_debug_fetch_bf16, crfp_simple_debug_fetch_bf16, crfp_dense_debug_fetch_bf16};
+            const long l1 = crfp_stub_launches();
+            for (int k = 0; k < 8; ++k) {
+                const int wiring = k % 4;   // 0 dsv, 1 cra, 2 simple, 3 dense
+                int c = -1, hh = -1, ww = -1;
+                EXPECT(fetch[k](nullptr, 3, 33, 47, wsp, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+                EXPECT(fetch[k]("x_hr", 3, 33, 47, nullptr, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+                EXPECT(fetch[k]("x_hr", 0, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+                EXPECT(fetch[k]("x_hr", 3, 7, 47, wsp, nullptr, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+                EXPECT(fetch[k]("no_such_buffer", 3, 33, 47, wsp, out, &c, &hh, &ww, stream) == CRFP_E_BADARG);
+                EXPECT(std::strstr(crfp_last_error_string(), "unknown buffer 'no_such_buffer'") != nullptr);
+                EXPECT(c == -1 && hh == -1 && ww == -1);
+                EXPECT(fetch[k]("prop0", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == (wiring >= 2 ? 32 : 24) && hh == 66 && ww == 94);
+                EXPECT(fetch[k]("prop0.1", 2, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == (wiring >= 2 ? 32 : 24));
+                EXPECT(fetch[k]("prop_a", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == (wiring >= 2 ? 32 : 24));
+                EXPECT(fetch[k]("state_hr", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 4 && hh == 264 && ww == 376);
+                EXPECT(fetch[k]("flow_lr", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 2 && c == 4 && hh == 33 && ww == 47);
+                for (const char* nm : {"cra.s1", "cra.a", "cra.b", "cra.lv0", "cra.lv1.1", "cra.lv2", "cra.y", "cra.fused"}) {
+                    const int n = fetch[k](nm, 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream);
+                    EXPECT(wiring == 1 ? n >= 1 : n == CRFP_E_BADARG);
+                }
+                if (wiring == 1) {
+                    EXPECT(fetch[k]("cra.s1", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 3 && c == 4 && hh == 264 && ww == 376);   // a group's items
+                    EXPECT(fetch[k]("cra.lv1", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 16 && hh == 66 && ww == 94);
+                    EXPECT(fetch[k]("cra.fused", 3, 33, 47, wsp, nullptr, &c, &hh, &ww, stream) == 1 && c == 32 && hh == 66 && ww == 94);
+                }
+            }
+            EXPECT(crfp_stub_launches() == l1);
+            for (int k = 0; k < 8; ++k) {
+                EXPECT(fetch[k]("prop_b", 3, 33, 47, wsp, out, nullptr, nullptr, nullptr, stream) == 0);
+                EXPECT(fetch[k]("flow2.1", 3, 33, 47, wsp, out, nullptr, nullptr, nullptr, stream) == 0);   // a copy, not a launch
+                if (k % 4 == 1) EXPECT(fetch[k]("cra.lv0.1", 3, 33, 47, wsp, out, nullptr, nullptr, nullptr, stream) == 0);
+            }
+            EXPECT(crfp_stub_launches() == l1 + 8 + 2);
+        }
         EXPECT(crfp_fnet_forward(pk, lrs, lrs, out, 2, 180, 320, wsp, crfp_dsv_workspace_bytes(3, 180, 320), stream) == 0);
         EXPECT(crfp_debug_side_tables() >= 1);
         EXPECT(crfp_shutdown() == 0);

@@ -3,6 +3,8 @@
 against the oracle's taps of the same frame, run with the engine's own flow.
   python tools/bisect_engine.py [--storage bf16] [--h 24 --w 40] [--t 2]
   CRFP_DCN_FUSED=0 python tools/bisect_engine.py --schedule dcn_fused0       another schedule: its switches go into the environment
+  python tools/bisect_engine.py --wiring cra|simple|dense [--storage bf16] [--t 3]   the other clip wirings (crfp_cra_ / crfp_simple_ /
+        crfp_dense_debug_fetch; the tables of tests/helpers/wiring_stage_cases.py; schedules product | unfused: CRFP_DCN_FUSED=0 CRFP_CONV_PAIR=0)
   python tools/bisect_engine.py --rt [--h 24 --w 40 --fv 64 --warp 128 192]    the regional runtime engine (crfp_rt_debug_fetch)"""
 import argparse
 import os
@@ -24,6 +26,8 @@ ap.add_argument("--fv", type=int, default=64)
 ap.add_argument("--t", type=int, default=2, help="frames of the clip: the buffers hold frame t - 1 (parity set (t - 1) & 1)")
 ap.add_argument("--schedule", default="product", help="the schedule the environment selects (tests/helpers/dsv_stage_cases.py, SCHEDULES): "
                 "decides which buffers are live")
+ap.add_argument("--wiring", default="dsv", choices=("dsv", "cra", "simple", "dense"), help="the clip engine's wiring: CRFP_DSV, or CRFP_DSV_CRA / "
+                "CRFP_simple / CRFP through their own debug fetch and stage table (tests/helpers/wiring_stage_cases.py)")
 ap.add_argument("--rt", action="store_true", help="the regional runtime engine (crfp_rt_debug_fetch) instead of CRFP_DSV")
 ap.add_argument("--warp", type=int, nargs=2, default=(128, 192), help="--rt: warp_size")
 a = ap.parse_args()
@@ -65,6 +69,39 @@ if a.rt:   # frame 1 of a 2-frame clip: every fetch name against the fp32 oracle
 # tap each equals and where (mask-gated buffers: inside the fovea mask dilated by their distance to the blend) -- nothing else is printed.
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from helpers import dsv_stage_cases as sc  # noqa: E402
+
+if a.wiring != "dsv":   # the wiring's own table, weights of its own shapes, the same walk
+    from helpers import wiring_stage_cases as wc  # noqa: E402
+    sched, build, wiring = a.schedule, "bf16" if a.storage == "bf16" else "f32", a.wiring
+    for k, v in wc.SCHEDULES[sched].items():
+        if os.environ.get(k) != v:
+            sys.exit(f"--schedule {sched} needs {k}={v} in the environment (the library reads it once)")
+    sd = synth.make_state_dict_like(wc.shapes(wiring), wc.WEIGHTS_SEED)
+    t, h, w = a.t, a.h, a.w
+    lrs, fvs, mks = synth.make_clip(3, 1, t, h, w, fv_size=a.fv)
+    m = wc.make_model(wiring, sd, a.storage)
+    with torch.no_grad():
+        sc.dirty_workspace(m.engine(), t, h, w)
+        out = m(lrs=T(lrs).to(dev), fvs=T(fvs).to(dev), mks=T(mks).to(dev)).cpu()
+        eng = m.engine()
+        flows = eng.debug_fetch("flow_lr", t, h, w)[:, :2].cpu()[None]
+        refs = wc.oracle_taps(orc, wiring, sd, lrs, fvs, mks, flows=flows, bf16=build == "bf16")
+    f = wc.flags(wiring, build, sched)
+    print(f"{wiring}: {build} build, schedule {sched}, frame {t - 1} of a {t}-frame clip {h} x {w}; not written under this schedule: "
+          + " ".join(n for n in wc.fetch_names(wiring, t) if n not in wc.written_names(wiring, build, sched, t)))
+    for r in wc.rows_for(wiring, build, sched):
+        for name, idx, frame in wc.slots(r, t):
+            got = eng.debug_fetch(name, t, h, w)[idx:idx + 1].cpu()
+            got = got if r.sel is None else got[:, r.sel]
+            want = wc.tap_of(refs[frame], r.tap)
+            reg = wc.region(r, f, mks[0, frame, 0])
+            if reg is not None:
+                keep = T(reg)[None, None]
+                got, want = torch.where(keep, got, torch.zeros(())), torch.where(keep, want, torch.zeros(()))
+            show(f"{r.key} [{name}, frame {frame}]", got, want)
+    for i in range(t):
+        show(f"out frame {i}", out[:, i], refs[i]["out"])
+    sys.exit(0)
 
 sched = a.schedule
 for k, v in sc.SCHEDULES[sched][0].items():
