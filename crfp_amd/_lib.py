@@ -47,6 +47,18 @@ class NarrowReport(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("kernel", "kq", "epi", "gate", "st2", "kqg", "res", "tiles", "workgroups")]
 
 
+class DcnTailArgs(C.Structure):
+    """crfp_dcn_tail_args of include/crfp_hip.h: the device buffers of a crfp_dcn_tail_probe call (test hook)."""
+    _fields_ = [(k, C.c_void_p) for k in ("feat", "flow", "wconv", "bconv", "x", "wdcn", "bdcn", "out", "status", "warp_src", "warp_flow", "warp_dst")] + \
+               [(k, C.c_longlong) for k in ("feat_b", "flow_b", "x_b", "out_b", "warp_src_b", "warp_flow_b", "warp_dst_b")] + \
+               [(k, C.c_int) for k in ("n", "h", "w", "bands")]
+
+
+class DcnTailReport(C.Structure):
+    """crfp_dcn_tail_report: how the fused DCN launch of a crfp_dcn_tail_probe call is sized."""
+    _fields_ = [(k, C.c_int) for k in ("cus", "tiles", "persistent", "warp_wgs", "plan_taken", "grid")]
+
+
 NARROW_KERNELS = ("none", "narrow", "seq", "pair", "chain")   # CRFP_NARROWK_*
 NARROW_MODES = {"single": 0, "pair": 1, "chain": 2}
 NARROW_EPI = {"plain": 0, "blend": 1, "last": 2, "offmask3": 3}
@@ -151,6 +163,8 @@ SIGNATURES = {
     "crfp_narrow_probe": (C.c_int, _NARROW_HEAD + [C.c_void_p, C.c_void_p, C.POINTER(NarrowReport), C.c_void_p, C.c_size_t, C.c_void_p]),
     "crfp_dsv_debug_fetch": (C.c_int, [C.c_char_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p] +
                              [C.POINTER(C.c_int)] * 3 + [C.c_void_p]),
+    "crfp_dcn_tail_plan": (C.c_int, [C.POINTER(DcnTailArgs), C.POINTER(DcnTailReport)]),
+    "crfp_dcn_tail_probe": (C.c_int, [C.POINTER(DcnTailArgs), C.POINTER(DcnTailReport), C.c_void_p]),
 }
 CRA_NUM_PARAMS = 144
 
@@ -209,6 +223,8 @@ for _n in ("workspace_bytes", "kernel", ""):
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 for _n in ("workspace_bytes", "plan", ""):
     _n = "crfp_narrow_probe" + ("_" + _n if _n else "")
+    SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
+for _n in ("crfp_dcn_tail_plan", "crfp_dcn_tail_probe"):
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 
 _lib = None

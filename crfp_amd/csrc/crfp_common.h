@@ -62,6 +62,14 @@ bool precision_env_strict(int family);   // CRFP_PRECISION=f32 in the environmen
 // clip calls run a frame's state-independent work in groups of frames (engine.hip, prework_group); lab library: crfp_lab_prework_groups(0) keeps one
 // frame per launch.  Here, and not in the engine, because the lab library's bf16 engine is the product's object: both builds ask this one.
 bool prework_groups();
+// CRFP_DSV / CRFP_DSV_CRA: the 8x state warp (state_hr, flow8 -> prevhrw, first read by dcn_3's block.0) rides as equal row bands in the idle
+// last-round CUs of the frame's first warp_tail_bands() fused DCN launches (DcnWarpPlan, dcn_fused.inc) instead of standing in front of level 0
+// as a launch of its own; 0: the stand-alone launch.  Lab library: crfp_lab_warp_tail_bands(n), in runtime.hip for the reason above.
+#ifndef CRFP_WARP_TAIL_BANDS   // csrc/Makefile EXTRA=-DCRFP_WARP_TAIL_BANDS=<0..3>: product builds of the other splits, for A/Bs (only runtime.hip reads it)
+#define CRFP_WARP_TAIL_BANDS 3
+#endif
+constexpr int kWarpTailBands = CRFP_WARP_TAIL_BANDS;
+int warp_tail_bands();
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // diagnostic builds (tools/stamp_*.py): the s_memtime stamp buffer CRFP_STAMP_PTR when CRFP_STAMP_NAME names this launch site, else null
 static inline long long* lab_stamps(const char* site) {   // (static: the lab library links lab and product objects)
@@ -84,6 +92,7 @@ using crfp::ProfScope;
 using crfp::prof_enabled;
 using crfp::precision_env_strict;
 using crfp::prework_groups;
+using crfp::warp_tail_bands;
 using crfp::align_up;
 using crfp::lab_stamps;
 
@@ -424,8 +433,19 @@ int launch_dcn_g8(const float* x, long long xb, const float* offmask, long long 
 int launch_dcn_g8_pack(const float* w_oihw, float* wpk, hipStream_t s, bool f16 = false);  // fp32 [36][2][32][4] or split-fp16 image
 bool dcn_g8_use_f16();   // engine: split-fp16 DCN GEMM unless CRFP_DCN_MODE=f32
 // offset / mask conv (32 -> 216, model/CRFP.py:337-340) + dcn_g8 in ONE kernel: the 199 MB offset / mask tensor never exists
+// A row band of a one-quad flow_warp_p4_kernel launch (the 8x state warp) that rides in a fused launch's last round: the workgroups behind the
+// launch's tiles, one per CU that round leaves without a tile, walk rows [y0, y1) of every batch item (dcn_fused.inc).  dst == null: no plan.
+struct DcnWarpPlan {
+    const float* src = nullptr;    // P4 plane to sample (one quad)
+    const float* flow = nullptr;   // [H8][W8][2]
+    float* dst = nullptr;          // Q4
+    long long src_b = 0, flow_b = 0, dst_b = 0;   // between batch items, in elements of each tensor's own type (launch_flow_warp_q4's xb, fb, ob)
+    int H8 = 0, W8 = 0, y0 = 0, y1 = 0;
+    // band b of `bands` equal row bands of the H8 rows: the bands of a warp split over several launches tile [0, H8)
+    void band(int b, int bands) { y0 = (int)((long long)H8 * b / bands); y1 = (int)((long long)H8 * (b + 1) / bands); }
+};
 struct DcnFuseArgs {
-    const float* feat;      // the DCN offset feature (32 channels): SRC_S3 image in the fp32 build, bf16 Q4 in the bf16 build
+    const float* feat;     // the DCN offset feature (32 channels): SRC_S3 image in the fp32 build, bf16 Q4 in the bf16 build
     long long feat_b;       // floats (fp32 build) / elements (bf16 build) between batch items
     const float* flow;      // [H][W][2] (x, y) added to the offsets as (y, x)
     long long flow_b;
@@ -441,9 +461,16 @@ struct DcnFuseArgs {
     unsigned* ovf;
     int ovf_div;            // 0: one status word; 1: batch item n raises ovf[n]
     int probe;              // lab library only: timing experiments
+    DcnWarpPlan warp;       // optional: a warp band for the launch's idle last-round CUs (launch_dcn_fused refuses it where dcn_fused_tail_wgs is 0)
 };
 bool dcn_fused_enabled();   // default on; CRFP_DCN_FUSED=0 keeps the two-kernel path
 int launch_dcn_fused(const DcnFuseArgs& a, hipStream_t s);
+// How launch_dcn_fused sizes a launch of N maps of H x W on the current device (cus: its CU count rounded down to a multiple of 8, <= 0 with
+// the error set when it cannot be read): the persistent form on `cus` workgroups, or one workgroup per tile plus `warp_wgs` for a warp plan.
+struct DcnFusedGrid { int cus, tiles, persistent, warp_wgs; };
+DcnFusedGrid dcn_fused_grid(int N, int H, int W);
+// workgroups a warp plan would get in such a launch = CUs its last round leaves idle; 0: the launch takes no plan (persistent form, full last round, a lab form)
+int dcn_fused_tail_wgs(int N, int H, int W);
 int launch_dcn3(const float* x, long long xb, const float* offmask3, long long omb, const float* w_oihw,
                 const float* bias, float* out, long long ob, int N, int H, int W, hipStream_t s);
 int launch_dcn3_fused(const float* x, long long xb, const float* g2, long long gb, const float* flow, const float* wom, const float* bom,

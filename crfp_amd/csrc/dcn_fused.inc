@@ -374,6 +374,30 @@ constexpr double kFusedBytesPerPixel = 8.0 + (32 + 32 + 32) * sizeof(act_t);
         __builtin_amdgcn_sched_barrier(0);                                                                \
     }
 
+// The warp plan (DcnWarpPlan) of a one-tile launch: workgroups [tiles, tiles + M) of its 1-D grid, M = the CUs its last round leaves without a
+// tile (launch_dcn_fused).  Workgroups are handed out in index order, so these start only when every tile has a CU: they fill the hole and never
+// displace a tile.  Warp workgroup g of M walks the band's 64-pixel row segments -- (batch item, row, segment), wave-uniform -- wave by wave in a
+// grid-stride loop, DF_WARP_U segments per trip: such a CU holds these 8 waves and nothing else (the kernel's LDS and registers allow one
+// workgroup), so the load latency is covered inside the thread, not by occupancy -- 4 flow reads, then 16 corner loads (fp32) per thread, 128 KB
+// of gathers in flight per CU.  Per pixel it is flow_warp_p4_kernel's program (flow_warp_p4_pixels): the same bits.
+constexpr int DF_WARP_U = 4;
+__device__ __forceinline__ void df_warp_tail(const DcnWarpPlan& p, int N, int g, int M, int tid) {
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int segs_x = (p.W8 + 63) >> 6, per = segs_x * (p.y1 - p.y0), total = per * N, step = 8 * M;
+    for (int s0 = 8 * g + wave; s0 < total; s0 += DF_WARP_U * step) {
+        int n[DF_WARP_U], px[DF_WARP_U], py[DF_WARP_U];
+        bool st[DF_WARP_U];
+#pragma unroll
+        for (int u = 0; u < DF_WARP_U; ++u) {
+            const int s = s0 + u * step, sc = min(s, total - 1);   // past the end: the last segment again, nothing stored
+            const int nn = sc / per, r = sc - nn * per, y = r / segs_x, x = (r - y * segs_x) * 64 + lane;
+            n[u] = nn; py[u] = p.y0 + y; px[u] = min(x, p.W8 - 1);
+            st[u] = s < total && x < p.W8;
+        }
+        flow_warp_p4_pixels<DF_WARP_U>(p.src, p.src_b, p.flow, p.flow_b, p.dst, p.dst_b, 1, p.H8, p.W8, n, px, py, st);
+    }
+}
+
 // NW = 4: workgroup of 4 rows x 32 pixels, two per CU, one weight stage (two barriers per stage).  NW = 8: 8 rows, one workgroup
 // per CU, the weight stage double-buffered (one barrier per stage, half the L2 -> LDS weight and DCN-image traffic per pixel).
 // PS (round 6): the PERSISTENT form.  gridDim.x workgroups (one per CU) walk the tile list of the whole launch (all batch items), XCD x
@@ -409,9 +433,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void dcn_fused_kernel(con
     }
     int tx0, ty0, n;
     if (PS) DF_DECODE(t_cur, tx0, ty0, n)
-    else if (DB) {   // the one-tile form walks the tile list in the XCD-banded order too (xcd_band_tile over the launch's linear workgroup id)
-        const int lin_ = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-        const int tb_ = xcd_band_tile(lin_, (int)(gridDim.x * gridDim.y * gridDim.z));
+    else if (DB) {   // the one-tile form: a 1-D grid that walks the tile list in the XCD-banded order too; the workgroups behind the tiles carry the warp plan
+        const int ntiles_ = tiles_x * tiles_y * a.N;
+        if ((int)blockIdx.x >= ntiles_) {
+            df_warp_tail(a.warp, a.N, (int)blockIdx.x - ntiles_, (int)gridDim.x - ntiles_, tid0);
+            return;
+        }
+        const int tb_ = xcd_band_tile((int)blockIdx.x, ntiles_);
         DF_DECODE(tb_, tx0, ty0, n)
     }
     else { tx0 = blockIdx.x * 32; ty0 = blockIdx.y * NW; n = blockIdx.z; }
@@ -524,17 +552,60 @@ bool dcn_fused_enabled() {
     return on;
 }
 
-constexpr int kFusedPersistWgs = 256;   // workgroups of the persistent form = CUs of an MI355X (one 8-wave workgroup per CU: 155 KB of LDS, 250 VGPRs)
+// The CUs of the current device, rounded down to a multiple of 8 (one 8-wave workgroup per CU: 155 KB of LDS, 250 VGPRs; the persistent form
+// deals its workgroups to the 8 XCDs evenly): 256 on an MI355X.  Read once per device.  <= 0 with the error set when the device cannot be asked.
+static int fused_cus() {
+    constexpr int kDevs = 64;
+    static std::atomic<int> cus[kDevs];
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevs) { set_error("dcn_fused: no current device (hipGetDevice)"); return 0; }
+    int v = cus[dev].load(std::memory_order_relaxed);
+    if (v == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 8) { set_error("dcn_fused: cannot read the device's CU count"); return 0; }
+        v = prop.multiProcessorCount & ~7;
+        cus[dev].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
 // launches with at least this many tiles take the persistent form (six rounds of one workgroup per CU); the lab knob overrides (tests)
-static int fused_persist_min_tiles() {
-    const int v = CRFP_LAB_KNOB("CRFP_DF_PS_MIN_TILES", 6 * kFusedPersistWgs);
-    return v > kFusedPersistWgs ? v : kFusedPersistWgs + 1;
+static int fused_persist_min_tiles(int cus) {
+    const int k = CRFP_LAB_KNOB("CRFP_DF_PS_MIN_TILES", 0);
+    const int v = k > 0 ? k : 6 * cus;
+    return v > cus ? v : cus + 1;
+}
+
+DcnFusedGrid dcn_fused_grid(int N, int H, int W) {
+    DcnFusedGrid g = {fused_cus(), ((W + 31) / 32) * ((H + 7) / 8) * N, 0, 0};
+    if (g.cus <= 0) return g;
+    g.persistent = g.tiles >= fused_persist_min_tiles(g.cus);
+    const int rem = g.tiles % g.cus;   // tiles of the last round
+    if (!g.persistent && rem) g.warp_wgs = g.cus - rem;
+    return g;
+}
+
+int dcn_fused_tail_wgs(int N, int H, int W) {
+#ifdef CRFP_LAB   // the lab-only kernel forms (launch_dcn_fused_lab) take no plan
+    if (CRFP_LAB_KNOB("CRFP_DCN_FUSE_NW", 8) != 8 || CRFP_LAB_KNOB("CRFP_DCN_FUSE_V", 1) == 2) return 0;
+#endif
+    return dcn_fused_grid(N, H, W).warp_wgs;
 }
 
 int launch_dcn_fused(const DcnFuseArgs& args, hipStream_t s) {
     if ((long long)(args.H + 1) * (args.W + 1) >= (1ll << 24)) { set_error("dcn_g8: plane of %d x %d exceeds the sampler's 2^24-element index range", args.H, args.W); return CRFP_E_UNSUPPORTED; }
+    const DcnWarpPlan& wp = args.warp;
+    const int warp_wgs = wp.dst ? dcn_fused_tail_wgs(args.N, args.H, args.W) : 0;
+    if (wp.dst) {   // a plan is taken whole or refused: the caller asks dcn_fused_tail_wgs first and keeps its stand-alone warp where that is 0
+        if (!warp_wgs) { set_error("dcn_fused: this launch (%d x %d x %d) has no idle last-round CUs for a warp plan", args.N, args.H, args.W); return CRFP_E_UNSUPPORTED; }
+        if (!wp.src || !wp.flow || wp.H8 < 1 || wp.W8 < 1 || wp.y0 < 0 || wp.y1 <= wp.y0 || wp.y1 > wp.H8 || (long long)(wp.H8 + 1) * (wp.W8 + 1) >= (1ll << 27)) {   // (32-bit byte offsets)
+            set_error("dcn_fused: bad warp plan (rows [%d, %d) of %d x %d)", wp.y0, wp.y1, wp.H8, wp.W8);
+            return CRFP_E_BADARG;
+        }
+    }
     const double px = (double)args.N * args.H * args.W;
-    ProfScope prof("offset_mask_conv+dcnv2_g8_fused", s, px * kFusedBytesPerPixel, 2.0 * px * 32 * 216 * 9 + 2.0 * px * 32 * 32 * 9 + px * 288 * 7);
+    const double wpx = wp.dst ? (double)args.N * (wp.y1 - wp.y0) * wp.W8 : 0.0;   // the band it carries: flow_warp_q4_c4's bytes and flops per pixel
+    ProfScope prof("offset_mask_conv+dcnv2_g8_fused", s, px * kFusedBytesPerPixel + wpx * (2.0 * 4 * sizeof(act_t) + 8),
+                   2.0 * px * 32 * 216 * 9 + 2.0 * px * 32 * 32 * 9 + px * 288 * 7 + wpx * 4 * 7.0);
 #ifdef CRFP_LAB
     DcnFuseArgs a = args;
     if (launch_dcn_fused_lab(a, s)) { CRFP_CHECK_LAUNCH(); return 0; }   // the environment asked for a lab-only form
@@ -544,9 +615,11 @@ int launch_dcn_fused(const DcnFuseArgs& args, hipStream_t s) {
     // 8-wave workgroups: per launch same-box against <4>, 151.6 vs 165.3 us (fp32) and 91.9 vs 97.0 us (bf16, one clip)
     // Round 6: both forms walk the tile list in the XCD-banded order (HBM traffic 170 -> 112-116 MB per launch @A).  Launches of six rounds of
     // the chip and more (a lock-step batch, the 4K map) take the persistent form (-1 % there, +1.5 % at 3.5 rounds: profiles/r06_dcn_fused_persistent_ab.txt)
-    const int tiles = ((a.W + 31) / 32) * ((a.H + 7) / 8) * a.N;
-    if (tiles >= fused_persist_min_tiles()) dcn_fused_kernel<8, true><<<dim3(kFusedPersistWgs, 1, 1), 512, 0, s>>>(a);
-    else dcn_fused_kernel<8><<<dim3((a.W + 31) / 32, (a.H + 7) / 8, a.N), 512, 0, s>>>(a);
+    // The one-tile form is a 1-D grid: its tiles, then the workgroups of the warp plan (one per CU the last round leaves idle), if it carries one.
+    const DcnFusedGrid g = dcn_fused_grid(a.N, a.H, a.W);
+    if (g.cus <= 0) return CRFP_E_UNSUPPORTED;
+    if (g.persistent) dcn_fused_kernel<8, true><<<dim3(g.cus, 1, 1), 512, 0, s>>>(a);
+    else dcn_fused_kernel<8><<<dim3(g.tiles + warp_wgs, 1, 1), 512, 0, s>>>(a);
     CRFP_CHECK_LAUNCH();
     return 0;
 }

@@ -931,6 +931,11 @@ struct Runner {
         std::vector<NB> r3_srcs;   // inputs of forward_resblocks_3.main.0
         // forward_resblocks_3 as one launch; the bf16 chain kernel takes at most two input quads (CRFP's three: three launches there)
         const bool r3_chain = (chain_mask() & 2) && !(kActBf16 && dense && !first);
+        // the levels' offset / mask head + dcn_g8 as one launch (else two kernels)
+        const bool dcn_fused = (M.use_s3 || kActBf16) && !strict && dcn_g8_use_f16() && dcn_fused_enabled();
+        // The 8x state warp goes into the fused launches' idle last-round CUs, whole, or stays a launch of its own: all three launches of a frame
+        // have one shape, so they take a plan or none does (the persistent form -- a lock-step batch, the 4K map -- and a full last round take none).
+        const int warp_bands = !first && !abl && dcn_fused && dcn_fused_tail_wgs(B, H2, W2) > 0 ? warp_tail_bands() : 0;
         if (!first) {
             float* flow2 = F(L.flow2[par]);
             float* flow8 = F(L.flow8[par]);
@@ -944,7 +949,7 @@ struct Runner {
             WarpDualStrides wb;
             wb.xa = L.prev2.bs; wb.xb = L.carry.bs; wb.flow = f2b; wb.outa = L.prev2w.bs; wb.outb = L.carryw.bs;
             RUN(launch_flow_warp_p4_dual_8_6(F(L.prev2), carry, flow2, F(L.prev2w), F(L.carryw), H2, W2, s, B, wb));
-            RUN(launch_flow_warp_q4(F(L.state_hr), L.state_hr.bs, flow8, f8b, F(L.prevhrw), L.prevhrw.bs, B, 1, H8, W8, 0, 1, s));
+            if (!warp_bands) RUN(launch_flow_warp_q4(F(L.state_hr), L.state_hr.bs, flow8, f8b, F(L.prevhrw), L.prevhrw.bs, B, 1, H8, W8, 0, 1, s));
             }
             const float* offprev = nullptr;
             if (fg) RUN(crfp::launch_fg_prep(fg, F(L.fg2), H8, W8, s));
@@ -972,7 +977,7 @@ struct Runner {
                 }
                 const Item& dw = M.items[it_lvl(l, L_DCNW)];
                 const bool f16 = !strict && dcn_g8_use_f16();
-                if ((s3 || kActBf16) && f16 && dcn_fused_enabled()) {   // offset / mask head + dcn_g8 in one launch: offsets stay in registers
+                if (dcn_fused) {   // offset / mask head + dcn_g8 in one launch: offsets stay in registers
                     const Item& om = M.items[it_lvl(l, L_OMF)];
                     DcnFuseArgs fa;
                     memset(&fa, 0, sizeof(fa));
@@ -981,6 +986,11 @@ struct Runner {
                     fa.x = F(L.prev2); fa.xb = L.prev2.bs;
                     fa.wdcn = packed + dw.off_w + 36 * 2 * 32 * 4; fa.bdcn = packed + dw.off_b;
                     fa.out = F(L.aligned); fa.ob = bs8; fa.N = B; fa.H = H2; fa.W = W2; fa.ovf = ovf(); fa.ovf_div = ovf_div;
+                    if (l < warp_bands) {   // level l carries band l of the state warp
+                        fa.warp.src = F(L.state_hr); fa.warp.src_b = L.state_hr.bs; fa.warp.flow = flow8; fa.warp.flow_b = f8b;
+                        fa.warp.dst = F(L.prevhrw); fa.warp.dst_b = L.prevhrw.bs; fa.warp.H8 = H8; fa.warp.W8 = W8;
+                        fa.warp.band(l, warp_bands);
+                    }
                     RUN(launch_dcn_fused(fa, s));
                 } else {
                     mfma(it_lvl(l, L_OM), B, H2, W2, {{f, bs8}}, {{F(L.offmask), L.offmask.bs, 0, 54}}, 0, 0, nullptr, 0, flow2, f2b);

@@ -8,6 +8,7 @@
 // 1-KiB row segments that the CU's L1 serves 3 times out of 4; HBM sees each input line once.
 #include "crfp_common.h"
 #include "dcn_sampler.h"
+#include <atomic>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -80,40 +81,64 @@ __global__ __launch_bounds__(256) void flow_warp_q4_kernel(const float* __restri
 
 #endif
 
+// The per-pixel program of the P4 warp, written once for its two callers: flow_warp_p4_kernel (U = 1) and the warp workgroups of a fused DCN
+// launch (dcn_fused.inc, U pixels of a lane in flight).  Pixel u of the lane is (px[u], py[u]) of batch item n[u] (n, py: wave-uniform); every
+// lane computes and loads -- the caller hands lanes without a pixel the coordinates of one that exists -- and st[u] says whether it stores.
+// Per quad all U flow reads, then all 4 U corner loads go out before the first blend.
+template <int U>
+__device__ __forceinline__ void flow_warp_p4_pixels(const float* __restrict__ x, long long xb, const float* __restrict__ flow, long long fb,
+                                                    float* __restrict__ out, long long ob, int nq, int H, int W, const int (&n)[U],
+                                                    const int (&px)[U], const int (&py)[U], const bool (&st)[U]) {
+    const float dw = (float)(W - 1 > 1 ? W - 1 : 1), dh = (float)(H - 1 > 1 ? H - 1 : 1);
+    const int PW = W + 1, pitch = PW * QB, plane_b = (H + 1) * pitch;
+    // the descriptor starts one pad row + one element BEFORE plane 0 (zeroed guard that every P4
+    // allocation carries) so that (y0,x0) = (-1,-1) is still a non-negative offset
+    const int guard = pitch + QB;
+    const long long oplane = (long long)H * W * 4;
+    float2 f[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f[u] = ldnt2(flow + (long long)n[u] * fb + ((long long)py[u] * W + px[u]) * 2);
+    float w00[U], w01[U], w10[U], w11[U];
+    int voff[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const float gx = 2.0f * ((float)px[u] + f[u].x) / dw - 1.0f;
+        const float gy = 2.0f * ((float)py[u] + f[u].y) / dh - 1.0f;
+        float ix = (gx + 1.0f) * ((float)(W - 1) / 2.0f);
+        float iy = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
+        ix = fminf(fmaxf(ix, -1.0f), (float)W);
+        iy = fminf(fmaxf(iy, -1.0f), (float)H);
+        const float fx = floorf(ix), fy = floorf(iy);
+        const float lx = ix - fx, ly = iy - fy, hx = 1.0f - lx, hy = 1.0f - ly;
+        w00[u] = hy * hx; w01[u] = hy * lx; w10[u] = ly * hx; w11[u] = ly * lx;
+        voff[u] = ((int)fy * PW + (int)fx) * QB + guard;
+    }
+    for (int q = 0; q < nq; ++q) {
+        pairraw_t tp[U], bt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+                (char*)const_cast<act_t*>(as_act(x) + (long long)n[u] * xb) - guard, 0, nq * plane_b + guard, 0x00020000);
+            const int vo = voff[u] + q * plane_b;
+            tp[u] = bload_pair(r, vo, 0); bt[u] = bload_pair(r, vo, pitch);
+        }
+        if (U > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            act_t* os = as_act(out) + (long long)n[u] * ob + ((long long)py[u] * W + px[u]) * 4;
+            if (st[u]) stq(os + q * oplane, pair_lo(tp[u]) * w00[u] + pair_hi(tp[u]) * w01[u] + pair_lo(bt[u]) * w10[u] + pair_hi(bt[u]) * w11[u]);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void flow_warp_p4_kernel(const float* __restrict__ x, long long xb,
                                                            const float* __restrict__ flow, long long fb,
                                                            float* __restrict__ out, long long ob, int nq, int H,
                                                            int W) {
     const int px = blockIdx.x * 64 + (threadIdx.x & 63);
     const int py = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int n = blockIdx.z;
     if (px >= W || py >= H) return;
-    const long long pix = (long long)py * W + px;
-    const float2 f = ldnt2(flow + (long long)n * fb + pix * 2);
-    const float dw = (float)(W - 1 > 1 ? W - 1 : 1), dh = (float)(H - 1 > 1 ? H - 1 : 1);
-    const float gx = 2.0f * ((float)px + f.x) / dw - 1.0f;
-    const float gy = 2.0f * ((float)py + f.y) / dh - 1.0f;
-    float ix = (gx + 1.0f) * ((float)(W - 1) / 2.0f);
-    float iy = (gy + 1.0f) * ((float)(H - 1) / 2.0f);
-    ix = fminf(fmaxf(ix, -1.0f), (float)W);
-    iy = fminf(fmaxf(iy, -1.0f), (float)H);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const float lx = ix - fx, ly = iy - fy, hx = 1.0f - lx, hy = 1.0f - ly;
-    const float w00 = hy * hx, w01 = hy * lx, w10 = ly * hx, w11 = ly * lx;
-    const int PW = W + 1, pitch = PW * QB, plane_b = (H + 1) * pitch;
-    // the descriptor starts one pad row + one element BEFORE plane 0 (zeroed guard that every P4
-    // allocation carries) so that (y0,x0) = (-1,-1) is still a non-negative offset
-    const int guard = pitch + QB;
-    const int voff = ((int)fy * PW + (int)fx) * QB + guard;
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-        (char*)const_cast<act_t*>(as_act(x) + (long long)n * xb) - guard, 0, nq * plane_b + guard, 0x00020000);
-    act_t* os = as_act(out) + (long long)n * ob + pix * 4;
-    const long long oplane = (long long)H * W * 4;
-    for (int q = 0; q < nq; ++q) {
-        const int vo = voff + q * plane_b;
-        const pairraw_t tp = bload_pair(r, vo, 0), bt = bload_pair(r, vo, pitch);
-        stq(os + q * oplane, pair_lo(tp) * w00 + pair_hi(tp) * w01 + pair_lo(bt) * w10 + pair_hi(bt) * w11);
-    }
+    flow_warp_p4_pixels<1>(x, xb, flow, fb, out, ob, nq, H, W, {(int)blockIdx.z}, {px}, {py}, {true});
 }
 
 // Two P4 tensors warped by the same flow field in one launch (the engine warps prev2 [8 quads] and the carried features

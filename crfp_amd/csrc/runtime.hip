@@ -39,6 +39,12 @@ bool prework_groups() { return g_prework_groups.load() != 0; }
 #else
 bool prework_groups() { return true; }
 #endif
+#ifdef CRFP_LAB
+static std::atomic<int> g_warp_tail_bands{kWarpTailBands};
+int warp_tail_bands() { return g_warp_tail_bands.load(); }
+#else
+int warp_tail_bands() { return kWarpTailBands; }
+#endif
 
 static hipEvent_t get_event() {
     if (!g_free_events.empty()) {
@@ -79,6 +85,9 @@ int crfp_version(void) { return CRFP_VERSION; }
 // frame per launch into two buffer sets, the order before round 25, so that tests can hold the two orders equal; returns the previous setting.
 // Not a header entry point: call it while no clip call is in flight.
 int crfp_lab_prework_groups(int on) { return g_prework_groups.exchange(on != 0); }
+// Lab library only, as above: the number of fused DCN launches of a frame that carry a row band of the 8x state warp (0 .. 3; 0 keeps the warp a
+// launch of its own, the schedule before the warp plan), for the tests that hold the schedules equal and for A/Bs; returns the previous setting.
+int crfp_lab_warp_tail_bands(int n) { return g_warp_tail_bands.exchange(n < 0 ? 0 : (n > 3 ? 3 : n)); }
 #endif
 
 const char* crfp_last_error_string(void) { return g_err; }

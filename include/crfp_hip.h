@@ -765,6 +765,37 @@ int crfp_narrow_probe_bf16(int mode, const crfp_narrow_stencil* a, const crfp_na
                            int w, const unsigned* status_in, unsigned* status_out, crfp_narrow_report* report, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- Test hook: the fused offset head + DCNv2 launch of a 2x level with the frame's 8x state warp in its idle last-round CUs
+ * (tests/test_gpu_dcn_fused_tail.py).  Not a product entry and no conversions: every pointer is a device buffer in the build's storage
+ * layout, bound as the clip engine binds it -- feat: the offset feature image (fp32 build: 8 planes [h][w] of 16-byte elements, 8 fp16 each;
+ * bf16 build: 8 planes of bf16 quads), wconv / bconv / wdcn / bdcn: the packed images of the head and of dcn_g8, x / warp_src: P4 planes
+ * ((h + 1) x (w + 1) quads, zero pad row and column, 8 and 1 of them) behind a zeroed guard of one pad row + one quad, flow [h][w][2],
+ * warp_flow [4h][4w][2], out / warp_dst: Q4, status: n words.  Strides between batch items in elements of each tensor's own type.
+ * bands = 0: the fused launch, then the stand-alone warp.  bands = k in 1..3: k fused launches, launch b carrying row band b of k of the
+ * warp -- unless the launch shape can take no plan (persistent form, full last round), which the report says (plan_taken = 0) and which
+ * then runs as bands = 0.  crfp_dcn_tail_plan fills the report on the host alone. */
+typedef struct crfp_dcn_tail_args {
+    const void *feat, *flow, *wconv, *bconv, *x, *wdcn, *bdcn;
+    void* out;
+    unsigned* status;
+    const void *warp_src, *warp_flow;
+    void* warp_dst;
+    long long feat_b, flow_b, x_b, out_b, warp_src_b, warp_flow_b, warp_dst_b;
+    int n, h, w, bands;
+} crfp_dcn_tail_args;
+typedef struct crfp_dcn_tail_report {
+    int cus;          /* CUs of the device, rounded down to a multiple of 8 */
+    int tiles;        /* 8 x 32-pixel tiles of the launch, all batch items */
+    int persistent;   /* the launch takes the persistent form (cus workgroups) */
+    int warp_wgs;     /* CUs the last round of the one-tile form leaves idle = workgroups of a warp plan; 0: no plan possible */
+    int plan_taken;   /* this call's fused launches carry the warp */
+    int grid;         /* workgroups of each fused launch */
+} crfp_dcn_tail_report;
+int crfp_dcn_tail_plan(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* report);
+int crfp_dcn_tail_probe(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* report, void* stream);
+int crfp_dcn_tail_plan_bf16(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* report);
+int crfp_dcn_tail_probe_bf16(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* report, void* stream);
+
 /* ---- The benchmark-only regional wiring, model/CRFP_runtime.py::MRCF_simple_v18.forward(lrs, fvs, warp_size) (:8469-8664;
  * built and timed by the reference's test_runtime.py:41,142) as ONE call per clip.  mid_channels = 32, split_ratio = 3, offset_prop.
  * Same conventions as the CRFP_DSV engine above: parameters as CRFP_RT_NUM_PARAMS device pointers in state_dict order

@@ -6,7 +6,9 @@
 #include <cstddef>
 
 static long g_launches = 0, g_streams = 0, g_events = 0;
+static dim3 g_last_grid, g_last_block;
 extern "C" long crfp_stub_launches(void) { return g_launches; }
+extern "C" long crfp_stub_last_grid(int axis) { return axis == 0 ? g_last_grid.x : (axis == 1 ? g_last_grid.y : (axis == 2 ? g_last_grid.z : g_last_block.x)); }   // 3: block x
 
 extern "C" {
 void** __hipRegisterFatBinary(const void*) { static void* h = nullptr; return &h; }
@@ -19,6 +21,7 @@ hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t shmem, hipStream_t 
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* shmem, hipStream_t* s) { *g = t_cfg.g; *b = t_cfg.b; *shmem = t_cfg.shmem; *s = t_cfg.s; return hipSuccess; }
 hipError_t hipLaunchKernel(const void*, dim3 g, dim3 b, void**, size_t, hipStream_t) {
     ++g_launches;
+    g_last_grid = g; g_last_block = b;
     // what the real runtime would refuse: an empty or oversized grid / block
     if (g.x == 0 || g.y == 0 || g.z == 0 || b.x * b.y * b.z == 0 || b.x * b.y * b.z > 1024 || g.y > 65535 || g.z > 65535) return hipErrorInvalidConfiguration;
     return hipSuccess;
@@ -26,6 +29,7 @@ hipError_t hipLaunchKernel(const void*, dim3 g, dim3 b, void**, size_t, hipStrea
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "stub HIP runtime"; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
+hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 256; return hipSuccess; }   // an MI355X's CU count; nothing else is read
 hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) { return hipSuccess; }
 hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) { return hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = reinterpret_cast<hipStream_t>(0x1000 + 16 * ++g_streams); return hipSuccess; }

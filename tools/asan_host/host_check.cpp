@@ -11,6 +11,7 @@
 #include <initializer_list>
 #include <cstdint>
 extern "C" long crfp_stub_launches(void);
+extern "C" long crfp_stub_last_grid(int axis);   // the last launch's grid x / y / z (0 .. 2) and block x (3)
 
 static int fails = 0;
 #define EXPECT(cond)                                                              \
@@ -984,6 +985,49 @@ int main() {
         EXPECT(crfp_shutdown() == 0);
         EXPECT(crfp_dsv_forward_clip(pk, 0, lrs, fvs, mks, out, 2, 20, 36, wsp, crfp_dsv_workspace_bytes(2, 20, 36), stream) == 0);   // and a fresh call after it
         std::printf("host_check: %ld launches enqueued on the stub runtime\n", crfp_stub_launches() - l0);
+    }
+    // ---- the fused DCN launch with a warp plan in its idle last-round CUs (crfp_dcn_tail_probe): the argument block and the grid sizing on the
+    // stub's 256 CUs -- fewer tiles than CUs, a multiple of the CUs (no plan: the stand-alone warp), one tile more than a multiple, the persistent form
+    {
+        crfp_dcn_tail_args a;
+        std::memset(&a, 0, sizeof(a));
+        crfp_dcn_tail_report r;
+        void* const p = reinterpret_cast<void*>(256);
+        a.feat = a.flow = a.wconv = a.bconv = a.x = a.wdcn = a.bdcn = a.warp_src = a.warp_flow = p;
+        a.out = a.warp_dst = p;
+        a.status = reinterpret_cast<unsigned*>(256);
+        struct Shape { int n, h, w, tiles, wgs, persistent; };
+        const Shape shapes[] = {{1, 20, 36, 6, 250, 0},    {1, 33, 47, 10, 246, 0},  {2, 33, 47, 20, 236, 0}, {1, 128, 544, 272, 240, 0}, {4, 64, 256, 256, 0, 0},
+                                {1, 64, 257, 72, 184, 0},  {4, 64, 288, 288, 224, 0}, {1, 8, 8192, 256, 0, 0}, {1, 8, 8192 + 32, 257, 255, 0},
+                                {1, 360, 640, 900, 124, 0}, {2, 360, 640, 1800, 0, 1}, {1, 384, 1024, 1536, 0, 1}, {1, 383, 1024, 1536, 0, 1}, {1, 376, 1024, 1504, 32, 0}};
+        for (const Shape& sh : shapes)
+            for (int bands = 0; bands <= 3; ++bands) {
+                a.n = sh.n; a.h = sh.h; a.w = sh.w; a.bands = bands;
+                EXPECT(crfp_dcn_tail_plan(&a, &r) == 0 && crfp_dcn_tail_plan_bf16(&a, &r) == 0);
+                EXPECT(r.cus == 256 && r.tiles == sh.tiles && r.warp_wgs == sh.wgs && r.persistent == sh.persistent);
+                const bool taken = bands > 0 && sh.wgs > 0;
+                EXPECT(r.plan_taken == taken && r.grid == (sh.persistent ? 256 : sh.tiles + (taken ? sh.wgs : 0)));
+                EXPECT(!taken || (r.tiles + r.warp_wgs) % 256 == 0);   // the plan's workgroups fill the last round exactly
+                for (int bf = 0; bf < 2; ++bf) {
+                    const long l0 = crfp_stub_launches();
+                    crfp_dcn_tail_report q;
+                    EXPECT((bf ? crfp_dcn_tail_probe_bf16 : crfp_dcn_tail_probe)(&a, &q, nullptr) == 0 && std::memcmp(&q, &r, sizeof(q)) == 0);
+                    EXPECT(crfp_stub_launches() == l0 + (taken ? bands : 2));   // k fused launches, or the fused launch and the stand-alone warp
+                    if (taken) EXPECT(crfp_stub_last_grid(0) == r.grid && crfp_stub_last_grid(1) == 1 && crfp_stub_last_grid(2) == 1 && crfp_stub_last_grid(3) == 512);
+                    else EXPECT(crfp_stub_last_grid(0) == (4 * sh.w + 63) / 64 && crfp_stub_last_grid(1) == sh.h && crfp_stub_last_grid(2) == sh.n);
+                }
+            }
+        // refusals, before any launch
+        const long l0 = crfp_stub_launches();
+        a.n = 1; a.h = 20; a.w = 36; a.bands = 4;
+        EXPECT(crfp_dcn_tail_plan(&a, &r) == CRFP_E_BADARG && crfp_dcn_tail_probe(&a, &r, nullptr) == CRFP_E_BADARG);
+        a.bands = 3; a.h = 0;
+        EXPECT(crfp_dcn_tail_probe_bf16(&a, &r, nullptr) == CRFP_E_BADARG);
+        a.h = 20; a.warp_dst = nullptr;
+        EXPECT(crfp_dcn_tail_probe(&a, &r, nullptr) == CRFP_E_BADARG && std::strstr(crfp_last_error_string(), "null tensor") != nullptr);
+        a.warp_dst = p;
+        EXPECT(crfp_dcn_tail_probe(&a, nullptr, nullptr) == CRFP_E_BADARG && crfp_dcn_tail_plan(nullptr, &r) == CRFP_E_BADARG);
+        EXPECT(crfp_stub_launches() == l0);
     }
     std::printf("host_check: %d parameters (dsv) / %d (cra) / %d (rt), %d failed expectations\n", np, nc, nr, fails);
     return fails ? 1 : 0;
