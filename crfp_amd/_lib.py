@@ -59,6 +59,20 @@ class DcnTailReport(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("cus", "tiles", "persistent", "warp_wgs", "plan_taken", "grid")]
 
 
+class GatherArgs(C.Structure):
+    """crfp_gather_args of include/crfp_hip.h: the NCHW fp32 tensors and the mode of a crfp_gather_probe call (test hook)."""
+    _fields_ = [(k, C.c_void_p) for k in ("x", "x2", "aux", "mask", "flow", "head_w", "head_b", "weight", "bias", "out", "out2", "out_raw", "out2_raw",
+                                          "status")] + [(k, C.c_int) for k in ("mode", "c", "n", "h", "w")]
+
+
+class GatherReport(C.Structure):
+    """crfp_gather_report: the kernel a gather launch took, how a fused DCN launch is sized, the strides of the raw destinations."""
+    _fields_ = [(k, C.c_int) for k in ("kernel", "cus", "tiles", "persistent", "split", "rsv")] + [(k, C.c_longlong) for k in ("out_stride", "out2_stride")]
+
+
+GATHER_MODES = {"warp": 0, "warp_dual": 1, "dcn_g8": 2, "dcn_fused": 3, "dcn3": 4, "dcn3_fused": 5}   # CRFP_GPROBE_*
+GATHER_KERNELS = ("none", "flow_warp_p4", "flow_warp_p4_dual_split", "flow_warp_p4_dual", "dcn_g8_pipe", "dcn_fused", "dcn_fused_persistent", "dcn3",
+                  "dcn3_fused")   # CRFP_GATHERK_*
 NARROW_KERNELS = ("none", "narrow", "seq", "pair", "chain")   # CRFP_NARROWK_*
 NARROW_MODES = {"single": 0, "pair": 1, "chain": 2}
 NARROW_EPI = {"plain": 0, "blend": 1, "last": 2, "offmask3": 3}
@@ -165,6 +179,9 @@ SIGNATURES = {
                              [C.POINTER(C.c_int)] * 3 + [C.c_void_p]),
     "crfp_dcn_tail_plan": (C.c_int, [C.POINTER(DcnTailArgs), C.POINTER(DcnTailReport)]),
     "crfp_dcn_tail_probe": (C.c_int, [C.POINTER(DcnTailArgs), C.POINTER(DcnTailReport), C.c_void_p]),
+    "crfp_gather_probe_workspace_bytes": (C.c_size_t, [C.POINTER(GatherArgs)]),
+    "crfp_gather_probe_plan": (C.c_int, [C.POINTER(GatherArgs), C.POINTER(GatherReport)]),
+    "crfp_gather_probe": (C.c_int, [C.POINTER(GatherArgs), C.POINTER(GatherReport), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 CRA_NUM_PARAMS = 144
 
@@ -224,7 +241,7 @@ for _n in ("workspace_bytes", "kernel", ""):
 for _n in ("workspace_bytes", "plan", ""):
     _n = "crfp_narrow_probe" + ("_" + _n if _n else "")
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
-for _n in ("crfp_dcn_tail_plan", "crfp_dcn_tail_probe"):
+for _n in ("crfp_dcn_tail_plan", "crfp_dcn_tail_probe", "crfp_gather_probe_workspace_bytes", "crfp_gather_probe_plan", "crfp_gather_probe"):
     SIGNATURES[_n + "_bf16"] = SIGNATURES[_n]
 
 _lib = None

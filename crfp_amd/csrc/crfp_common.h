@@ -84,6 +84,9 @@ int launch_upflow(const float* flow_q4, long long fb, float* out_nhw2, long long
                   hipStream_t s);
 int launch_fg_prep(const uint8_t* fg, float* fg2, int H8, int W8, hipStream_t s);
 int launch_q4_to_nchw(const float* x, float* out, int N, int C, int H, int W, int pad, hipStream_t s);
+// (the test hook gather_probe.hip: offsets and masks are float tensors in both builds)
+int launch_nchw_to_q4(const float* x, float* out, int N, int C, int H, int W, int pad, hipStream_t s, unsigned* ovf, int ovf_div);
+int launch_offmask_nchw_to_q4(const float* offset, const float* mask, float* out, int N, int noff, int nmask, int H, int W, hipStream_t s);
 }  // namespace crfp
 
 namespace CRFP_NS {
@@ -425,6 +428,8 @@ NarrowGrid narrow_chain_grid(const NarrowArgs& a);
 struct WarpDualStrides { long long xa = 0, xb = 0, flow = 0, outa = 0, outb = 0; };
 int launch_flow_warp_p4_dual_8_6(const float* xa, const float* xb, const float* flow, float* outa, float* outb, int H, int W,
                                  hipStream_t s, int N = 1, const WarpDualStrides& bs = WarpDualStrides());
+// the launcher's choice, for it and the test hook (gather_probe.hip): flow_warp_p4_dual_split_kernel while its grid's z axis holds N * 4 groups
+bool flow_warp_dual_split(int N);
 int launch_flow_warp_q4(const float* x, long long xb, const float* flow, long long fb, float* out, long long ob,
                         int N, int nq, int H, int W, int border, int src_pad, hipStream_t s);
 int launch_dcn_g8(const float* x, long long xb, const float* offmask, long long omb, const float* wpk,

@@ -251,13 +251,15 @@ __global__ __launch_bounds__(256) void flow_warp_p4_dual_split_kernel(const floa
     else if (GQ > 3 && cnt == 3) warp_quads<3>(r, voff, pitch, plane_b, w00, w01, w10, w11, os, oplane);
 }
 
+bool flow_warp_dual_split(int N) { return N * 4 <= 65535; }
+
 // prev2 (8 quads) + carry (6 quads) by flow2, one launch; zeros padding, P4 sources
 int launch_flow_warp_p4_dual_8_6(const float* xa, const float* xb, const float* flow, float* outa, float* outb, int H, int W,
                                  hipStream_t s, int N, const WarpDualStrides& bs) {
     const double px = (double)N * H * W;
     ProfScope prof("flow_warp_q4_c32+c24", s, px * (2.0 * 14 * 4 * sizeof(act_t) + 8), px * 14 * 4 * 7.0);
     const dim3 g4((W + 63) / 64, (H + 3) / 4, N);
-    if (N * 4 <= 65535) flow_warp_p4_dual_split_kernel<8, 6, 4><<<dim3(g4.x, g4.y, N * 4), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
+    if (flow_warp_dual_split(N)) flow_warp_p4_dual_split_kernel<8, 6, 4><<<dim3(g4.x, g4.y, N * 4), 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
     else flow_warp_p4_dual_kernel<8, 6, 4><<<g4, 256, 0, s>>>(xa, xb, flow, outa, outb, H, W, bs);
     CRFP_CHECK_LAUNCH();
     return 0;

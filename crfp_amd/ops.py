@@ -751,3 +751,75 @@ def narrow_probe(a, b=None, c=None, mode="single", storage="f32", res=False, sta
     if raw:
         result["raw"], result["raw2"] = rw, rw2
     return result
+
+
+def _gather_report(r):
+    return {"kernel": _lib.GATHER_KERNELS[r.kernel], "cus": r.cus, "tiles": r.tiles, "persistent": bool(r.persistent), "split": bool(r.split),
+            "out_stride": r.out_stride, "out2_stride": r.out2_stride}
+
+
+def gather_probe_plan(mode, n, h, w, c=32, storage="f32"):
+    """crfp_gather_probe_plan: what gather_probe would report for an [n, ., h, w] launch of `mode`, on the host alone (the fused DCN launch asks
+    the current device for its CU count)."""
+    import ctypes as C
+    L = _lib.lib()
+    sfx = "_bf16" if storage == "bf16" else ""
+    a = _lib.GatherArgs(mode=_lib.GATHER_MODES[mode], c=c, n=n, h=h, w=w)
+    rep = _lib.GatherReport()
+    _lib.check(getattr(L, "crfp_gather_probe_plan" + sfx)(C.byref(a), C.byref(rep)), "crfp_gather_probe_plan" + sfx)
+    return _gather_report(rep)
+
+
+def gather_probe(mode, x, storage="f32", raw=False, x2=None, aux=None, mask=None, flow=None, head_w=None, head_b=None, weight=None, bias=None):
+    """Test hook (crfp_gather_probe / crfp_gather_probe_bf16): one launch of the engines' own gather kernels on the caller's NCHW fp32 tensors.
+
+    mode "warp" (x [n, 4 | 24 | 32, h, w], flow [n, h, w, 2]), "warp_dual" (x 32 and x2 24 channels, one flow), "dcn_g8" (x 32, aux = offsets
+    [n, 144, h, w], mask [n, 72, h, w], weight, bias), "dcn_fused" (aux = the offset feature [n, 32, h, w], flow, head_w [216, 32, 3, 3], head_b,
+    weight, bias), "dcn3" (x 4, aux [n, 3, h, w] = (dy, dx, mask), weight [4, 4, 3, 3], bias) or "dcn3_fused" (aux = the head's input [n, 4, h, w],
+    flow, head_w [3, 4, 3, 3], head_b, weight, bias).  Returns a dict: ``out`` (NCHW fp32; elements no lane wrote are NaN), ``out2`` (warp_dual),
+    ``status`` (int32 [n]: the range-guard word of every batch item), ``report`` (the kernel taken, the fused launch's sizing, the raw strides),
+    and with raw=True ``raw`` / ``raw2``: the destinations' raw bytes as uint8 [n, stride in bytes], an item's map first, then its slack."""
+    import ctypes as C
+    L = _lib.lib()
+    sfx = "_bf16" if storage == "bf16" else ""
+    eb = 2 if storage == "bf16" else 4
+    x = _dev(x, "x")
+    n, c, h, w = x.shape
+    dev = x.device
+    keep = [x]
+
+    def ptr(t, name):
+        if t is None:
+            return None
+        t = _dev(t, name)
+        keep.append(t)
+        return t.data_ptr()
+
+    a = _lib.GatherArgs(mode=_lib.GATHER_MODES[mode], c=c, n=n, h=h, w=w, x=x.data_ptr(), x2=ptr(x2, "x2"), aux=ptr(aux, "aux"), mask=ptr(mask, "mask"),
+                        flow=ptr(flow, "flow"), head_w=ptr(head_w, "head_w"), head_b=ptr(head_b, "head_b"), weight=ptr(weight, "weight"),
+                        bias=ptr(bias, "bias"))
+    with _on(*keep):
+        plan = _lib.GatherReport()
+        _lib.check(getattr(L, "crfp_gather_probe_plan" + sfx)(C.byref(a), C.byref(plan)), "crfp_gather_probe_plan" + sfx)
+        out = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+        out2 = torch.empty((n, 24, h, w), dtype=torch.float32, device=dev) if mode == "warp_dual" else None
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        a.out, a.out2, a.status = out.data_ptr(), None if out2 is None else out2.data_ptr(), status.data_ptr()
+        rw = rw2 = None
+        if raw:
+            rw = torch.empty((n, plan.out_stride * eb), dtype=torch.uint8, device=dev)
+            a.out_raw = rw.data_ptr()
+            if out2 is not None:
+                rw2 = torch.empty((n, plan.out2_stride * eb), dtype=torch.uint8, device=dev)
+                a.out2_raw = rw2.data_ptr()
+        nb = getattr(L, "crfp_gather_probe_workspace_bytes" + sfx)(C.byref(a))
+        if nb == 0:
+            _lib.check(-1, "crfp_gather_probe_workspace_bytes" + sfx)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        rep = _lib.GatherReport()
+        _lib.check(getattr(L, "crfp_gather_probe" + sfx)(C.byref(a), C.byref(rep), ws.data_ptr(), nb, _stream()), "crfp_gather_probe" + sfx)
+        torch.cuda.current_stream().synchronize()   # the workspace goes away with this call
+    result = {"out": out, "out2": out2, "status": status, "report": _gather_report(rep)}
+    if raw:
+        result["raw"], result["raw2"] = rw, rw2
+    return result

@@ -796,6 +796,65 @@ int crfp_dcn_tail_probe(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* re
 int crfp_dcn_tail_plan_bf16(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* report);
 int crfp_dcn_tail_probe_bf16(const crfp_dcn_tail_args* args, crfp_dcn_tail_report* report, void* stream);
 
+/* ---- Test hook: ONE launch of the engines' own gather kernels (csrc/gather.hip, dcn_fused.inc) on caller-supplied tensors
+ * (tests/test_gpu_gather_probe.py).  Not a product entry: every call converts the API tensors (contiguous NCHW fp32 device memory; flow
+ * [n, h, w, 2] (dx, dy)) to the build's storage layouts with the library's own conversions, packs the weight images as the engines' pack loop
+ * does, binds the launch arguments as the clip engine binds them, launches once, converts back and reports the kernel taken.  Every sampled
+ * tensor sits in padded planes ((h + 1) x (w + 1) quads) behind a zeroed guard; every tensor has a batch stride of its own with slack between
+ * the items (zero for sources); every destination, its slack included, is filled with 0xFF bytes before the launch.
+ *   mode CRFP_GPROBE_WARP:       out [n, c, h, w] = flow_warp(x [n, c, h, w], flow), zeros padding; c in {4, 24, 32}
+ *        CRFP_GPROBE_WARP_DUAL:  out [n, 32, h, w], out2 [n, 24, h, w] = flow_warp of x (32) and x2 (24) by one flow field
+ *        CRFP_GPROBE_DCN_G8:     out [n, 32, h, w] = DCNv2(x (32), offset = aux [n, 144, h, w] (flow already added), mask [n, 72, h, w], weight
+ *                                [32, 32, 3, 3], bias [32]), 8 deformable groups, on the split-fp16 weight image
+ *        CRFP_GPROBE_DCN_FUSED:  the same with the offset / mask head inside: aux = the offset feature [n, 32, h, w], head_w [216, 32, 3, 3]
+ *                                (rows 0..143 offsets (dy, dx), 144..215 masks), head_b [216]; offsets = 10 tanh + flow (y, x), masks = sigmoid.
+ *                                fp32 build: the offset feature reaches the launch as the split-fp16 pair image a centre-tap identity conv
+ *                                writes (x to the 22 bits of the pair); bf16 build: as bf16 quads
+ *        CRFP_GPROBE_DCN3:       out [n, 4, h, w] = DCNv2 4 -> 4, one group, aux [n, 3, h, w] = (dy, dx, mask) shared by the 9 taps (flow
+ *                                already added), weight [4, 4, 3, 3], bias [4]
+ *        CRFP_GPROBE_DCN3_FUSED: the same with its 4 -> 3 head inside: aux = the head's input [n, 4, h, w], head_w [3, 4, 3, 3], head_b [3]
+ *   out_raw / out2_raw (optional): the raw destination buffers, n * stride elements of the storage type (crfp_gather_report.out_stride /
+ *   out2_stride; an item's map is its first elements), slack and the guard behind the last item included.
+ *   status (device, n words): the range-guard words after the launch, batch item k raises word k (DCN_G8, DCN_FUSED; zero otherwise).
+ * Refused: n outside 1 .. 65535, planes of (h + 1)(w + 1) >= 2^22 elements (the hook's own limit), and DCN_G8 / DCN_FUSED under CRFP_PRECISION=f32.
+ * crfp_gather_probe_plan fills the report on the host alone (no launch, tensor pointers ignored). */
+#define CRFP_GPROBE_WARP 0
+#define CRFP_GPROBE_WARP_DUAL 1
+#define CRFP_GPROBE_DCN_G8 2
+#define CRFP_GPROBE_DCN_FUSED 3
+#define CRFP_GPROBE_DCN3 4
+#define CRFP_GPROBE_DCN3_FUSED 5
+#define CRFP_GATHERK_NONE 0
+#define CRFP_GATHERK_WARP_P4 1         /* flow_warp_p4_kernel */
+#define CRFP_GATHERK_WARP_DUAL_SPLIT 2 /* flow_warp_p4_dual_split_kernel<8, 6, 4> */
+#define CRFP_GATHERK_WARP_DUAL 3       /* flow_warp_p4_dual_kernel<8, 6, 4> */
+#define CRFP_GATHERK_DCN_G8_PIPE 4     /* dcn_g8_pipe_kernel */
+#define CRFP_GATHERK_DCN_FUSED 5       /* dcn_fused_kernel<8> */
+#define CRFP_GATHERK_DCN_FUSED_PS 6    /* dcn_fused_kernel<8, true> */
+#define CRFP_GATHERK_DCN3 7            /* dcn3_kernel<false> */
+#define CRFP_GATHERK_DCN3_FUSED 8      /* dcn3_kernel<true> */
+typedef struct crfp_gather_args {
+    const float *x, *x2, *aux, *mask, *flow;
+    const float *head_w, *head_b, *weight, *bias;
+    float *out, *out2;
+    void *out_raw, *out2_raw;
+    unsigned* status;
+    int mode, c, n, h, w;
+} crfp_gather_args;
+typedef struct crfp_gather_report {
+    int kernel;                     /* CRFP_GATHERK_* */
+    int cus, tiles, persistent;     /* DCN_FUSED: dcn_fused_grid of the launch */
+    int split;                      /* WARP_DUAL: the quads of a pixel are split over workgroups */
+    int rsv;
+    long long out_stride, out2_stride;   /* elements of the storage type between the batch items of the raw destinations */
+} crfp_gather_report;
+size_t crfp_gather_probe_workspace_bytes(const crfp_gather_args* args);   /* 0: refused (crfp_last_error) */
+int crfp_gather_probe_plan(const crfp_gather_args* args, crfp_gather_report* report);
+int crfp_gather_probe(const crfp_gather_args* args, crfp_gather_report* report, void* workspace, size_t workspace_bytes, void* stream);
+size_t crfp_gather_probe_workspace_bytes_bf16(const crfp_gather_args* args);
+int crfp_gather_probe_plan_bf16(const crfp_gather_args* args, crfp_gather_report* report);
+int crfp_gather_probe_bf16(const crfp_gather_args* args, crfp_gather_report* report, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- The benchmark-only regional wiring, model/CRFP_runtime.py::MRCF_simple_v18.forward(lrs, fvs, warp_size) (:8469-8664;
  * built and timed by the reference's test_runtime.py:41,142) as ONE call per clip.  mid_channels = 32, split_ratio = 3, offset_prop.
  * Same conventions as the CRFP_DSV engine above: parameters as CRFP_RT_NUM_PARAMS device pointers in state_dict order

@@ -19,7 +19,41 @@ static int fails = 0;
         if (!(cond)) { std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); ++fails; } \
     } while (0)
 
-int main() {
+// `host_check precision`: the process runs with CRFP_PRECISION=f32 (the library reads the switch once per process, so it has to be there before the
+// first call) and walks what the test hooks refuse under it: crfp_gather_probe has no dcn_g8 / dcn_fused launch to reach without the split-fp16 kernels
+static int precision_refusals() {
+    setenv("CRFP_PRECISION", "f32", 1);
+    crfp_gather_args a;
+    std::memset(&a, 0, sizeof(a));
+    crfp_gather_report r;
+    float* const p = reinterpret_cast<float*>(256);
+    void* const wsp = reinterpret_cast<char*>(1ull << 40);
+    a.x = a.x2 = a.aux = a.mask = a.flow = a.head_w = a.head_b = a.weight = a.bias = p;
+    a.out = a.out2 = p;
+    a.status = reinterpret_cast<unsigned*>(256);
+    a.c = 32; a.n = 3; a.h = 9; a.w = 33;
+    const long l0 = crfp_stub_launches();
+    const struct { int mode; const char* text; } rows[] = {{CRFP_GPROBE_DCN_G8, "the engines' dcn_g8 runs on the split-fp16 image (no CRFP_PRECISION override)"},
+                                                           {CRFP_GPROBE_DCN_FUSED, "the fused DCN launch needs the default conv / DCN kernels (no CRFP_PRECISION override)"}};
+    for (const auto& row : rows) {
+        a.mode = row.mode;
+        EXPECT(crfp_gather_probe_workspace_bytes(&a) == 0 && std::strstr(crfp_last_error_string(), row.text) != nullptr);
+        EXPECT(crfp_gather_probe_workspace_bytes_bf16(&a) == 0 && std::strstr(crfp_last_error_string(), row.text) != nullptr);
+        EXPECT(crfp_gather_probe_plan(&a, &r) == CRFP_E_UNSUPPORTED && crfp_gather_probe_plan_bf16(&a, &r) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_gather_probe(&a, &r, wsp, 1 << 20, nullptr) == CRFP_E_UNSUPPORTED && crfp_gather_probe_bf16(&a, &r, wsp, 1 << 20, nullptr) == CRFP_E_UNSUPPORTED);
+    }
+    EXPECT(crfp_stub_launches() == l0);
+    for (int mode : {CRFP_GPROBE_WARP, CRFP_GPROBE_WARP_DUAL, CRFP_GPROBE_DCN3, CRFP_GPROBE_DCN3_FUSED}) {   // the other modes do not depend on the switch
+        a.mode = mode;
+        const size_t bytes = crfp_gather_probe_workspace_bytes(&a), bytes16 = crfp_gather_probe_workspace_bytes_bf16(&a);
+        EXPECT(bytes > 0 && bytes16 > 0 && crfp_gather_probe(&a, &r, wsp, bytes, nullptr) == 0 && crfp_gather_probe_bf16(&a, &r, wsp, bytes16, nullptr) == 0);
+    }
+    std::printf("host_check precision: %d failed expectations\n", fails);
+    return fails ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "precision")) return precision_refusals();
     EXPECT(crfp_version() > 0);
     // ---- sizes (test_sizes_are_sane) over geometries incl. ragged and degenerate ones
     const size_t pw = crfp_dsv_packed_weight_bytes(0);
@@ -1028,6 +1062,88 @@ int main() {
         a.warp_dst = p;
         EXPECT(crfp_dcn_tail_probe(&a, nullptr, nullptr) == CRFP_E_BADARG && crfp_dcn_tail_plan(nullptr, &r) == CRFP_E_BADARG);
         EXPECT(crfp_stub_launches() == l0);
+    }
+    // ---- one gather launch at a time (crfp_gather_probe): every mode in both builds on the stub runtime -- the workspace layout, the plan items
+    // and the launch arguments under the sanitizers -- the report on the stub's 256 CUs, and the refusals, which come before any launch
+    {
+        crfp_gather_args a;
+        std::memset(&a, 0, sizeof(a));
+        crfp_gather_report r, q;
+        float* const p = reinterpret_cast<float*>(256);
+        void* const wsp = reinterpret_cast<char*>(1ull << 40);
+        a.x = a.x2 = a.aux = a.mask = a.flow = a.head_w = a.head_b = a.weight = a.bias = p;
+        a.out = a.out2 = p;
+        a.status = reinterpret_cast<unsigned*>(256);
+        static const int kernels[6] = {CRFP_GATHERK_WARP_P4, CRFP_GATHERK_WARP_DUAL_SPLIT, CRFP_GATHERK_DCN_G8_PIPE, CRFP_GATHERK_DCN_FUSED, CRFP_GATHERK_DCN3,
+                                       CRFP_GATHERK_DCN3_FUSED};
+        for (int mode = CRFP_GPROBE_WARP; mode <= CRFP_GPROBE_DCN3_FUSED; ++mode)
+            for (int bf = 0; bf < 2; ++bf) {
+                a.mode = mode; a.c = 24; a.n = 3; a.h = 9; a.w = 33;
+                const size_t bytes = (bf ? crfp_gather_probe_workspace_bytes_bf16 : crfp_gather_probe_workspace_bytes)(&a);
+                EXPECT(bytes > 0);
+                EXPECT((bf ? crfp_gather_probe_plan_bf16 : crfp_gather_probe_plan)(&a, &r) == 0 && r.kernel == kernels[mode]);
+                EXPECT(r.out_stride > (mode == CRFP_GPROBE_WARP ? 24 : (mode >= CRFP_GPROBE_DCN3 ? 4 : 32)) * 9 * 33 && (mode == CRFP_GPROBE_WARP_DUAL) == (r.out2_stride > 0));
+                if (mode == CRFP_GPROBE_DCN_FUSED) EXPECT(r.cus == 256 && r.tiles == 3 * 2 * 2 && !r.persistent);
+                const long l0 = crfp_stub_launches();
+                EXPECT((bf ? crfp_gather_probe_bf16 : crfp_gather_probe)(&a, &q, wsp, bytes, nullptr) == 0 && std::memcmp(&q, &r, sizeof(q)) == 0);
+                EXPECT(crfp_stub_launches() > l0);
+                EXPECT((bf ? crfp_gather_probe_bf16 : crfp_gather_probe)(&a, &q, wsp, bytes - 1, nullptr) == CRFP_E_WORKSPACE);
+                EXPECT((bf ? crfp_gather_probe_bf16 : crfp_gather_probe)(&a, &q, nullptr, bytes, nullptr) == CRFP_E_WORKSPACE);
+            }
+        // the launchers' own choices: the unsplit dual warp past 65 535 z groups, the persistent fused form from 6 rounds of the chip
+        a.mode = CRFP_GPROBE_WARP_DUAL; a.n = 16384; a.h = 1; a.w = 2;
+        EXPECT(crfp_gather_probe_plan(&a, &r) == 0 && r.kernel == CRFP_GATHERK_WARP_DUAL && !r.split);
+        a.n = 16383;
+        EXPECT(crfp_gather_probe_plan_bf16(&a, &r) == 0 && r.kernel == CRFP_GATHERK_WARP_DUAL_SPLIT && r.split);
+        a.mode = CRFP_GPROBE_DCN_FUSED; a.n = 1537; a.h = 3; a.w = 5;
+        EXPECT(crfp_gather_probe_plan(&a, &r) == 0 && r.kernel == CRFP_GATHERK_DCN_FUSED_PS && r.persistent && r.tiles == 1537);
+        a.n = 1535;
+        EXPECT(crfp_gather_probe_plan_bf16(&a, &r) == 0 && r.kernel == CRFP_GATHERK_DCN_FUSED && !r.persistent);
+        // refusals
+        const long l0 = crfp_stub_launches();
+        auto refused = [&](int rc, const char* text) {
+            const bool f32 = crfp_gather_probe_workspace_bytes(&a) == 0 && std::strstr(crfp_last_error_string(), text) != nullptr && crfp_gather_probe_plan(&a, &r) == rc;
+            const bool b16 = crfp_gather_probe_workspace_bytes_bf16(&a) == 0 && std::strstr(crfp_last_error_string(), text) != nullptr && crfp_gather_probe_plan_bf16(&a, &r) == rc;
+            return f32 && b16 && crfp_gather_probe(&a, &r, wsp, 1 << 20, nullptr) == rc && crfp_gather_probe_bf16(&a, &r, wsp, 1 << 20, nullptr) == rc;
+        };
+        a.n = 3; a.h = 9; a.w = 33;
+        a.mode = 6;
+        EXPECT(refused(CRFP_E_BADARG, "unknown mode 6"));
+        a.mode = CRFP_GPROBE_WARP; a.c = 8;
+        EXPECT(refused(CRFP_E_BADARG, "a warp takes 4, 24 or 32 channels"));
+        a.c = 4; a.n = 0;
+        EXPECT(refused(CRFP_E_BADARG, "bad geometry (n=0 h=9 w=33)"));
+        a.n = 65536;
+        EXPECT(refused(CRFP_E_BADARG, "bad geometry"));
+        a.n = 1; a.w = 0;
+        EXPECT(refused(CRFP_E_BADARG, "bad geometry"));
+        a.h = 2047; a.w = 2047;
+        EXPECT(refused(CRFP_E_UNSUPPORTED, "plane of 2047 x 2047 exceeds the hook's 2^22-element range"));
+        a.mode = CRFP_GPROBE_DCN_G8;
+        EXPECT(refused(CRFP_E_UNSUPPORTED, "plane of 2047 x 2047 exceeds the hook's 2^22-element range"));
+        a.h = 2047; a.w = 2046; a.n = 1;   // just inside: sized, never launched here
+        EXPECT(crfp_gather_probe_workspace_bytes(&a) > 0 && crfp_gather_probe_plan_bf16(&a, &r) == 0);
+        a.n = 3;
+        a.h = 9; a.w = 33;
+        EXPECT(crfp_gather_probe_workspace_bytes(nullptr) == 0 && crfp_gather_probe_plan_bf16(nullptr, &r) == CRFP_E_BADARG && crfp_gather_probe_plan(&a, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_gather_probe(&a, nullptr, wsp, 1 << 20, nullptr) == CRFP_E_BADARG);
+        // null tensors, per mode: what the mode reads, and nothing it does not
+        struct Null { int mode; const float** field; const char* text; };
+        const Null nulls[] = {{CRFP_GPROBE_WARP, &a.x, "null tensor"}, {CRFP_GPROBE_WARP, &a.flow, "null tensor"}, {CRFP_GPROBE_WARP_DUAL, &a.x2, "null tensor"},
+                              {CRFP_GPROBE_DCN_G8, &a.aux, "null tensor"}, {CRFP_GPROBE_DCN_G8, &a.mask, "null tensor"}, {CRFP_GPROBE_DCN_G8, &a.weight, "null weight or bias"},
+                              {CRFP_GPROBE_DCN_FUSED, &a.flow, "null tensor"}, {CRFP_GPROBE_DCN_FUSED, &a.head_w, "null head weight or bias"},
+                              {CRFP_GPROBE_DCN3, &a.bias, "null weight or bias"}, {CRFP_GPROBE_DCN3_FUSED, &a.head_b, "null head weight or bias"}};
+        for (const Null& z : nulls) {
+            a.mode = z.mode;
+            *z.field = nullptr;
+            const size_t bytes = crfp_gather_probe_workspace_bytes(&a);   // sizes do not ask for tensors
+            EXPECT(bytes > 0 && crfp_gather_probe(&a, &r, wsp, bytes, nullptr) == CRFP_E_BADARG && std::strstr(crfp_last_error_string(), z.text) != nullptr);
+            EXPECT(crfp_gather_probe_bf16(&a, &r, wsp, bytes, nullptr) == CRFP_E_BADARG);
+            *z.field = p;
+        }
+        a.mode = CRFP_GPROBE_DCN3; a.mask = a.flow = a.head_w = a.x2 = nullptr;   // ... dcn3 reads none of these
+        EXPECT(crfp_stub_launches() == l0);
+        EXPECT(crfp_gather_probe(&a, &r, wsp, crfp_gather_probe_workspace_bytes(&a), nullptr) == 0 && crfp_stub_launches() > l0);
     }
     std::printf("host_check: %d parameters (dsv) / %d (cra) / %d (rt), %d failed expectations\n", np, nc, nr, fails);
     return fails ? 1 : 0;
