@@ -1,6 +1,7 @@
 // Per-operator C-ABI entry points (NCHW tensors as the reference's Python operators pass them).
 #include "crfp_common.h"
 
+#include <cmath>
 #include <cstring>
 
 using namespace crfp;
@@ -471,6 +472,52 @@ int crfp_upsample_bilinear_f32(const float* x, float* out, int n, int c, int h, 
 int crfp_avgpool2_f32(const float* x, float* out, int n, int c, int h, int w, void* stream) {
     if (!x || !out || n < 1 || c < 1 || h < 2 || w < 2) { set_error("avgpool2: bad argument"); return CRFP_E_BADARG; }
     return launch_avgpool2_nchw(x, out, n, c, h, w, (hipStream_t)stream);
+}
+
+// ---- the backward passes of the resize and the pool, and the Charbonnier loss (train_backward.hip); every refusal before any HIP call
+int crfp_upsample_bilinear_backward_f32(const float* grad_out, float* grad_x, int n, int c, int h, int w, int oh, int ow, float scale_h,
+                                        float scale_w, float mul, void* stream) {
+    if (!grad_out || !grad_x || n < 1 || c < 1 || h < 1 || w < 1 || oh < 1 || ow < 1) { set_error("upsample_backward: bad argument"); return CRFP_E_BADARG; }
+    if (!(scale_h > 0.0f && scale_w > 0.0f && std::isfinite(scale_h) && std::isfinite(scale_w))) {
+        set_error("upsample_backward: the source-index scales must be positive and finite");
+        return CRFP_E_BADARG;
+    }
+    if (!train_backward_plane_shape_ok(n, c, h, w, oh, ow)) { set_error("upsample_backward: n * c > 65535, h > 262140 or more than 2^58 elements"); return CRFP_E_UNSUPPORTED; }
+    return launch_upsample_bilinear_backward(grad_out, grad_x, n, c, h, w, oh, ow, scale_h, scale_w, mul, (hipStream_t)stream);
+}
+
+int crfp_avgpool2_backward_f32(const float* grad_out, float* grad_x, int n, int c, int h, int w, void* stream) {
+    if (!grad_out || !grad_x || n < 1 || c < 1 || h < 2 || w < 2) { set_error("avgpool2_backward: bad argument"); return CRFP_E_BADARG; }
+    if (!train_backward_plane_shape_ok(n, c, h, w, h / 2, w / 2)) { set_error("avgpool2_backward: n * c > 65535, h > 262140 or more than 2^58 elements"); return CRFP_E_UNSUPPORTED; }
+    return launch_avgpool2_backward(grad_out, grad_x, n, c, h, w, (hipStream_t)stream);
+}
+
+static int charbonnier_domain(const char* who, int n, int c, int h, int w, const float* weight, int weight_c, float eps) {
+    if (n < 1 || c < 1 || h < 1 || w < 1) { set_error("%s: bad argument (need n, c, h, w >= 1)", who); return CRFP_E_BADARG; }
+    if (weight ? (weight_c != 1 && weight_c != c) : weight_c != 0) { set_error("%s: weight_c %d (0 with a null weight, else 1 or c = %d)", who, weight_c, c); return CRFP_E_BADARG; }
+    if (!(eps >= 0.0f) || !std::isfinite(eps)) { set_error("%s: eps must be finite and >= 0", who); return CRFP_E_BADARG; }
+    if (n > 65535 || (long long)h * w > (1LL << 58) / ((long long)n * c)) { set_error("%s: n > 65535 or more than 2^58 elements", who); return CRFP_E_UNSUPPORTED; }
+    return 0;
+}
+
+size_t crfp_charbonnier_workspace_bytes(int n, int c, int h, int w) {
+    if (n < 1 || c < 1 || h < 1 || w < 1 || n > 65535 || (long long)h * w > (1LL << 58) / ((long long)n * c)) return 0;
+    return charbonnier_workspace_bytes(n, c, h, w);
+}
+
+int crfp_charbonnier_f32(const float* pred, const float* target, const float* weight, int weight_c, double* sums, int n, int c, int h, int w,
+                         float eps, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pred || !target || !sums) { set_error("charbonnier: null pointer"); return CRFP_E_BADARG; }
+    if (const int rc = charbonnier_domain("charbonnier", n, c, h, w, weight, weight_c, eps)) return rc;
+    if (!workspace || workspace_bytes < charbonnier_workspace_bytes(n, c, h, w)) { set_error("charbonnier: workspace too small"); return CRFP_E_WORKSPACE; }
+    return launch_charbonnier(pred, target, weight, weight_c, sums, n, c, h, w, eps, workspace, (hipStream_t)stream);
+}
+
+int crfp_charbonnier_backward_f32(const float* pred, const float* target, const float* weight, int weight_c, const float* scale,
+                                  float* grad_pred, int n, int c, int h, int w, float eps, void* stream) {
+    if (!pred || !target || !scale || !grad_pred) { set_error("charbonnier_backward: null pointer"); return CRFP_E_BADARG; }
+    if (const int rc = charbonnier_domain("charbonnier_backward", n, c, h, w, weight, weight_c, eps)) return rc;
+    return launch_charbonnier_backward(pred, target, weight, weight_c, scale, grad_pred, n, c, h, w, eps, (hipStream_t)stream);
 }
 
 // fused a-15: conv_tttf on [state | x_hr], fovea blend, LeakyReLU -> new state; conv_last + bilinear x8 base -> frame

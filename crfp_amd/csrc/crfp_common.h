@@ -558,6 +558,16 @@ size_t conv3x3_backward_workspace_bytes(int n, int cin_t, int cout, int h, int w
 int launch_conv3x3_backward(const float* x, int cin, const float* x2, int cin2, const float* weight, const float* out, const float* go, float* gx,
                             float* gx2, float* gw, float* gb, int N, int cout, int H, int W, int act, float post_scale, int unshuffle_r,
                             int shuffle_r, void* workspace, hipStream_t s);
+// train_backward.hip (fp32 build only): the resize and pool backward and the Charbonnier loss; gradients bitwise reproducible
+bool train_backward_plane_shape_ok(int n, int c, int h, int w, int oh, int ow);   // what the plane kernels' grids and indices take
+int launch_upsample_bilinear_backward(const float* go, float* gx, int N, int C, int H, int W, int OH, int OW, float sh, float sw, float mul,
+                                      hipStream_t s);
+int launch_avgpool2_backward(const float* go, float* gx, int N, int C, int H, int W, hipStream_t s);
+size_t charbonnier_workspace_bytes(int n, int c, int h, int w);
+int launch_charbonnier(const float* pred, const float* target, const float* wgt, int wc, double* sums, int N, int C, int H, int W, float eps,
+                       void* workspace, hipStream_t s);
+int launch_charbonnier_backward(const float* pred, const float* target, const float* wgt, int wc, const float* scale, float* gp, int N, int C,
+                                int H, int W, float eps, hipStream_t s);
 #endif
 
 }  // namespace CRFP_NS

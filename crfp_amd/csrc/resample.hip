@@ -4,20 +4,11 @@
 // AvgPool2d(2,2) (:755,762,769), the x8 LR upsample + fovea blend in front of encoder_hr
 // (:1538,1542-1547) and the squared-error reduction behind PSNR (utils.py:166-185,328-330).
 #include "crfp_common.h"
+#include "resample_index.h"
 
 namespace CRFP_NS {
 
-// PyTorch's source index for align_corners=False (area_pixel_compute_source_index + guard):
-//   src = scale*(dst+0.5)-0.5, clamped at 0; i0 = min(floor(src), in-1); i1 = min(i0+1, in-1);
-//   l1 = clamp(src - i0, 0, 1); l0 = 1 - l1
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.0f) src = 0.0f;
-    i0 = min((int)floorf(src), in_size - 1);
-    i1 = min(i0 + 1, in_size - 1);
-    l1 = fminf(fmaxf(src - (float)i0, 0.0f), 1.0f);
-    l0 = 1.0f - l1;
-}
+using crfp_index::src_index;   // PyTorch's source index for align_corners=False (shared with the resize backward)
 
 // pad = 1: destination / source planes are (H+1) x (W+1) ("P4"); pads are not touched here
 __global__ void nchw_to_q4_kernel(const float* __restrict__ x, act_t* __restrict__ out, int C, int H, int W, int pad, unsigned* __restrict__ ovf,

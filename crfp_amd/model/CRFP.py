@@ -6,10 +6,11 @@ ResidualBlockNoBN :433, ResidualBlocksWithInputConv :516, FNet :743, CRFP_DSV :1
 checkpoints load with ``strict=True`` and ``main.py:34`` / ``trainer.py:318`` call it unchanged.
 The modules only *hold parameters*; all arithmetic runs in the HIP library: ``CRFP_DSV.forward`` is
 one C-ABI call per clip (crfp_amd.engine.DSVEngine), the smaller modules call per-operator entry
-points.  CUDA/HIP tensors only.  The engines and the model classes' ``forward`` are inference only; the
-smaller modules built on ``ops.conv3x3`` / ``ops.conv3x3_ex`` / ``ops.dcnv2*`` / ``ops.flow_warp`` (DCN_module,
-ResidualBlockNoBN, ResidualBlocksWithInputConv, PixelShufflePack, PixelUnShufflePack_v2) are differentiable
-through those operators' HIP backward passes (first order, fp32).
+points.  CUDA/HIP tensors only.  The engines are inference only; the smaller modules built on ``ops.conv3x3`` /
+``ops.conv3x3_ex`` / ``ops.dcnv2*`` / ``ops.flow_warp`` / ``ops.upsample_bilinear`` / ``ops.avgpool2`` (DCN_module,
+ResidualBlockNoBN, ResidualBlocksWithInputConv, PixelShufflePack, PixelUnShufflePack_v2, FNet, the LTE encoders) are
+differentiable through those operators' HIP backward passes (first order, fp32), and ``CRFP_DSV.forward_train`` runs
+the whole recurrence on them with the graph kept (``trainable = True`` routes ``forward`` there under grad mode).
 """
 import torch
 import torch.nn as nn
@@ -185,8 +186,10 @@ class FNet(nn.Module):
         self.flow = nn.Sequential(nn.Conv2d(64, 32, 3, 1, 1, bias=True), nn.ReLU(inplace=True),
                                   nn.Conv2d(32, 2, 3, 1, 1, bias=True))
 
-    def forward(self, x1, x2):
-        """Flow from x1 to x2, [n,2,h,w]; convs and resizes on the HIP kernels."""
+    def forward(self, x1, x2, exact_tanh=False):
+        """Flow from x1 to x2, [n,2,h,w]; convs and resizes on the HIP kernels.  exact_tanh (the training forward): the flow head's tanh to
+        float32 accuracy.  The conv epilogue's tanh is accurate to 3e-7 absolute, which the factor 256 makes 5e-6 px of flow -- nine times
+        a float32 graph's error, and every gradient of the recurrence depends on the bilinear cells the flow selects."""
         _, _, h, w = x1.shape
         o = None
         for blk in (self.encoder1, self.encoder2, self.encoder3):
@@ -196,7 +199,11 @@ class FNet(nn.Module):
         for blk in (self.decoder1, self.decoder2, self.decoder3):
             o = _run(blk[2], _run(blk[0], o, "relu"), "relu")
             o = ops.upsample_bilinear(o, scale_factor=2)
-        o = _run(self.flow[2], _run(self.flow[0], o, "relu"), "tanh", 256.0)
+        o, head = _run(self.flow[0], o, "relu"), self.flow[2]
+        if exact_tanh:
+            o = torch.tanh(_run(head, o)) * 256.0
+        else:
+            o = _run(head, o, "tanh", 256.0)
         return ops.upsample_bilinear(o, size=(h, w))
 
 
@@ -269,6 +276,13 @@ class SPyNet(nn.Module):
             warped = flow_warp(supps[level], flow_up.permute(0, 2, 3, 1).contiguous(), padding_mode='border')
             flow = flow_up + self.basic_module[level](torch.cat([refs[level], warped, flow_up], 1))
         return flow
+
+
+def _refuse_training(model):
+    """The training path exists for CRFP_DSV alone: every other model class refuses ``trainable = True``."""
+    if getattr(model, "trainable", False):
+        raise NotImplementedError(f"crfp_amd: {type(model).__name__} has no training path (trainable = True): forward_train is "
+                                  "implemented for CRFP_DSV")
 
 
 class _ClipEngine(PackedModel):
@@ -347,6 +361,9 @@ class CRFP_DSV(nn.Module, _ClipEngine):
         self.on_overflow = "poison"   # "poison" | "fallback" | "raise" when an activation leaves the fp16 operand range
         self.storage = "f32"          # "f32" | "bf16": activation / state storage in HBM (BASELINE configs 3-5 are bf16)
         self.inputs_resident = False  # streaming only: the frame tensors are complete before each call (CRFP_DSV_INPUTS_RESIDENT, engine.py)
+        self.trainable = False        # True: under grad mode ``forward`` is ``forward_train`` (per-operator HIP calls with the graph kept)
+
+    _trainable_class = True   # forward_train exists for this wiring (the subclasses with another wiring or a streaming forward: False)
 
     def compute_flow(self, lrs):
         n, t, c, h, w = lrs.shape
@@ -356,11 +373,35 @@ class CRFP_DSV(nn.Module, _ClipEngine):
             return self.spynet(cur.contiguous(), prev.contiguous()).view(n, t - 1, 2, h, w), None
         return self.engine().compute_flow(cur, prev).view(n, t - 1, 2, h, w), None
 
-    @torch.no_grad()
+    def _module_flow(self, lrs):
+        """compute_flow through ``self.spynet`` (the FNet module mirror: per-operator calls that carry a graph), whatever engine exists."""
+        n, t, c, h, w = lrs.shape
+        return self.spynet(lrs[:, 1:].reshape(-1, c, h, w).contiguous(), lrs[:, :-1].reshape(-1, c, h, w).contiguous(),
+                           exact_tanh=True).view(n, t - 1, 2, h, w)
+
     def forward(self, lrs, fvs, mks):
-        if not self.has_engine():
-            return self.forward_composed(lrs, fvs, mks)
-        return self.engine().forward(lrs, fvs, mks)
+        grad_mode = torch.is_grad_enabled()   # read before the no-grad region below
+        if self.trainable:
+            if not self._trainable_class:
+                _refuse_training(self)
+            if grad_mode:
+                return self.forward_train(lrs, fvs, mks)
+        with torch.no_grad():
+            if not self.has_engine():
+                return self.forward_composed(lrs, fvs, mks)
+            return self.engine().forward(lrs, fvs, mks)
+
+    def forward_train(self, lrs, fvs, mks):
+        """The training forward: forward_composed's recurrence (model/CRFP.py:1510-1686, the ``y_only`` base included) with the autograd graph
+        kept -- every convolution, warp, resize, pool and deformable convolution a per-operator HIP call with a HIP backward -- for any
+        mid_channels, with or without a one-call engine.  The flow comes from ``self.spynet`` (the FNet module mirror, its flow head's
+        tanh to float32 accuracy), never from the engine, so the flow net trains and the gradient passes through the flow.  ``hr_dcn=False`` / ``offset_prop=False`` behave as in
+        forward_composed.  The packed weights are marked stale (``invalidate_packed``): the engines cache them and an optimizer writes
+        parameters in place, so the next engine call repacks."""
+        if not self._trainable_class:
+            raise NotImplementedError(f"crfp_amd: {type(self).__name__} has no training path: forward_train is implemented for CRFP_DSV")
+        self.invalidate_packed()
+        return self._composed(lrs, fvs, mks, module_flow=True)[0]
 
     @torch.no_grad()
     def forward_composed(self, lrs, fvs, mks):
@@ -373,10 +414,11 @@ class CRFP_DSV(nn.Module, _ClipEngine):
         tensors on the device; concatenations ride as the second input of the consuming conv where the operator has one."""
         return self._composed(lrs, fvs, mks)[0]
 
-    def _composed(self, lrs, fvs, mks, state=None, prev_lr=None):
+    def _composed(self, lrs, fvs, mks, state=None, prev_lr=None, module_flow=False):
         """forward_composed's loop from a given recurrent state -- (the 8x state [n, last, 8h, 8w], the three carried level tensors) -- and the
         LR frame [n, 3, h, w] in front of lrs[:, 0] (both None: a clip starts from nothing) -> (out [n, t, 3|1, 8h, 8w], the state after the
-        last frame).  The streaming model of the CRFP_DSV_CRA wiring carries the two between calls."""
+        last frame).  The streaming model of the CRFP_DSV_CRA wiring carries the two between calls.  module_flow: the flow from
+        ``_module_flow`` (forward_train) instead of ``compute_flow``."""
         if lrs.dim() != 5 or not lrs.is_cuda:
             raise RuntimeError("crfp_amd: forward_composed needs CUDA/HIP tensors lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], mks[n,t,1,8h,8w]")
         n, t, _, h, w = lrs.shape
@@ -386,7 +428,7 @@ class CRFP_DSV(nn.Module, _ClipEngine):
         # flows[:, i] belongs to frame i + 1 of the clip; with a previous frame it is prepended and frame i uses flows[:, i]
         ext = lrs if prev_lr is None else torch.cat((prev_lr.float()[:, None], lrs), 1)
         shift = 1 if prev_lr is None else 0
-        flows = self.compute_flow(ext)[0] if ext.shape[1] > 1 else None
+        flows = (self._module_flow(ext) if module_flow else self.compute_flow(ext)[0]) if ext.shape[1] > 1 else None
         flat = lrs.reshape(n * t, 3, h, w)
         up8_all = ops.upsample_bilinear(flat, scale_factor=8)                               # :1538
         x_lr = self.encoder_lr(flat, islr=True)[2].view(n, t, m, h, w)                      # :1540
@@ -491,6 +533,7 @@ class CRFP_DSV_CRA(CRFP_DSV):
     call is MRCF_simple_v18_cra's."""
 
     _engine_class = CRAEngine
+    _trainable_class = False
 
     def __init__(self, device, mid_channels=16, y_only=False, hr_dcn=True, offset_prop=True, spynet_pretrained=None):
         super().__init__(device, mid_channels, y_only, hr_dcn, offset_prop, spynet_pretrained)
@@ -540,6 +583,7 @@ class CRFP_simple(nn.Module, _ClipEngine):
 
     dense = False
     _engine_class = SimpleEngine
+    trainable = False   # the training path exists for CRFP_DSV alone: True makes forward / forward_train raise
 
     def __init__(self, device, mid_channels=16, y_only=False, hr_dcn=True, offset_prop=True, spynet_pretrained=None):
         super().__init__()
@@ -580,8 +624,12 @@ class CRFP_simple(nn.Module, _ClipEngine):
 
     init_weights = CRFP_DSV.init_weights
 
+    def forward_train(self, lrs, fvs, mks):
+        raise NotImplementedError(f"crfp_amd: {type(self).__name__} has no training path: forward_train is implemented for CRFP_DSV")
+
     @torch.no_grad()
     def forward(self, lrs, fvs, mks):
+        _refuse_training(self)
         if not self.has_engine():
             return self.forward_composed(lrs, fvs, mks)
         return self.engine().forward(lrs, fvs, mks)
@@ -678,7 +726,10 @@ class MRCF_simple_v18(CRFP_DSV):
             raise NotImplementedError("split_ratio 3 only (the reference's shipped configuration)")
         super().__init__(device, mid_channels, y_only, hr_dcn, offset_prop, spynet_pretrained)
 
+    _trainable_class = False
+
     def forward(self, lrs, fvs, mks, fgs=None):
+        _refuse_training(self)
         return self.forward_stream(lrs, fvs, mks, fgs)
 
 
@@ -703,6 +754,7 @@ class _AblationStream:
     @torch.no_grad()
     def forward(self, lrs, fvs, mks, fgs=None):
         """lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], mks / fgs[n,t,1,8h,8w] -> [n,t,3|1,8h,8w], continuing the sequence of the previous call."""
+        _refuse_training(self)
         if not self.has_engine():
             out, self._stream_state = self._composed(lrs, fvs, mks, self._stream_state, self._stream_prev)
             self._stream_prev = lrs[:, -1].float().clone()   # a copy, as the reference's pre_lrs (:1299-1304)

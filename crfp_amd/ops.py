@@ -174,9 +174,9 @@ def dcnv2(x, offset, mask, weight, bias, kernel_size=3, padding=1, dilation=1, d
     """Drop-in for ``dcn_v2.DCNv2.forward`` (reference model/CRFP.py:350), forward and backward.  With grad mode on and at least one of
     the five tensors requiring grad the result carries a ``grad_fn`` whose backward is crfp_dcnv2_backward_f32 (fp32, first order only;
     grad_input is an unordered float atomic sum, the other four gradients are bitwise reproducible); otherwise this is the plain
-    forward call.  ``dcnv2_shared``, ``flow_warp``, ``conv3x3`` and ``conv3x3_ex`` have a backward of their own in the same mould; the
-    other wrappers of this module (``dcnv2_g8_packed``, the ``*_packed`` / ``*_unpacked`` convs, ``convkxk``, ``fovea_head``, the
-    resamplers) are forward-only."""
+    forward call.  ``dcnv2_shared``, ``flow_warp``, ``conv3x3``, ``conv3x3_ex``, ``upsample_bilinear``, ``avgpool2`` and ``charbonnier``
+    have a backward of their own in the same mould; the other wrappers of this module (``dcnv2_g8_packed``, the ``*_packed`` /
+    ``*_unpacked`` convs, ``convkxk``, ``fovea_head``, ``upsample_bilinear_ac``) are forward-only."""
     x, offset, mask = _dev(x, "input"), _dev(offset, "offset"), _dev(mask, "mask")
     weight, bias = _dev(weight, "weight"), _dev(bias, "bias")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, offset, mask, weight, bias)):
@@ -444,7 +444,9 @@ def conv3x3_unpacked(x, weight, bias, act="none", post_scale=1.0):
 
 
 def upsample_bilinear(x, scale_factor=None, size=None, mul=1.0):
-    """nn.Upsample(scale_factor=.., 'bilinear', align_corners=False) or F.interpolate(size=..)."""
+    """nn.Upsample(scale_factor=.., 'bilinear', align_corners=False) or F.interpolate(size=..), times ``mul``; forward and backward.  With
+    grad mode on and ``x`` requiring grad the result carries a ``grad_fn`` whose backward is crfp_upsample_bilinear_backward_f32 (fp32,
+    first order only, bitwise reproducible); otherwise this is the plain forward call."""
     x = _dev(x, "x")
     n, c, h, w = x.shape
     if scale_factor is not None:
@@ -455,11 +457,39 @@ def upsample_bilinear(x, scale_factor=None, size=None, mul=1.0):
         # PyTorch computes in/out in float32 when only a size is given
         sh = float(torch.tensor(h, dtype=torch.float32) / torch.tensor(oh, dtype=torch.float32))
         sw = float(torch.tensor(w, dtype=torch.float32) / torch.tensor(ow, dtype=torch.float32))
+    if _needs_grad(x):
+        return _UpsampleBilinearFunction.apply(x, int(oh), int(ow), sh, sw, float(mul))
+    return _upsample_bilinear_forward(x, oh, ow, sh, sw, mul)
+
+
+def _upsample_bilinear_forward(x, oh, ow, sh, sw, mul):
+    """crfp_upsample_bilinear_f32 on a float32, contiguous device tensor."""
+    n, c, h, w = x.shape
     out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
     with _on(x):
         _lib.check(_lib.lib().crfp_upsample_bilinear_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, oh, ow, sh, sw,
                                                          float(mul), _stream()), "crfp_upsample_bilinear_f32")
     return out
+
+
+class _UpsampleBilinearFunction(torch.autograd.Function):
+    """``upsample_bilinear`` under autograd: forward = ``_upsample_bilinear_forward``, backward = crfp_upsample_bilinear_backward_f32."""
+
+    @staticmethod
+    def forward(ctx, x, oh, ow, sh, sw, mul):
+        ctx.cfg = (tuple(x.shape), oh, ow, sh, sw, mul)
+        return _upsample_bilinear_forward(x, oh, ow, sh, sw, mul)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (n, c, h, w), oh, ow, sh, sw, mul = ctx.cfg
+        grad_out = _dev(grad_out, "grad_out")
+        gx = torch.empty((n, c, h, w), dtype=torch.float32, device=grad_out.device)
+        with _on(grad_out):
+            _lib.check(_lib.lib().crfp_upsample_bilinear_backward_f32(grad_out.data_ptr(), gx.data_ptr(), n, c, h, w, oh, ow, sh, sw, mul,
+                                                                      _stream()), "crfp_upsample_bilinear_backward_f32")
+        return gx, None, None, None, None, None
 
 
 def sq_err_sums(a, b):
@@ -474,13 +504,100 @@ def sq_err_sums(a, b):
 
 
 def avgpool2(x):
-    """nn.AvgPool2d(2, 2) (floor mode) on an NCHW tensor."""
+    """nn.AvgPool2d(2, 2) (floor mode) on an NCHW tensor, forward and backward.  With grad mode on and ``x`` requiring grad the result
+    carries a ``grad_fn`` whose backward is crfp_avgpool2_backward_f32; otherwise this is the plain forward call."""
     x = _dev(x, "x")
+    if _needs_grad(x):
+        return _AvgPool2Function.apply(x)
+    return _avgpool2_forward(x)
+
+
+def _avgpool2_forward(x):
+    """crfp_avgpool2_f32 on a float32, contiguous device tensor."""
     n, c, h, w = x.shape
     out = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
     with _on(x):
         _lib.check(_lib.lib().crfp_avgpool2_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, _stream()), "crfp_avgpool2_f32")
     return out
+
+
+class _AvgPool2Function(torch.autograd.Function):
+    """``avgpool2`` under autograd: forward = ``_avgpool2_forward``, backward = crfp_avgpool2_backward_f32."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.shape = tuple(x.shape)
+        return _avgpool2_forward(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        n, c, h, w = ctx.shape
+        grad_out = _dev(grad_out, "grad_out")
+        gx = torch.empty((n, c, h, w), dtype=torch.float32, device=grad_out.device)
+        with _on(grad_out):
+            _lib.check(_lib.lib().crfp_avgpool2_backward_f32(grad_out.data_ptr(), gx.data_ptr(), n, c, h, w, _stream()),
+                       "crfp_avgpool2_backward_f32")
+        return gx
+
+
+def charbonnier(pred, target, weight=None, eps=1e-12):
+    """The raw material of the reference's masked Charbonnier loss (loss/loss.py:26-68,115-124) in one pass: ``sums[n, 2]`` (float64, on the
+    device) = per sample (sum sqrt((pred - target)^2 + eps) * weight, sum weight), the weight [n,1,h,w] or [n,c,h,w] expanded over the
+    channels (none: the second column is the element count).  Forward and backward: with grad mode on and ``pred`` or ``target`` requiring
+    grad the result carries a ``grad_fn`` whose backward is crfp_charbonnier_backward_f32 on the upstream gradient of ``sums[:, 0]`` (the
+    gradient of ``target`` is the negation of ``pred``'s; the weight gets none).  crfp_amd.loss builds the reductions on it."""
+    pred, target = _dev(pred, "pred"), _dev(target, "target")
+    if pred.dim() != 4 or tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"charbonnier: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be the same [n, c, h, w]")
+    if weight is not None:
+        weight = _dev(weight, "weight")
+        n, c, h, w = pred.shape
+        if tuple(weight.shape) not in ((n, 1, h, w), (n, c, h, w)):
+            raise ValueError(f"charbonnier: weight {tuple(weight.shape)} must be [n, 1, h, w] or [n, c, h, w]")
+    if _needs_grad(pred, target):
+        return _CharbonnierFunction.apply(pred, target, weight, float(eps))
+    return _charbonnier_forward(pred, target, weight, float(eps))
+
+
+def _charbonnier_forward(pred, target, weight, eps):
+    """crfp_charbonnier_f32 on float32, contiguous device tensors."""
+    n, c, h, w = pred.shape
+    L = _lib.lib()
+    sums = torch.empty((n, 2), dtype=torch.float64, device=pred.device)
+    with _on(pred, target, weight):
+        nb = L.crfp_charbonnier_workspace_bytes(n, c, h, w)
+        if nb == 0:
+            _lib.check(-3, "crfp_charbonnier_workspace_bytes")
+        ws = _ws(nb, pred.device)
+        _lib.check(L.crfp_charbonnier_f32(pred.data_ptr(), target.data_ptr(), None if weight is None else weight.data_ptr(),
+                                          0 if weight is None else weight.shape[1], sums.data_ptr(), n, c, h, w, eps, ws.data_ptr(), ws.numel(),
+                                          _stream()), "crfp_charbonnier_f32")
+    return sums
+
+
+class _CharbonnierFunction(torch.autograd.Function):
+    """``charbonnier`` under autograd: forward = ``_charbonnier_forward``, backward = crfp_charbonnier_backward_f32 with scale = the upstream
+    gradient of sums[:, 0] (float32, made on the device: no host sync)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, eps):
+        ctx.save_for_backward(pred, target, weight)
+        ctx.eps = eps
+        return _charbonnier_forward(pred, target, weight, eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sums):
+        pred, target, weight = ctx.saved_tensors
+        n, c, h, w = pred.shape
+        scale = grad_sums[:, 0].to(torch.float32).contiguous()
+        gp = torch.empty_like(pred)
+        with _on(pred, target, weight, scale):
+            _lib.check(_lib.lib().crfp_charbonnier_backward_f32(pred.data_ptr(), target.data_ptr(), None if weight is None else weight.data_ptr(),
+                                                                0 if weight is None else weight.shape[1], scale.data_ptr(), gp.data_ptr(),
+                                                                n, c, h, w, ctx.eps, _stream()), "crfp_charbonnier_backward_f32")
+        return (gp if ctx.needs_input_grad[0] else None), (-gp if ctx.needs_input_grad[1] else None), None, None
 
 
 def fovea_head(state, x_hr, mask, lr, w_tttf, b_tttf, w_last, b_last, y_only=False):

@@ -182,12 +182,19 @@ def make_clip(seed: int, n: int, t: int, h: int, w: int, fv_size: int = 96, sigm
     ``fv_size`` window whose centre follows a gaze walk N(centre, sigma_t) (reference
     test_video.py:309-343), zero elsewhere (reference dataset/reds.py:196-203); ``mks`` is the
     bool window mask.  Returns float32 lrs[n,t,3,h,w], fvs[n,t,3,8h,8w], bool mks[n,t,1,8h,8w]."""
+    return make_clip_hr(seed, n, t, h, w, fv_size, sigma_t, max_shift_hr)[:3]
+
+
+def make_clip_hr(seed: int, n: int, t: int, h: int, w: int, fv_size: int = 96, sigma_t: float = 10.0, max_shift_hr: int = 16):
+    """``make_clip`` plus the HR frames it downsamples -- the training target: (lrs, fvs, mks, hrs[n,t,3,8h,8w] float32 in [0, 1]).  Same
+    random stream, so the first three are make_clip's bit for bit."""
     rs = np.random.RandomState(seed)
     H, W = 8 * h, 8 * w
     fv = min(fv_size, H, W)
     lrs = np.zeros((n, t, 3, h, w), np.float32)
     fvs = np.zeros((n, t, 3, H, W), np.float32)
     mks = np.zeros((n, t, 1, H, W), np.bool_)
+    hrs = np.zeros((n, t, 3, H, W), np.float32)
     for b in range(n):
         scene = _smooth_field(rs, 3, H, W)
         scene += rs.uniform(-0.05, 0.05, scene.shape)
@@ -196,6 +203,7 @@ def make_clip(seed: int, n: int, t: int, h: int, w: int, fv_size: int = 96, sigm
             sy += int(rs.randint(-max_shift_hr, max_shift_hr + 1))
             sx += int(rs.randint(-max_shift_hr, max_shift_hr + 1))
             hr = np.roll(scene, (sy, sx), axis=(1, 2))
+            hrs[b, i] = np.clip(hr, 0, 1).astype(np.float32)
             lr = hr.reshape(3, h, 8, w, 8).mean(axis=(2, 4))
             lr = lr + rs.uniform(-0.02, 0.02, lr.shape)
             lrs[b, i] = np.clip(lr, 0, 1).astype(np.float32)
@@ -204,4 +212,4 @@ def make_clip(seed: int, n: int, t: int, h: int, w: int, fv_size: int = 96, sigm
             y0, x0 = cy - fv // 2, cx - fv // 2
             mks[b, i, 0, y0:y0 + fv, x0:x0 + fv] = True
             fvs[b, i, :, y0:y0 + fv, x0:x0 + fv] = np.clip(hr[:, y0:y0 + fv, x0:x0 + fv], 0, 1)
-    return lrs, fvs, mks
+    return lrs, fvs, mks, hrs

@@ -30,6 +30,8 @@
  *   crfp_dcnv2_backward_f32   the same extension's backward (autograd of self.dcn(pre_x, offset, mask), model/CRFP.py:350)
  *   crfp_conv3x3_f32          every nn.Conv2d(k=3,s=1,p=1) on the path (e.g. model/CRFP.py:48-50,303-317)
  *   crfp_conv3x3_ex_backward_f32  autograd of those convs with their activation, cat and pixel (un)shuffle (ATen convolution_backward)
+ *   crfp_upsample_bilinear_backward_f32 / crfp_avgpool2_backward_f32  autograd of those resizes and of nn.AvgPool2d(2, 2)
+ *   crfp_charbonnier_f32 / _backward_f32  loss/loss.py:26-68,115-124 (masked Charbonnier loss and its autograd)
  *   crfp_upsample_bilinear_f32  nn.Upsample / F.interpolate(align_corners=False) (model/CRFP.py:808-812,1471-1478)
  *   crfp_fnet_*               model/CRFP.py:743-814  FNet.forward, :1483-1508 compute_flow
  *   crfp_dsv_*                model/CRFP.py:1387-1706 CRFP_DSV (ctor weights, forward) and the
@@ -242,6 +244,33 @@ int crfp_psnr_partial_f32(const float* a, const float* b, double* acc, int n, in
 
 /* nn.AvgPool2d(2, 2), floor mode (FNet, model/CRFP.py:755): x [n,c,h,w] -> out [n,c,h/2,w/2]. */
 int crfp_avgpool2_f32(const float* x, float* out, int n, int c, int h, int w, void* stream);
+
+/* ---- backward of crfp_upsample_bilinear_f32 (scale and size mode, downscaling included): grad_x [n,c,h,w] = the adjoint of the
+ * forward applied to grad_out [n,c,oh,ow], times mul.  A gather: every input pixel walks the outputs whose footprint can hold it and
+ * keeps those for which the forward's own source-index function names it, with the forward's weight bits; at a clamped edge both
+ * weights of an output land on one input and both are added.  An input no output reads gets an exact zero; grad_x needs no clear.
+ * fp32, no atomics, bitwise reproducible.  A null pointer, a size < 1 or a scale that is not positive and finite: CRFP_E_BADARG.
+ * n * c > 65535, h > 262140, a size above 2^30 or more than 2^58 elements: CRFP_E_UNSUPPORTED.  Refusals precede any HIP call. */
+int crfp_upsample_bilinear_backward_f32(const float* grad_out, float* grad_x, int n, int c, int h, int w, int oh, int ow,
+                                        float scale_h, float scale_w, float mul, void* stream);
+
+/* backward of crfp_avgpool2_f32: grad_x[y][x] = 0.25 * grad_out[y/2][x/2] inside the pooled area, an exact zero on the odd trailing
+ * row / column floor mode drops.  A null pointer, n or c < 1, h or w < 2: CRFP_E_BADARG; the limits above: CRFP_E_UNSUPPORTED. */
+int crfp_avgpool2_backward_f32(const float* grad_out, float* grad_x, int n, int c, int h, int w, void* stream);
+
+/* ---- masked Charbonnier loss (loss/loss.py:26-68,115-124) in one pass over pred and target [n,c,h,w]: sums[n][2] (float64, device) =
+ * per sample (sum sqrt(d^2 + eps) * w, sum w) with d = pred - target and w the weight expanded over c (1 without a weight: the second
+ * sum is then the element count).  weight: NULL with weight_c = 0, [n,1,h,w] with weight_c = 1, or [n,c,h,w] with weight_c = c.
+ * Elements in fp32, sums in float64 through per-workgroup partials in the workspace added in a fixed order: bitwise reproducible, no
+ * atomics; sums needs no clear.  The backward writes grad_pred = scale[sample] * w * d / sqrt(d^2 + eps); scale is n floats on the
+ * device (the upstream gradient of sums[:, 0]).  A null pointer, a size < 1, a weight_c that does not fit, eps negative or not finite:
+ * CRFP_E_BADARG.  n > 65535 or more than 2^58 elements: CRFP_E_UNSUPPORTED (size query 0).  A missing or short workspace:
+ * CRFP_E_WORKSPACE.  Refusals precede any HIP call. */
+size_t crfp_charbonnier_workspace_bytes(int n, int c, int h, int w);
+int crfp_charbonnier_f32(const float* pred, const float* target, const float* weight, int weight_c, double* sums, int n, int c, int h,
+                         int w, float eps, void* workspace, size_t workspace_bytes, void* stream);
+int crfp_charbonnier_backward_f32(const float* pred, const float* target, const float* weight, int weight_c, const float* scale,
+                                  float* grad_pred, int n, int c, int h, int w, float eps, void* stream);
 
 /* Fovea fusion + output head of one frame, fused (model/CRFP.py:1672-1684):
  *   f' = conv_tttf(cat(state, x_hr)); new_state = LeakyReLU_0.1(mask ? f' : state); out = conv_last(new_state) + bilinear_x8(lr)

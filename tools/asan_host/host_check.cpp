@@ -5,6 +5,7 @@
 // sizes), the parameter tables, and every argument-error path (tests/test_host_logic.py::test_argument_errors_do_not_touch_the_gpu,
 // test_sizes_are_sane).  Exit code 0 = every expectation held and no sanitizer report was raised.
 #include "../../include/crfp_hip.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -424,6 +425,59 @@ int main(int argc, char** argv) {
                                                           1, 1.0f, v[6], v[7], p16, ws, nullptr) == 0);
         }
         EXPECT(crfp_stub_launches() == l0 + 18 + 7 * 6);
+    }
+    // the resize / pool backward and the Charbonnier loss: every refusal before the first launch, then the launches a good call takes
+    {
+        const long l0 = crfp_stub_launches();
+        EXPECT(crfp_upsample_bilinear_backward_f32(nullptr, p16, 1, 1, 2, 2, 4, 4, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, nullptr, 1, 1, 2, 2, 4, 4, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_BADARG);
+        const int bad_up[6][6] = {{0, 1, 2, 2, 4, 4}, {1, 0, 2, 2, 4, 4}, {1, 1, 0, 2, 4, 4}, {1, 1, 2, -1, 4, 4}, {1, 1, 2, 2, 0, 4}, {1, 1, 2, 2, 4, 0}};
+        for (const auto& v : bad_up) EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, v[0], v[1], v[2], v[3], v[4], v[5], 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_BADARG);
+        const float bad_scale[5] = {0.0f, -0.5f, NAN, INFINITY, -INFINITY};
+        for (const float sc : bad_scale) {
+            EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 1, 1, 2, 2, 4, 4, sc, 0.5f, 1.0f, nullptr) == CRFP_E_BADARG);
+            EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 1, 1, 2, 2, 4, 4, 0.5f, sc, 1.0f, nullptr) == CRFP_E_BADARG);
+        }
+        EXPECT(std::strstr(crfp_last_error_string(), "positive and finite") != nullptr);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 65536, 1, 2, 2, 4, 4, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 256, 256, 2, 2, 4, 4, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 1, 1, 262141, 2, 4, 4, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 1, 1, 2, (1 << 30) + 1, 4, 4, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 65535, 1, 2, 2, 1 << 30, 1 << 30, 0.5f, 0.5f, 1.0f, nullptr) == CRFP_E_UNSUPPORTED);   // 2^58 elements
+        EXPECT(crfp_avgpool2_backward_f32(nullptr, p16, 1, 1, 2, 2, nullptr) == CRFP_E_BADARG && crfp_avgpool2_backward_f32(p16, nullptr, 1, 1, 2, 2, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_avgpool2_backward_f32(p16, p16, 0, 1, 2, 2, nullptr) == CRFP_E_BADARG && crfp_avgpool2_backward_f32(p16, p16, 1, 0, 2, 2, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_avgpool2_backward_f32(p16, p16, 1, 1, 1, 2, nullptr) == CRFP_E_BADARG && crfp_avgpool2_backward_f32(p16, p16, 1, 1, 2, 1, nullptr) == CRFP_E_BADARG);
+        EXPECT(crfp_avgpool2_backward_f32(p16, p16, 65536, 1, 2, 2, nullptr) == CRFP_E_UNSUPPORTED && crfp_avgpool2_backward_f32(p16, p16, 1, 1, 300000, 2, nullptr) == CRFP_E_UNSUPPORTED);
+        const size_t need = crfp_charbonnier_workspace_bytes(2, 3, 9, 11);
+        EXPECT(need >= 2 * 2 * sizeof(double) && crfp_charbonnier_workspace_bytes(1, 3, 1440, 2560) >= need);
+        EXPECT(crfp_charbonnier_workspace_bytes(0, 3, 9, 11) == 0 && crfp_charbonnier_workspace_bytes(2, 0, 9, 11) == 0 && crfp_charbonnier_workspace_bytes(2, 3, -1, 11) == 0);
+        EXPECT(crfp_charbonnier_workspace_bytes(2, 3, 9, 0) == 0 && crfp_charbonnier_workspace_bytes(65536, 3, 9, 11) == 0);
+        EXPECT(crfp_charbonnier_workspace_bytes(65535, 2147483647, 2147483647, 2147483647) == 0);
+        double* const d16 = reinterpret_cast<double*>(p16);
+#define CBF(P, T, W, WC, S, N, C, EPS, WS, WSB) crfp_charbonnier_f32(P, T, W, WC, S, N, C, 9, 11, EPS, WS, WSB, nullptr)
+#define CBB(P, T, W, WC, SC, G, N, C, EPS) crfp_charbonnier_backward_f32(P, T, W, WC, SC, G, N, C, 9, 11, EPS, nullptr)
+        EXPECT(CBF(nullptr, p16, nullptr, 0, d16, 2, 3, 1e-12f, p16, need) == CRFP_E_BADARG && CBF(p16, nullptr, nullptr, 0, d16, 2, 3, 1e-12f, p16, need) == CRFP_E_BADARG);
+        EXPECT(CBF(p16, p16, nullptr, 0, nullptr, 2, 3, 1e-12f, p16, need) == CRFP_E_BADARG && std::strstr(crfp_last_error_string(), "null") != nullptr);
+        EXPECT(CBF(p16, p16, nullptr, 0, d16, 0, 3, 1e-12f, p16, need) == CRFP_E_BADARG && CBF(p16, p16, nullptr, 0, d16, 2, 0, 1e-12f, p16, need) == CRFP_E_BADARG);
+        EXPECT(CBF(p16, p16, nullptr, 1, d16, 2, 3, 1e-12f, p16, need) == CRFP_E_BADARG && CBF(p16, p16, p16, 0, d16, 2, 3, 1e-12f, p16, need) == CRFP_E_BADARG);
+        EXPECT(CBF(p16, p16, p16, 2, d16, 2, 3, 1e-12f, p16, need) == CRFP_E_BADARG && std::strstr(crfp_last_error_string(), "weight_c") != nullptr);
+        EXPECT(CBF(p16, p16, nullptr, 0, d16, 2, 3, -1.0f, p16, need) == CRFP_E_BADARG && CBF(p16, p16, nullptr, 0, d16, 2, 3, NAN, p16, need) == CRFP_E_BADARG);
+        EXPECT(CBF(p16, p16, nullptr, 0, d16, 65536, 3, 1e-12f, p16, (size_t)1 << 40) == CRFP_E_UNSUPPORTED);
+        EXPECT(CBF(p16, p16, nullptr, 0, d16, 2, 3, 1e-12f, nullptr, need) == CRFP_E_WORKSPACE && CBF(p16, p16, nullptr, 0, d16, 2, 3, 1e-12f, p16, need - 1) == CRFP_E_WORKSPACE);
+        EXPECT(CBB(nullptr, p16, nullptr, 0, p16, p16, 2, 3, 1e-12f) == CRFP_E_BADARG && CBB(p16, nullptr, nullptr, 0, p16, p16, 2, 3, 1e-12f) == CRFP_E_BADARG);
+        EXPECT(CBB(p16, p16, nullptr, 0, nullptr, p16, 2, 3, 1e-12f) == CRFP_E_BADARG && CBB(p16, p16, nullptr, 0, p16, nullptr, 2, 3, 1e-12f) == CRFP_E_BADARG);
+        EXPECT(CBB(p16, p16, nullptr, 3, p16, p16, 2, 3, 1e-12f) == CRFP_E_BADARG && CBB(p16, p16, p16, 2, p16, p16, 2, 3, 1e-12f) == CRFP_E_BADARG);
+        EXPECT(CBB(p16, p16, nullptr, 0, p16, p16, 2, 3, INFINITY) == CRFP_E_BADARG && CBB(p16, p16, nullptr, 0, p16, p16, 70000, 3, 1e-12f) == CRFP_E_UNSUPPORTED);
+        EXPECT(crfp_stub_launches() == l0);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 2, 3, 5, 7, 40, 56, 0.125f, 0.125f, 8.0f, nullptr) == 0 && crfp_stub_launches() == l0 + 1);
+        EXPECT(crfp_upsample_bilinear_backward_f32(p16, p16, 1, 1, 262140, 1, 1, 1 << 30, 1e-30f, 3e38f, 1.0f, nullptr) == 0 && crfp_stub_launches() == l0 + 2);
+        EXPECT(crfp_avgpool2_backward_f32(p16, p16, 2, 3, 45, 80, nullptr) == 0 && crfp_stub_launches() == l0 + 3);
+        EXPECT(CBF(p16, p16, nullptr, 0, d16, 2, 3, 1e-12f, p16, need) == 0 && crfp_stub_launches() == l0 + 5);   // partials, then the fixed-order sum
+        EXPECT(CBF(p16, p16, p16, 1, d16, 2, 3, 0.0f, p16, need) == 0 && CBF(p16, p16, p16, 3, d16, 2, 3, 1e-6f, p16, need) == 0 && crfp_stub_launches() == l0 + 9);
+        EXPECT(CBB(p16, p16, nullptr, 0, p16, p16, 2, 3, 1e-12f) == 0 && CBB(p16, p16, p16, 1, p16, p16, 2, 3, 1e-12f) == 0 && crfp_stub_launches() == l0 + 11);
+        EXPECT(crfp_charbonnier_f32(p16, p16, nullptr, 0, d16, 8, 3, 4320, 7680, 1e-12f, p16, crfp_charbonnier_workspace_bytes(8, 3, 4320, 7680), nullptr) == 0);
+#undef CBF
+#undef CBB
     }
     // the DCNv2 backward: sizing, every refusal before the first launch, the launches each subset of wanted outputs takes
     {
